@@ -18,11 +18,18 @@ all-gather, through the C-ABI's own RCCL communicator (cz_comm_init / cz_comm_ba
 The batch, its shards, the communicator and the statistics exchange are `cooking_zoo_amd.ShardedVecEnv` - the same object a user
 gets; this file only times it.
 
-Timing: W warmup steps, then the K-step region is timed `--repeats` times; every region is bracketed by a stream
-synchronisation + barrier over all ranks on both sides, its time is the MAX over ranks, and `value` / `ms_per_step` are
+Timing: W warmup steps (then one untimed K-step region, or for K > 256 one replay of every HIP graph the timed region uses: a
+timed region is never the first of its kind), then the K-step region is timed `--repeats` times (default 1: K timed steps);
+every region is bracketed by a stream synchronisation + barrier over all ranks on both sides, its time is the MAX over ranks, and `value` / `ms_per_step` are
 the MEDIAN over the regions (min and max are reported next to it).  Every timed launch is the boundary-ordered one-step kernel
 `cz::k_step<1,1,2,3,0>` replayed from HIP graphs: `value`, `roofline.kernel_us` and profiles/rNN/kernel_stats.csv (newest round) describe the same
 launches.
+
+A plain run measures the headline only.  `--full` adds everything else the line has carried: the roofline block (its own run of
+event-timed launches), the `sustained` stretch, the extra legs and configs, BASELINE config 4 (N > 1), the check of the RCCL
+statistics all-gather against the control plane, and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step
+returned (observations, rewards, terminations, truncations) as DIR/<name>.npy; the inputs are the same on every run with the same
+arguments, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -627,21 +634,51 @@ def with_deadline(fn, seconds):
     return (not th.is_alive()), box.get("r")
 
 
+DUMP_LIMIT_BYTES = 64 << 20                   # --dump-outputs: bytes written by all ranks together
+
+
+def dump_outputs(out_dir, rank, world, env_id_base, arrays):
+    """--dump-outputs: this rank's outputs of the last timed step as out_dir/<name>.npy (suffix _rank<r> when N > 1), flags as float32.
+    A rank whose rows exceed its share of DUMP_LIMIT_BYTES writes a fixed sample of env rows (seeded, sorted) and their global ids."""
+    arrays = {k: np.asarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items() if v is not None}
+    n = next(iter(arrays.values())).shape[0]
+    per_env = sum(a[0].nbytes for a in arrays.values()) + 8
+    budget = DUMP_LIMIT_BYTES // world
+    if n * per_env > budget:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=(budget - 4096) // per_env, replace=False))     # (4 KB: .npy headers)
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sampled_env_ids"] = (env_id_base + rows).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--repeats", type=int, default=30, help="how many times the K-step region is timed (median reported)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="how many times the K-step region is timed (median reported); the run times steps x repeats steps")
     ap.add_argument("--envs", type=int, default=4096, help="env instances per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, sustained stretch, extra legs and configs, config4 (N > 1), the statistics all-gather check "
+                         "and the CPU baseline; a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline measurement: skip closed_loop / cooking_policy / configs / config4 (profiling runs)")
+                    help="with --full: skip sustained / closed_loop / cooking_policy / configs / config4 (profiling runs)")
     ap.add_argument("--no-obs", action="store_true", help="ablation only: skip the observation encode (INVALID as a result)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float64 / float32, at most "
+                         f"{DUMP_LIMIT_BYTES >> 20} MB in all: a fixed sample of env rows beyond that)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work at all: every rank reports made-up timings so that the launcher / rendezvous / "
                          "aggregation path can be exercised on a machine without GPUs (the line is marked INVALID)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs a real run (a dry run computes nothing)")
+    return args
 
 
 def aggregate(per_rank, K):
@@ -744,7 +781,7 @@ def worker_body(args, rdzv):
                     "stats_total_env_steps": sum(e["stats"]["env_steps"] for e in every),
                     "device_ids": [e["device_id"] for e in every], "env_id_bases": [e["env_id_base"] for e in every]}
             line.update(aggregate(every, K))
-            if world > 1 and not args.no_extras:
+            if world > 1 and args.full and not args.no_extras:
                 line["config4"] = config4_block(world, [e["cfg4"] for e in every], None)
             emit(line)
         return 0
@@ -780,26 +817,40 @@ def worker_body(args, rdzv):
         senv.ring_prepare(K, ring, period, first_slot_of(r), *outs)
     if Wm > 0:
         senv.step_device_ring(Wm, ring, period, 0, *outs)
+    # a timed region is never the first of its kind: K <= 256 - one untimed region (the launches / the graph the first timed region
+    # replays, between the same barriers); longer regions are cut into runs of up to 256 launches (one graph each) that restart at
+    # slot 0 - each of those graphs replayed once (a graph's first replay is slower than the ones after it)
+    if K <= 256:
+        timed_regions(senv, K, 1, ring, outs, first_slot_of)
+    else:
+        for k in sorted({256} | ({K % 256} if K % 256 else set())):
+            senv.step_device_ring(k, ring, period, 0, *outs)
     L.cz_launch_counts(h, None, None, 1)
     elapsed, steps_done = timed_regions(senv, K, R, ring, outs, first_slot_of)
     g_k, d_k = C.c_int64(), C.c_int64()
     L.cz_launch_counts(h, C.byref(g_k), C.byref(d_k), 0)
+    if args.dump_outputs:                                  # (before anything else steps the batch and overwrites the outputs)
+        dump_outputs(args.dump_outputs, rank, world, senv.local_begin,
+                     {"obs": None if args.no_obs else s_obs.to_host(), "rewards": s_rew.to_host(), "terminations": s_term.to_host(),
+                      "truncations": s_trunc.to_host()})
+    mine = {"elapsed_s": elapsed, "env_steps": steps_done}
 
     # dominant-kernel duration: HIP events on the kernels' own stream around max(R*K, 4000) of the SAME launches issued back to back
     # (the host <-> GPU round trip of a synchronised region, ~20 us on this platform whatever K is, is not kernel time)
-    ev_ms = C.c_float()
-    n_ev = max(R * K, 4000)
-    senv.ring_prepare(n_ev, ring, period, 0, *outs)
-    senv.barrier()
-    _native.check(h, L.cz_timer_start(h))
-    env.step_device_ring(n_ev, d_actions, env.num_envs * 2, period, 0, None if args.no_obs else d_obs, d_rew, d_term, d_trunc)
-    _native.check(h, L.cz_timer_stop(h, C.byref(ev_ms)))       # event after the last launch, synchronised
-    kernel_us = ev_ms.value * 1e3 / n_ev
-    mine = {"elapsed_s": elapsed, "env_steps": steps_done, "kernel_us": [kernel_us]}
+    if args.full:
+        ev_ms = C.c_float()
+        n_ev = max(R * K, 4000)
+        senv.ring_prepare(n_ev, ring, period, 0, *outs)
+        senv.barrier()
+        _native.check(h, L.cz_timer_start(h))
+        env.step_device_ring(n_ev, d_actions, env.num_envs * 2, period, 0, None if args.no_obs else d_obs, d_rew, d_term, d_trunc)
+        _native.check(h, L.cz_timer_stop(h, C.byref(ev_ms)))       # event after the last launch, synchronised
+        kernel_us = ev_ms.value * 1e3 / n_ev
+        mine["kernel_us"] = [kernel_us]
 
     # ---- a sustained stretch of the headline's launches (a sampler of GPU activity sees the device busy)
     sustained = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         n_s = max(2000, K)
         senv.barrier()
         t0 = time.perf_counter()
@@ -818,7 +869,7 @@ def worker_body(args, rdzv):
     # ---- BASELINE config 4 when there are several ranks: 262144 envs over 8 GPUs = 32768 envs per rank, global env ids (the
     # statistics exchange below is that config's only collective); every rank times the same K-step regions between barriers
     cfg4_every = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         K4, R4 = CFG4_K, 5
         senv4 = ShardedVecEnv(CFG4_ENVS_PER_GPU * world, *WORKLOAD, comm="host", **sharded, **WORKLOAD_KW)
         senv4.reset(return_obs=False)
@@ -833,45 +884,41 @@ def worker_body(args, rdzv):
         b_alg4 = algorithmic_bytes_per_env_step(senv4.shards[0])
         senv4.close()
 
-    # ---- episode statistics: RCCL all-gather over xGMI of one cz_stats per shard (the path's only collective), checked
+    # ---- episode statistics (--full): RCCL all-gather over xGMI of one cz_stats per shard (the path's only collective), checked
     # against the same structs exchanged over the control plane.  The control-plane copy is taken HERE, after every leg that
     # steps this batch (the sustained stretch above included) and with nothing stepping between it and the RCCL gather -
     # a copy taken earlier describes an older batch and can never compare equal (BENCH_r05 left with rc 3).
     senv.sync()
     senv.barrier()
-    mine["stats"] = env.stats()
+    if args.full:
+        mine["stats"] = env.stats()
     every = [json.loads(b) for b in rdzv.all_gather(json.dumps(mine).encode())]
     stats_all = {}
     rc = 0
-    if comm_ok:
-        done, res = with_deadline(senv.stats_per_shard, COMM_DEADLINE_S)
-        if not done:
-            stats_all["cz_stats_allgather"] = f"timed out after {COMM_DEADLINE_S:.0f} s"
-            rc = EXIT_COMM_FAILED
-        elif isinstance(res, Exception):
-            stats_all["cz_stats_allgather"] = "failed: " + str(res)
-            rc = EXIT_COMM_FAILED
-        else:
-            same = res == [e["stats"] for e in every]
-            stats_all["cz_stats_allgather"] = "ok, identical to the control-plane gather" if same else "ok, but DIFFERENT from the control-plane gather"
-            stats_all["total"] = czd.reduce_stats(res)
-            if not same:
+    if args.full:
+        if comm_ok:
+            done, res = with_deadline(senv.stats_per_shard, COMM_DEADLINE_S)
+            if not done:
+                stats_all["cz_stats_allgather"] = f"timed out after {COMM_DEADLINE_S:.0f} s"
                 rc = EXIT_COMM_FAILED
-    else:
-        stats_all["cz_stats_allgather"] = "communicator not available: " + comm_msg
-        stats_all["total"] = czd.reduce_stats([e["stats"] for e in every])
-        rc = EXIT_COMM_FAILED
+            elif isinstance(res, Exception):
+                stats_all["cz_stats_allgather"] = "failed: " + str(res)
+                rc = EXIT_COMM_FAILED
+            else:
+                same = res == [e["stats"] for e in every]
+                stats_all["cz_stats_allgather"] = "ok, identical to the control-plane gather" if same else "ok, but DIFFERENT from the control-plane gather"
+                stats_all["total"] = czd.reduce_stats(res)
+                if not same:
+                    rc = EXIT_COMM_FAILED
+        else:
+            stats_all["cz_stats_allgather"] = "communicator not available: " + comm_msg
+            stats_all["total"] = czd.reduce_stats([e["stats"] for e in every])
+            rc = EXIT_COMM_FAILED
     flags = [int(b) for b in rdzv.all_gather(str(rc).encode())]     # every rank leaves with the same code
     rc = max(flags)
 
     if rank == 0:
         agg = aggregate(every, K)
-        # the floor of a launch that has to emit this much output: same grid shape, nothing but the stores
-        out_only_us = None
-        if not args.no_obs:
-            us = C.c_float()
-            if L.cz_probe_output_only(h, d_obs.ptr, N * 2 * env.F * 8, 500, C.byref(us)) == 0:
-                out_only_us = float(us.value)
         rccl_path, hip_path = C.create_string_buffer(512), C.create_string_buffer(512)
         L.cz_runtime_paths(rccl_path, hip_path, 512)
         b_alg = algorithmic_bytes_per_env_step(env)
@@ -879,16 +926,6 @@ def worker_body(args, rdzv):
                f"by launch boundaries; of the {g_k.value + d_k.value} timed launches 0 went out as overlapped launches (that mode was removed in "
                f"round 5), {g_k.value} were replayed from HIP graphs of {K if K <= 256 else 'up to 256'} launches and {d_k.value} launched "
                f"directly; actions/obs/rewards/flags resident in HBM")
-        roof = roofline_block(b_alg, N, kernel_us, "cz::k_step<1,1,2,3,0> (one wavefront per env, 8 envs per workgroup)",
-                              f"HIP events on the kernels' stream around {n_ev} launches issued back to back (graph replay, ordered by launch "
-                              f"boundaries) - the launches `value` times -, divided by the number of launches; rocprofv3 --kernel-trace of the same "
-                              f"command: {latest_profile('kernel_stats.csv')}", "k_step<1,1,2,3,0>")
-        roof["traffic"] = pmc_traffic(f"k_step_{N}")
-        roof["traffic_from"] = f"rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE separately) of the same kernel: {latest_profile('traffic.json')}"
-        # measured on this box, same run: a kernel of the same grid shape that ONLY writes the observation bytes (write-through
-        # 16-byte stores); write-only traffic does not reach the 8 TB/s read+write peak
-        roof["output_only_launch_us"] = out_only_us
-        roof["frac_of_output_only_launch"] = (out_only_us / kernel_us) if out_only_us else None
         line = {
             "metric": "env-steps/sec at N parallel envs (1/2/4/8 GPU) + achieved HBM GB/s",
             "value": agg["value"], "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": Wm,
@@ -903,36 +940,53 @@ def worker_body(args, rdzv):
                                   "actions resident in HBM, device-resident outputs",
                        "envs_per_gpu": N, "parallelism": f"env-sharded x{world} (ShardedVecEnv: {senv.comm_note}), one wavefront per env, one process per GPU, no torch",
                        "api": api},
-            "roofline": roof,
             "achieved_hbm_gbs_end_to_end": b_alg * agg["value"] / 1e9 / world,
             "runtime": {"hip": hip_path.value.decode(), "rccl": rccl_path.value.decode(), "torch_imported": "torch" in sys.modules},
-            "episode_stats_allgather": stats_all,
         }
-        if sustained is not None:
-            line["sustained"] = sustained
-        if not args.no_obs:
-            fused = guarded(leg_fused, env, K)
-            if "error" not in fused:
-                fused["roofline"] = roofline_block(b_alg, N, fused["ms_per_step"] * 1e3, "cz::k_step<1,1,2,3,1> (32 steps per launch)",
-                                                   "wall clock around the cz_rollout launches", "k_step<1,1,2,3,1>")
-            line["fused_rollout"] = fused
-        if cfg4_every is not None:
-            line["config4"] = config4_block(world, cfg4_every, b_alg4)
-        if world == 1 and not args.no_extras and not args.no_obs:
-            # what users get beside the open-loop headline; each leg a fraction of a second of GPU time.  An extra leg must never be
-            # able to lose the headline measured above: whatever it raises is recorded under its key.
-            line["fused_actions"] = guarded(leg_fused_actions, env, K)
-            line["fused_compact"] = guarded(leg_fused_compact, env, K)
-            line["ring_fused"] = guarded(leg_ring_fused, env, K, d_obs, d_rew, d_term, d_trunc)
-            line["closed_loop"] = guarded(leg_closed_loop, env, d_obs, d_rew, d_term, d_trunc)
-            line["closed_loop_compact"] = guarded(leg_closed_loop_compact, env, d_rew, d_term, d_trunc)
-            line["closed_loop_caller_graph"] = guarded(leg_closed_loop_captured, env, d_obs, d_rew, d_term, d_trunc)
-            line["cooking_policy"] = guarded(leg_cooking_policy, local_rank)
-            line["configs"] = guarded(leg_configs, local_rank)
-            if isinstance(line["configs"], dict) and "error" not in line["configs"]:
-                line["configs"]["config4_on_one_gpu"] = guarded(leg_config4_on_one_gpu, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = guarded(cpu_baseline, env)
+        if args.full:
+            # the floor of a launch that has to emit this much output: same grid shape, nothing but the stores
+            out_only_us = None
+            if not args.no_obs:
+                us = C.c_float()
+                if L.cz_probe_output_only(h, d_obs.ptr, N * 2 * env.F * 8, 500, C.byref(us)) == 0:
+                    out_only_us = float(us.value)
+            roof = roofline_block(b_alg, N, kernel_us, "cz::k_step<1,1,2,3,0> (one wavefront per env, 8 envs per workgroup)",
+                                  f"HIP events on the kernels' stream around {n_ev} launches issued back to back (graph replay, ordered by launch "
+                                  f"boundaries) - the launches `value` times -, divided by the number of launches; rocprofv3 --kernel-trace of the same "
+                                  f"command: {latest_profile('kernel_stats.csv')}", "k_step<1,1,2,3,0>")
+            roof["traffic"] = pmc_traffic(f"k_step_{N}")
+            roof["traffic_from"] = f"rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE separately) of the same kernel: {latest_profile('traffic.json')}"
+            # measured on this box, same run: a kernel of the same grid shape that ONLY writes the observation bytes (write-through
+            # 16-byte stores); write-only traffic does not reach the 8 TB/s read+write peak
+            roof["output_only_launch_us"] = out_only_us
+            roof["frac_of_output_only_launch"] = (out_only_us / kernel_us) if out_only_us else None
+            line["roofline"] = roof
+            line["episode_stats_allgather"] = stats_all
+            if sustained is not None:
+                line["sustained"] = sustained
+            if not args.no_obs:
+                fused = guarded(leg_fused, env, K)
+                if "error" not in fused:
+                    fused["roofline"] = roofline_block(b_alg, N, fused["ms_per_step"] * 1e3, "cz::k_step<1,1,2,3,1> (32 steps per launch)",
+                                                       "wall clock around the cz_rollout launches", "k_step<1,1,2,3,1>")
+                line["fused_rollout"] = fused
+            if cfg4_every is not None:
+                line["config4"] = config4_block(world, cfg4_every, b_alg4)
+            if world == 1 and not args.no_extras and not args.no_obs:
+                # what users get beside the open-loop headline; each leg a fraction of a second of GPU time.  An extra leg must never be
+                # able to lose the headline measured above: whatever it raises is recorded under its key.
+                line["fused_actions"] = guarded(leg_fused_actions, env, K)
+                line["fused_compact"] = guarded(leg_fused_compact, env, K)
+                line["ring_fused"] = guarded(leg_ring_fused, env, K, d_obs, d_rew, d_term, d_trunc)
+                line["closed_loop"] = guarded(leg_closed_loop, env, d_obs, d_rew, d_term, d_trunc)
+                line["closed_loop_compact"] = guarded(leg_closed_loop_compact, env, d_rew, d_term, d_trunc)
+                line["closed_loop_caller_graph"] = guarded(leg_closed_loop_captured, env, d_obs, d_rew, d_term, d_trunc)
+                line["cooking_policy"] = guarded(leg_cooking_policy, local_rank)
+                line["configs"] = guarded(leg_configs, local_rank)
+                if isinstance(line["configs"], dict) and "error" not in line["configs"]:
+                    line["configs"]["config4_on_one_gpu"] = guarded(leg_config4_on_one_gpu, local_rank)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = guarded(cpu_baseline, env)
         emit(line)
     sys.stdout.flush()
     try:

@@ -384,14 +384,14 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
                 v[a][i].y = *reinterpret_cast<const double *>(lutb + ((int)b[2 * i + 1] - sb[a][2 * i + 1]));
             }
         const uint32_t f0b = (uint32_t)(chunk * OBS_PAIRS * 128 + 2 * cx.lane) * 8u;      // byte offset of this lane's first pair
-#define CZ_OBS_STORES(AUX)                                                                                                   \
+#define CZ_OBS_WRITE_ROWS(AUX)                                                                                               \
     _Pragma("unroll") for (int i = 0; i < OBS_PAIRS; ++i)                                                                    \
         _Pragma("unroll") for (int a = 0; a < NA; ++a)                                                                       \
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, v[a][i]), rs[a], f0b + (uint32_t)i * 1024u, 0, AUX)
-        if (wt == 1u) { CZ_OBS_STORES(16); }            // sc1: write-through
-        else if (wt == 2u) { CZ_OBS_STORES(2); }        // nt: streaming
-        else { CZ_OBS_STORES(0); }
-#undef CZ_OBS_STORES
+        if (wt == 1u) { CZ_OBS_WRITE_ROWS(16); }            // sc1: write-through
+        else if (wt == 2u) { CZ_OBS_WRITE_ROWS(2); }        // nt: streaming
+        else { CZ_OBS_WRITE_ROWS(0); }
+#undef CZ_OBS_WRITE_ROWS
     }
     // the caller keeps the descriptors of chunk 0 across steps (fused rollout): restore them if later chunks replaced them
     if (P.F > 128 * OBS_PAIRS) load_desc(P, e.layout, 0, cx.lane, dsc);

@@ -39,6 +39,7 @@ def test_gpus_flag_spawns_ranks_and_aggregates():
     assert d["ms_per_step"] == pytest.approx(sorted(1e-3 * (2 + 0.01 * i) * 1e3 / 20 for i in range(5))[2])
     assert d["stats_total_env_steps"] == 2 * 20 * 64 * 5
     assert "DRY RUN" in d["data"]
+    assert "config4" not in d                             # (config 4 is a --full leg)
 
 
 def test_single_rank_goes_through_the_same_path():
@@ -145,7 +146,7 @@ def test_eight_ranks_dry_run_has_config4_and_one_device_per_rank():
     """First-contact insurance for the round-end 8-GPU run (no hardware needed): `bench.py --gpus 8 --dry-run` through
     launch_local - eight fresh rank processes, rendezvous, aggregation - gives one line with n_gpus 8, BASELINE config 4
     (262 144 envs) cut into eight contiguous shards of 32 768 global env ids, and every rank on the device LOCAL_RANK names."""
-    p = _run_bench("--gpus", "8", "--dry-run", "--steps", "20", "--warmup", "5", "--repeats", "3", "--envs", "4096")
+    p = _run_bench("--gpus", "8", "--dry-run", "--full", "--steps", "20", "--warmup", "5", "--repeats", "3", "--envs", "4096")
     assert p.returncode == 0, p.stderr
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -183,7 +184,8 @@ def test_the_drivers_torchrun_command_dry_run():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "CZ_RDZV_DIR", "MASTER_PORT", "MASTER_ADDR"):
         e.pop(k, None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run"],
+                        "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run",
+                        "--full"],
                        capture_output=True, text=True, env=e, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -50,7 +50,7 @@ def test_bench_single_gpu_goes_through_the_multi_rank_code():
     import json, os, subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "7",
-                        "--envs", "1024", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600)
+                        "--envs", "1024", "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert "timed launches 0 went out as overlapped launches" in d["config"]["api"]
@@ -65,14 +65,44 @@ def test_bench_single_gpu_goes_through_the_multi_rank_code():
     assert d["roofline"]["kernel_us"] <= d["ms_per_step"] * 1e3 * 1.05
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps launches, carries the headline keys and none of the --full legs, and
+    --dump-outputs writes the last timed step's outputs - bit for bit the same on a second run with the same arguments."""
+    import json, os, subprocess, sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "5", "--envs", "1024",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 60 and d["repeats"] == 1 and "of the 60 timed launches" in d["config"]["api"]
+    assert d["value"] > 1e6 and d["ms_per_step"] > 0
+    for k in ("roofline", "sustained", "fused_rollout", "closed_loop", "configs", "cpu_baseline", "episode_stats_allgather"):
+        assert k not in d, k
+    F = int(d["config"]["workload"].rsplit("F=", 1)[1])
+    want = {"obs": ((1024, 2, F), np.float64), "rewards": ((1024, 2), np.float64), "terminations": ((1024, 2), np.float32),
+            "truncations": ((1024, 2), np.float32)}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{k}.npy" for k in want)
+    for k, (shape, dtype) in want.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape == shape and a.dtype == dtype, (k, a.shape, a.dtype)
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), k
+    assert np.isfinite(np.load(tmp_path / "a" / "obs.npy")).all()
+
+
 def test_bench_driver_command_exits_zero_with_every_leg():
-    """The driver's own command, extras included (`python bench.py --gpus 1 --steps 20 --warmup 5`, only the CPU baseline left out):
+    """The driver's command with every leg (`python bench.py --gpus 1 --steps 20 --warmup 5 --full`, only the CPU baseline left out):
     exit code 0, and the RCCL all-gather of the statistics equals the control-plane copy although the sustained stretch steps the
     batch after the timed regions (BENCH_r05 left with rc 3: the copy was taken before that stretch)."""
     import json, os, subprocess, sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.returncode, p.stdout[-1500:], p.stderr[-3000:])
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert d["episode_stats_allgather"]["cz_stats_allgather"] == "ok, identical to the control-plane gather"
@@ -112,7 +142,7 @@ def test_bench_two_ranks_on_the_one_device():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "CZ_RDZV_DIR"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--repeats", "5",
-                        "--envs", "2048", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--envs", "2048", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 3 and len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-3000:])
     d = json.loads(lines[0])

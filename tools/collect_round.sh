@@ -7,11 +7,11 @@ R=${1:?round directory name, e.g. r06}
 O=gpurun_out/$R
 rm -rf $O; mkdir -p $O/trace $O/trace_k20 $O/fetch $O/write
 # 1. the bench line, then the same command under a kernel trace: the headline's launches ARE the roofline's kernel
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-timeout 600 python3 bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 400 --warmup 40 --repeats 5 --no-extras --no-cpu-baseline > $O/bench_under_trace.json 2> $O/trace.log
+timeout 900 python3 bench.py --full --repeats 30 > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python3 bench.py --full --repeats 30 --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --steps 400 --warmup 40 --repeats 5 --no-extras --no-cpu-baseline > $O/bench_under_trace.json 2> $O/trace.log
 echo "trace rc=$?"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_k20 -- python3 bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_under_trace_k20.json 2> $O/trace_k20.log
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_k20 -- python3 bench.py --full --repeats 30 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench_under_trace_k20.json 2> $O/trace_k20.log
 echo "trace_k20 rc=$?"
 find $O/trace -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 find $O/trace_k20 -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_k20.csv \;
@@ -49,6 +49,6 @@ if f[0] and w[0]:
 PY
 # 4. the bench line again now that this box's instruction counts exist (issue blocks filled in from this box)
 mkdir -p profiles/$R && cp $O/issue_per_env_step.json profiles/$R/issue_per_env_step.json && cp $O/traffic.json profiles/$R/traffic.json 2>/dev/null
-timeout 900 python3 bench.py > $O/bench_default_with_issue.json 2> /dev/null
+timeout 900 python3 bench.py --full --repeats 30 > $O/bench_default_with_issue.json 2> /dev/null
 rm -rf $O/trace $O/trace_k20 $O/fetch $O/write $O/inst_*_a $O/inst_*_b
 ls -la $O; cat $O/kernel_stats.csv | cut -c1-200 | head -8; cat $O/issue_per_env_step.json
