@@ -227,6 +227,8 @@ struct cz_handle_s {
     void *comm = nullptr;
     int n_ranks = 1, rank = 0;
     int wt_override = -1;          // CZ_WT experiment switch, read once
+    bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
+    int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
     bool huge = false;             // the 256-slot / 1024-cell instance (its own LDS image layout)
     unsigned long long *tl_base = nullptr;   // timeline build: stamp buffer, its capacity in launches, launches so far
     int32_t tl_cap = 0;
@@ -371,6 +373,7 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     P.time_penalty_step = cfg->max_time_penalty / (double)cfg->max_steps;       // cooking_env.py:307
     P.T = 1;
     if (const char *s = getenv("CZ_WT")) h->wt_override = atoi(s);
+    if (const char *s = getenv("CZ_LEAN")) h->lean_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_GRAPHS")) h->graphs_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_GRAPH_MIN_RUN")) h->graph_min_run = atoi(s) < 4 ? 4 : (atoi(s) > 256 ? 256 : atoi(s));   // 4..RING_MAX_GRAPH
     if (const char *s = getenv("CZ_RING_PREFIX")) h->ring_prefix = atoi(s) < 0 ? 0 : (atoi(s) > 16 ? 16 : atoi(s));
@@ -929,7 +932,11 @@ static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, boo
         h->kev_used += 2;
         HIPCHK(h, hipEventRecord(e0, stream));
     }
-    HIPCHK(h, h->kl.step(P, stream, fused ? LAUNCH_FUSED : LAUNCH_ONE));
+    // the lean one-step kernel (k_step_lean, cz_kernels.h) when every setting it fixes at compile time holds for this launch
+    const bool lean = !fused && h->lean_enabled && h->kl.step_lean && P.obs && !P.codes && !P.marks_out && !P.wide && !(P.auto_reset & 2) &&
+                      P.F <= 128 * OBS_PAIRS && P.wt == 1;
+    h->last_step_lean = lean ? 1 : 0;
+    HIPCHK(h, lean ? h->kl.step_lean(P, stream) : h->kl.step(P, stream, fused ? LAUNCH_FUSED : LAUNCH_ONE));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -1057,6 +1064,9 @@ extern "C" int cz_set_compact_output(cz_handle h, uint8_t *d_codes) {
     return 0;
 }
 extern "C" int32_t cz_codes_pitch(cz_handle h) { return h ? codes_pitch(h->P.F) : 0; }
+// diagnostic, not part of cookingzoo.h (tests/test_gpu_lean_step.py): 1 if the most recent step launch issued or captured by the
+// handle was the lean one-step kernel, 0 if another kernel, -1 before the first
+extern "C" int32_t cz_diag_last_step_lean(cz_handle h) { return h ? h->last_step_lean : -1; }
 extern "C" int cz_obs_table(cz_handle h, double *table) {
     if (!h || !table) return fail(h, "cz_obs_table: null argument");
     memcpy(table, h->obs_table, sizeof h->obs_table);

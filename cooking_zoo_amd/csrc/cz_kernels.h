@@ -93,7 +93,7 @@ typedef uint32_t uint2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t uint4_t __attribute__((ext_vector_type(4)));
 
 // Loads are clamped instead of exec-masked (no branches): every address stays inside the record.
-template <int OPL, int CPL, int NA>
+template <int OPL, int CPL, int NA, bool LEAN = false>
 __device__ __forceinline__ void load_env(const Params &P, Env<OPL, CPL, NA> &e, const Ctx &cx, const uint32_t *__restrict__ rec) {
     const uint32_t lane = (uint32_t)cx.lane;
     // header words: wave-uniform, one scalar load (nothing in this kernel writes a record before its loads are done, and the
@@ -126,7 +126,7 @@ __device__ __forceinline__ void load_env(const Params &P, Env<OPL, CPL, NA> &e, 
     e.episode = hw[W_EPISODE]; e.recipes = hw[W_RECIPES]; e.pool = hw[W_POOL];
     // (this test is also where the wave waits for its late scalar arguments -- before any LDS traffic is in flight, which
     // shares the wait counter with scalar loads: measured 0.1 us better than letting the first use wait further down)
-    e.marks_hi = P.wide ? hw[W_MARKS_HI] : 0u;
+    e.marks_hi = !LEAN && P.wide ? hw[W_MARKS_HI] : 0u;
     e.agw = (lane < (uint32_t)NA) ? aw : 0u;
 }
 
@@ -178,10 +178,10 @@ __device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t r
 }
 
 // every recipe of the env from scratch (reset): sets e.marks (and e.marks_hi for wide tables)
-template <int OPL, int CPL, int NA>
+template <int OPL, int CPL, int NA, bool LEAN = false>
 __device__ __forceinline__ void all_marks(const Params &P, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t rowv, Lds<CPL> &s) {
     uint32_t lo = 0, hi = 0;
-    if (__builtin_expect(P.wide != 0, 0)) {
+    if (!LEAN && __builtin_expect(P.wide != 0, 0)) {
 #pragma nounroll
         for (int r = 0; r < P.R; ++r) {
             const uint32_t id = (e.recipes >> (8 * r)) & 0xFFu;
@@ -261,7 +261,9 @@ typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {                       // v_pk_sub_u16: two 16-bit lanes, no borrow across
     return __builtin_bit_cast(uint32_t, (ushort2_t)(__builtin_bit_cast(ushort2_t, a) - __builtin_bit_cast(ushort2_t, b)));
 }
-template <int OPL, int CPL, int NA, bool F64 = true>
+// LEAN (k_step_lean, see step_kernel): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
+// time - one chunk, no store-flavour switch, no descriptor reload.
+template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false>
 __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
                                         const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
                                         bool objs_changed = true, bool cells_changed = true, uint8_t *__restrict__ codes = nullptr /* [A][Fp] */,
@@ -358,12 +360,12 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
             }
         }
     }
-    if (!F64 || !out) { __builtin_amdgcn_wave_barrier(); return; }      // (F64 = false: the codes-only instance carries no float64 path)
+    if (!F64 || (!LEAN && !out)) { __builtin_amdgcn_wave_barrier(); return; }      // (F64 = false: the codes-only instance carries no float64 path)
     decltype(__builtin_amdgcn_make_buffer_rsrc(out, 0, 0, 0)) rs[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) rs[a] = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)a * (uint32_t)P.F, 0, P.F * 8, 0x00020000);
-    const uint32_t wt = (uint32_t)P.wt;                                                 // wave-uniform
-    for (int chunk = 0; chunk * 128 * OBS_PAIRS < P.F; ++chunk) {
+    const uint32_t wt = LEAN ? 1u : (uint32_t)P.wt;                                     // wave-uniform
+    for (int chunk = 0; LEAN ? chunk == 0 : chunk * 128 * OBS_PAIRS < P.F; ++chunk) {
         if (chunk > 0) load_desc(P, e.layout, chunk, cx.lane, dsc);
         // branch-free stages so that the LDS reads of all pairs and observers are in flight together
         // (descriptor words past F are 0: they read image halfword 0 and their stores are out of range)
@@ -394,7 +396,7 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
 #undef CZ_OBS_WRITE_ROWS
     }
     // the caller keeps the descriptors of chunk 0 across steps (fused rollout): restore them if later chunks replaced them
-    if (P.F > 128 * OBS_PAIRS) load_desc(P, e.layout, 0, cx.lane, dsc);
+    if (!LEAN && P.F > 128 * OBS_PAIRS) load_desc(P, e.layout, 0, cx.lane, dsc);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -413,7 +415,7 @@ struct StepOut {
 // HINT (the fused instances): the reset pass and the end of an episode are laid out off the fall-through path - one step in max_steps + 1
 // takes them; in the one-step kernels the same hint cost the launches under a cooking policy 1.5 % (profiles/r05/ab_experiments.txt)
 #define CZ_RARE(hint, x) ((hint) ? __builtin_expect(!!(x), 0) : !!(x))
-template <int OPL, int CPL, int NA, int SCHEME, bool HINT = false>
+template <int OPL, int CPL, int NA, int SCHEME, bool HINT = false, bool LEAN = false>
 __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t acts,
                                          int64_t env_global, uint32_t &rowv, Lds<CPL> &lds, uint32_t (&dsc)[OBS_CHUNK], Dirty &dt, StepOut &o) {
     using O = Ops<OPL, CPL, NA, SCHEME>;
@@ -423,7 +425,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
     o.dbg = 0u;
 #endif
     // P.auto_reset: bit 0 = next-step auto-reset, bit 1 = agent despawn / respawn is on (cz_set_spawn)
-    const bool spawning = (P.auto_reset & 2) != 0;
+    const bool spawning = !LEAN && (P.auto_reset & 2) != 0;
     const SpawnCfg *const spawn_cfg = reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET);
     if (CZ_RARE(HINT, (e.status & ST_DONE) != 0u)) {
         o.header = true;
@@ -436,14 +438,14 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
             const kconst_u32 ctl = (kconst_u32)(lay0 - LAY_CTL_WORDS);
             uint32_t lay = next_layout(env_global, e.episode, e.pool, (uint32_t)P.L, ctl[LC_GROUPS], ctl[LC_ACTIVE]);
             uint32_t recipes = e.recipes, episode = e.episode, pool = e.pool;
-            load_env(P, e, cx, lay0 + (size_t)lay * P.RW);
+            load_env<OPL, CPL, NA, LEAN>(P, e, cx, lay0 + (size_t)lay * P.RW);
             e.t = 0; e.layout = lay; e.status = 0; e.episode = episode; e.recipes = recipes; e.pool = pool;
             if (spawning) {       // a fresh world: everybody present, grace periods running (load_level.py:67-68, parsing.py:142)
                 typedef const __attribute__((address_space(4))) SpawnCfg *kcfg;
                 e.status = spawn_initial_status(((kcfg)spawn_cfg)->grace_period, NA);
             }
-            all_marks(P, e, cx, rowv, lds);
-            if (P.obs) load_desc(P, lay, 0, cx.lane, dsc);
+            all_marks<OPL, CPL, NA, LEAN>(P, e, cx, rowv, lds);
+            if (LEAN || P.obs) load_desc(P, lay, 0, cx.lane, dsc);
             dt.cells = 1; dt.touched = 1; dt.interacted = 1;          // everything must be written back
         } else {
             o.term = (e.status & ST_TERM) ? 1u : 0u;
@@ -474,7 +476,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
     if (dt.moved & (uint32_t)P.walk_touches) { dt.touched = 1; dt.kinds = ~0ull; }
     if (dt.kinds & 0xFull) dt.kinds = ~0ull;                        // a Plate moved: it drags its content along -> anything
     bool done = false;
-    if (__builtin_expect(P.wide != 0, 0)) {
+    if (!LEAN && __builtin_expect(P.wide != 0, 0)) {
         // Wide recipe tables (a graph with more than 8 nodes in the book): no filters, every recipe of the env is
         // re-evaluated whenever an object moved or changed; marks are 16 bits per recipe (recipes 0, 1 in `marks`, 2, 3 in
         // `marks_hi`).  Without a change the marks, hence `done` (false, or the env would not be stepping), stay.
@@ -623,7 +625,11 @@ __host__ __device__ inline Early early_of(const Params &P) {
     return Early{P.state, P.actions, P.lut, P.N, P.RW, P.W, P.H, P.D, P.dyn0_off, P.dyn1_off};
 }
 
-template <int OPL, int CPL, int NA, int SCHEME, int FUSED_MODE>
+// LEAN (FUSED_MODE 0 only; k_step_lean): the one-step kernel with the handle's uniform settings fixed at compile time - narrow
+// recipe tables, no despawn / respawn, float64 observations of at most 128 * OBS_PAIRS features with write-through stores, no
+// compact output and no marks buffer (launch_step in cz_api.hip picks it when all of that holds).  The code is today's one-step
+// kernel with those tests folded away: same results, fewer scalar instructions and registers per wave.
+template <int OPL, int CPL, int NA, int SCHEME, int FUSED_MODE, bool LEAN = false>
 __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                             int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
                                             int32_t e_dyn1, const Params &P0) {
@@ -677,11 +683,11 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     if (!FUSED) av = ldg<int>(P.actions, ((uint32_t)env * (uint32_t)NA + (uint32_t)min(lane, NA - 1)) * 4u);
     double ret = ldg<double>(retp, ((uint32_t)lane & 3u) * 8u);                                       // running episode return, lane a = agent a
     Env<OPL, CPL, NA> e;
-    load_env(P, e, cx, rec);
+    load_env<OPL, CPL, NA, LEAN>(P, e, cx, rec);
     init_lds<CPL>(P, cx, lds);
     uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
     uint32_t dsc[OBS_CHUNK];
-    if (!CODES_ONLY && P.obs) load_desc(P, e.layout, 0, lane, dsc);
+    if (!CODES_ONLY && (LEAN || P.obs)) load_desc(P, e.layout, 0, lane, dsc);
     if (!SUBMASK_EARLY) submask = load_submask(P, lane);
     const int64_t env_global = P.env_id_base + env;
     bool cells_dirty = false, objs_dirty = false, header_dirty = FUSED;
@@ -740,7 +746,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         } else acts = action_hash(Pt.seed, env_global, lane & 3, Pt.step0 + (uint32_t)t, SCHEME == 3 ? 5u : 8u);
         Dirty dt{};
         StepOut o;
-        step_env<OPL, CPL, NA, SCHEME, FUSED>(Pt, (unsigned)offsetof(StepArgsMirror, p), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
+        step_env<OPL, CPL, NA, SCHEME, FUSED, LEAN>(Pt, (unsigned)offsetof(StepArgsMirror, p), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
 #ifdef CZ_TIMELINE
         tl_dbg |= o.dbg;
 #endif
@@ -798,25 +804,25 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
                 }
             }
         }
-        if (!FUSED) {
+        if (!FUSED && !LEAN) {
             uint32_t *const marks_out = kp->marks_out;
             if (marks_out && lane < 2) stg<uint32_t>(marks_out, (2u * (uint32_t)env + (uint32_t)lane) * 4u, lane == 0 ? e.marks : e.marks_hi);   // infos["recipe_done"] of the host API
         }
         CZ_STAMP(5);
         img_objs |= (dt.touched | dt.moved) != 0;
         img_cells |= dt.cells != 0;
-        if (Pt.obs || CODES) {
+        if (LEAN || Pt.obs || CODES) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
             uint8_t *const codes = CODES ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
             double *const obs_row = !CODES_ONLY && Pt.obs ? Pt.obs + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F) : nullptr;
-            observe<OPL, CPL, NA, !CODES_ONLY>(Pt, e, cx, lds, lut, dsc, submask, obs_row, img_objs, img_cells, codes, CODES ? &cpre : nullptr);
+            observe<OPL, CPL, NA, !CODES_ONLY, LEAN>(Pt, e, cx, lds, lut, dsc, submask, obs_row, img_objs, img_cells, codes, CODES ? &cpre : nullptr);
             img_objs = false; img_cells = false;
         }
         if (CZ_RARE(FUSED, o.finished)) {      // (the state is still that of the finished episode: the reset is the next pass)
             uint32_t *su = kp->stat_u + (size_t)env * SU_WORDS;
             double *sf = kp->stat_f + (size_t)env * SF_WORDS;
             const uint32_t a_of = (uint32_t)lane - SU_COMPLETED0;               // lane SU_COMPLETED0 + a: recipe a completed?
-            const uint32_t root = Pt.wide ? (((a_of < 2u ? e.marks : e.marks_hi) >> (16u * (a_of & 1u))) & 1u) : ((e.marks >> (8u * (a_of & 3u))) & 1u);
+            const uint32_t root = !LEAN && Pt.wide ? (((a_of < 2u ? e.marks : e.marks_hi) >> (16u * (a_of & 1u))) & 1u) : ((e.marks >> (8u * (a_of & 3u))) & 1u);
             const uint32_t inc = lane == (int)SU_EPISODES ? 1u : lane == (int)SU_LENSUM ? e.t : lane == (int)SU_TRUNC ? (uint32_t)o.trunc
                                  : lane == (int)SU_TERM ? (uint32_t)o.term : a_of < (uint32_t)NA ? root : 0u;
             if (lane < (int)SU_COMPLETED0 + NA && lane != (int)SU_STEPS) stg<uint32_t>(su, (uint32_t)lane * 4u, su_old + inc);
@@ -858,6 +864,13 @@ __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) CZ_STEP_ATTR void k_step(u
                                                           int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
                                                           int32_t e_dyn1, const Params P0) {
     step_kernel<OPL, CPL, NA, SCHEME, FUSED>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
+}
+// the lean one-step kernel (see step_kernel; small instance only: launchers_small)
+template <int OPL, int CPL, int NA, int SCHEME>
+__global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
+                                                                       int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
+                                                                       int32_t e_dyn1, const Params P0) {
+    step_kernel<OPL, CPL, NA, SCHEME, 0, true>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
 }
 // reset(): cooking_env.py:178-210 for envs [env_begin, env_begin + count)
 template <int OPL, int CPL, int NA>
@@ -917,6 +930,9 @@ struct Launchers {
     hipError_t (*step)(const Params &, hipStream_t, int mode);
     hipError_t (*reset)(const Params &, hipStream_t, int64_t, int, const int32_t *, const uint32_t *, const uint32_t *, double *);
     hipError_t (*observe)(const Params &, hipStream_t, int64_t, int, double *, uint8_t *);
+    // one step with k_step_lean (null: the instance has none).  Only for launches that satisfy every condition of the lean
+    // kernel (launch_step, cz_api.hip); same results as `step` with LAUNCH_ONE
+    hipError_t (*step_lean)(const Params &, hipStream_t);
 };
 
 template <int OPL, int CPL>
@@ -952,6 +968,24 @@ struct Inst {
         }
 #undef CZ_LAUNCH_STEP
         return hipGetLastError();
+    }
+    template <int NA>
+    static hipError_t step_lean_na(const Params &P, hipStream_t st) {
+        constexpr int EPW = envs_per_wg<CPL>();
+        const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
+        const Early E = early_of(P);
+        if (!P.actions) return hipErrorInvalidValue;
+        if (P.scheme == 3) hipLaunchKernelGGL((k_step_lean<OPL, CPL, NA, 3>), grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
+        else hipLaunchKernelGGL((k_step_lean<OPL, CPL, NA, 1>), grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
+        return hipGetLastError();
+    }
+    static hipError_t step_lean(const Params &P, hipStream_t st) {
+        switch (P.A) {
+        case 1: return step_lean_na<1>(P, st);
+        case 2: return step_lean_na<2>(P, st);
+        case 3: return step_lean_na<3>(P, st);
+        default: return step_lean_na<4>(P, st);
+        }
     }
     static hipError_t step(const Params &P, hipStream_t st, int mode) {
         switch (P.A) {

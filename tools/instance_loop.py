@@ -4,7 +4,7 @@ so that a rocprofv3 --pmc pass sees exactly one kernel instance with a known num
 
     python3 tools/instance_loop.py FORM [ENVS]
     FORM: step | step_compact | rollout | rollout_actions | rollout_compact | ring_in_place | cooking
-Prints `FORM instance=<key of issue_per_env_step.json> steps_per_launch=<T>` for tools/pmc_instances.py."""
+Prints `FORM instance=<key of issue_per_env_step.json> steps_per_launch=<T> kernel=<the kernel launched>` for tools/pmc_instances.py."""
 import os
 import sys
 
@@ -65,5 +65,11 @@ elif form == "ring_in_place":
 else:
     raise SystemExit(f"unknown form {form}")
 env.sync()
-print(f"{form} instance={inst} steps_per_launch={steps}")
+# the kernel the launches were (one-step forms: k_step_lean<...> when launch_step picked the lean kernel, libraries that have it)
+kernel = inst.split("/")[0]
+if form in ("step", "cooking"):
+    from cooking_zoo_amd import _native
+    if getattr(_native.lib(), "cz_diag_last_step_lean", None) is not None and _native.lib().cz_diag_last_step_lean(env._h) == 1:
+        kernel = f"k_step_lean<1,1,{A},3>"
+print(f"{form} instance={inst} steps_per_launch={steps} kernel={kernel}")
 env.close()

@@ -23,7 +23,8 @@ def main():
             continue
         inst, steps = m.group(1), int(m.group(2))
         d = line_file[:-4]
-        want = inst.split("/")[0].replace(",", ", ")                 # "k_step<1,1,2,3,0>/cooking" -> the kernel name's "k_step<1, 1, 2, 3, 0>"
+        k = re.search(r"kernel=(\S+)", open(line_file).read())              # (the lean one-step kernel stands in for k_step<...,0>)
+        want = (k.group(1) if k else inst.split("/")[0]).replace(",", ", ")   # "k_step<1,1,2,3,0>/cooking" -> the kernel name's "k_step<1, 1, 2, 3, 0>"
         agg = collections.defaultdict(list)
         for f in glob.glob(d + "*/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(f)):
@@ -35,7 +36,7 @@ def main():
         out[inst] = {"salu": round(per["SQ_INSTS_SALU"], 1), "valu": round(per["SQ_INSTS_VALU"], 1), "lds": round(per.get("SQ_INSTS_LDS", 0.0), 1),
                      "smem": round(per.get("SQ_INSTS_SMEM", 0.0), 1), "branch": round(per.get("SQ_INSTS_BRANCH", 0.0), 1),
                      "vmem_rd": round(per.get("SQ_INSTS_VMEM_RD", 0.0), 1), "vmem_wr": round(per.get("SQ_INSTS_VMEM_WR", 0.0), 1),
-                     "steps_per_launch": steps, "dispatches": len(agg["SQ_INSTS_SALU"])}
+                     "steps_per_launch": steps, "dispatches": len(agg["SQ_INSTS_SALU"]), "kernel": want}
     json.dump(out, sys.stdout, indent=1, sort_keys=True)
     print()
 
