@@ -230,6 +230,7 @@ struct cz_handle_s {
     bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
     int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
     bool huge = false;             // the 256-slot / 1024-cell instance (its own LDS image layout)
+    int instance = 0;              // which kernel instance cz_create picked: 0 small, 1 large, 2 huge (cz_diag_instance)
     unsigned long long *tl_base = nullptr;   // timeline build: stamp buffer, its capacity in launches, launches so far
     int32_t tl_cap = 0;
     int64_t tl_count = 0;
@@ -382,7 +383,8 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     if (!(P.D <= 64 && C <= 64)) { fail(nullptr, "cz_create: this diagnostic library holds the small kernel instance only"); cz_destroy(h); return 1; }
     h->kl = launchers_small();
 #else
-    h->kl = (P.D <= 64 && C <= 64) ? launchers_small() : (P.D <= 128 && C <= 256) ? launchers_large() : launchers_huge();
+    h->instance = (P.D <= 64 && C <= 64) ? 0 : (P.D <= 128 && C <= 256) ? 1 : 2;
+    h->kl = h->instance == 0 ? launchers_small() : h->instance == 1 ? launchers_large() : launchers_huge();
 #endif
     h->huge = P.D > 128 || C > 256;
     {   // the reward of a step on which no recipe node changed: cooking_env.py:304-307 with zero deltas, same op order
@@ -1067,6 +1069,9 @@ extern "C" int32_t cz_codes_pitch(cz_handle h) { return h ? codes_pitch(h->P.F) 
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_lean_step.py): 1 if the most recent step launch issued or captured by the
 // handle was the lean one-step kernel, 0 if another kernel, -1 before the first
 extern "C" int32_t cz_diag_last_step_lean(cz_handle h) { return h ? h->last_step_lean : -1; }
+// diagnostic, not part of cookingzoo.h (tests/test_gpu_instance_edges.py): the kernel instance the handle's launches use,
+// 0 small (Inst<1,1>), 1 large (Inst<2,4>), 2 huge (Inst<4,16>); -1 for a null handle
+extern "C" int32_t cz_diag_instance(cz_handle h) { return h ? h->instance : -1; }
 extern "C" int cz_obs_table(cz_handle h, double *table) {
     if (!h || !table) return fail(h, "cz_obs_table: null argument");
     memcpy(table, h->obs_table, sizeof h->obs_table);

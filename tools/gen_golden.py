@@ -1048,6 +1048,32 @@ def main():
         sets["odd_feature_length_1agent"] = lambda: run_set(
             "odd_feature_length_1agent", base_cfg("coop_test", 1, ["TomatoSalad"], scheme="scheme1", max_steps=80, meta=meta_odd),
             [(702, "bumper", 80)], args.out)
+    # capacity edges of the kernel instances and of the lean one-step kernel (cz_create / launch_step in csrc/cz_api.hip):
+    # F = 384 (the last feature count the lean kernel takes) and 385 (the first it must leave); one coop_test trajectory with its
+    # records padded to D = 64 | 65 (small | large instance) and 128 | 129 | 255 (large | huge); the 8x8 level whose 64 slots are
+    # all in use (small instance, two observation chunks) and the same level on the large instance
+    two = ["TomatoLettuceSalad", "CarrotBanana"]
+    for fcap in ("f384", "f385"):
+        sets["cap_" + fcap] = (lambda n="cap_" + fcap, m=mta("example_" + fcap): run_set(
+            n, base_cfg("coop_test", 2, two, max_steps=100, meta=m), [(1000, "bumper", 100), (1001, "bumper", 100)], args.out))
+    sets["cap_f384_scheme1"] = lambda: run_set(
+        "cap_f384_scheme1", base_cfg("coop_test", 1, ["TomatoSalad"], scheme="scheme1", max_steps=80, meta=mta("example_f384")),
+        [(1010, "bumper", 80)], args.out)
+    for dcap in (64, 65, 128, 129, 255):
+        sets[f"cap_d{dcap}"] = (lambda n=f"cap_d{dcap}", d=dcap: run_set(
+            n, base_cfg("coop_test", 2, two, max_steps=60, max_dyn=d), [(1020, "bumper", 60), (1021, "bumper", 60)], args.out))
+    if os.path.exists(lvl("dense_8x8")):
+        sets["dense8_4agents"] = lambda: run_set(
+            "dense8_4agents", base_cfg(lvl("dense_8x8"), 4, ["TomatoSalad", "no_recipe", "TomatoLettuceSalad", "CarrotBanana"],
+                                       max_steps=120, meta=mta("dense_8x8")),
+            [(1200, "bumper", 120), (1201, "bumper", 120)], args.out)
+        sets["dense8_scheme1"] = lambda: run_set(
+            "dense8_scheme1", base_cfg(lvl("dense_8x8"), 3, ["TomatoSalad", "no_recipe", "TomatoLettuceSalad"], scheme="scheme1",
+                                       max_steps=100, meta=mta("dense_8x8")),
+            [(1210, "bumper", 100), (1211, "bumper", 100)], args.out)
+        sets["dense8_d65"] = lambda: run_set(
+            "dense8_d65", base_cfg(lvl("dense_8x8"), 2, ["TomatoSalad", "no_recipe"], max_steps=100, meta=mta("dense_8x8"), max_dyn=65),
+            [(1220, "bumper", 100)], args.out)
     sets["api_traces"] = lambda: api_traces(args.out)
     sets["layouts_ref"] = lambda: layout_draws(args.out)
     sets["aec_traces"] = lambda: aec_traces(args.out)
@@ -1377,7 +1403,8 @@ def layout_draws(out_dir):
     M = os.path.join(REPO, "cooking_zoo_amd", "utils", "meta_files")
     cases = [("coop_test", "example", 2), ("coop_test", "example", 1), ("coexistence_test", "example", 2),
              ("switch_test", "example", 2), (os.path.join(L, "large_16x16.json"), os.path.join(M, "large_16x16.json"), 4),
-             (os.path.join(L, "crowded_6x5.json"), os.path.join(M, "crowded_6x5.json"), 3)]
+             (os.path.join(L, "crowded_6x5.json"), os.path.join(M, "crowded_6x5.json"), 3),
+             (os.path.join(L, "dense_8x8.json"), os.path.join(M, "dense_8x8.json"), 4)]
     out = []
     for level, meta, A in cases:
         for seed in (0, 1, 2, 3, 12345):

@@ -236,6 +236,55 @@ def huge_levels():
     return out
 
 
+def dense_8x8():
+    """the small kernel instance filled to its cap: 64 cells and exactly 64 object slots (16 Plate, 16 Tomato, 16 Bread with
+    16 clone slots) on the 48 Counters, all of them holding an object from reset on; F = 466, above the 384 features of one
+    observation chunk.  Two floor corridors joined by a two-cell passage; the fourth agent spawns in the passage, so a
+    respawn can find every cell of its area taken."""
+    W = H = 8
+    rows = ["--------",
+            "-      -",
+            "- ------",
+            "- ------",
+            "-      -",
+            "--------",
+            "--------",
+            "--------"]
+    one = lambda name, x, y: {name: {"COUNT": 1, "X_POSITION": [x], "Y_POSITION": [y]}}
+    statics = [one("Cutboard", 3, 2), one("Deliversquare", 4, 5)]
+    n_counters = sum(r.count("-") for r in rows) - len(statics)
+    allx, ally = list(range(W)), list(range(H))
+    counts = [("Plate", 16), ("Tomato", 16), ("Bread", 16)]
+    assert sum(c for _, c in counts) == n_counters == 48
+    dyn = [{name: {"COUNT": c, "X_POSITION": allx, "Y_POSITION": ally}} for name, c in counts]
+    agents = [{"MAX_COUNT": 1, "X_POSITION": [1, 2, 3], "Y_POSITION": [1]},
+              {"MAX_COUNT": 1, "X_POSITION": [4, 5, 6], "Y_POSITION": [1]},
+              {"MAX_COUNT": 1, "X_POSITION": [2, 3, 4, 5, 6], "Y_POSITION": [4]},
+              {"MAX_COUNT": 1, "X_POSITION": [1], "Y_POSITION": [2, 3]}]
+    lv = {"LEVEL_LAYOUT": "\n".join(rows), "STATIC_OBJECTS": statics, "DYNAMIC_OBJECTS": dyn, "AGENTS": agents,
+          "DYNAMIC_EXCLUDED_POSITIONS": []}
+    meta = [{"Cutboard": 1}, {"Counter": n_counters}, {"Deliversquare": 1}, {"Plate": 16}, {"Tomato": 16}, {"Bread": 32},
+            {"Agent": 4}]
+    return lv, meta
+
+
+def example_capacity_metas():
+    """example.json with extra Tomato / Plate slots: F = 384, the last feature count of the lean one-step kernel, and F = 385,
+    the first one past it"""
+    with open(os.path.join(META_DIR, "example.json")) as f:
+        base = json.load(f)
+    out = {}
+    for name, tomato, plate in (("example_f384", 20, 2), ("example_f385", 19, 4)):
+        meta = [dict(e) for e in base]
+        for e in meta:
+            if "Tomato" in e:
+                e["Tomato"] += tomato
+            if "Plate" in e:
+                e["Plate"] += plate
+        out[name] = meta
+    return out
+
+
 def main():
     os.makedirs(LEVEL_DIR, exist_ok=True)
     os.makedirs(META_DIR, exist_ok=True)
@@ -265,6 +314,11 @@ def main():
                 dump_level(os.path.join(LEVEL_DIR, name + ".json"), json.load(f))
         with open(os.path.join(REF, "meta_files", "example.json")) as f:
             dump_meta(os.path.join(META_DIR, "example.json"), json.load(f))
+    lv, meta = dense_8x8()
+    dump_level(os.path.join(LEVEL_DIR, "dense_8x8.json"), lv)
+    dump_meta(os.path.join(META_DIR, "dense_8x8.json"), meta)
+    for name, meta in example_capacity_metas().items():
+        dump_meta(os.path.join(META_DIR, name + ".json"), meta)
 
 
 if __name__ == "__main__":
