@@ -14,6 +14,7 @@
 
 #include "../../include/cookingzoo.h"
 #include "cz_kernels.h"
+#include "cz_generate.h"
 
 using namespace cz;
 
@@ -181,6 +182,10 @@ struct cz_handle_s {
     hipEvent_t ev_main_copy_done = nullptr;
     int32_t lay_groups = 1, lay_active = 0;
     int64_t n_layout_updates = 0;
+    void *d_gen_tables = nullptr;          // cz_load_level_programs: failure counter | program offsets | programs | level of every slot
+    GenParams gen = {};                     // ... and where its parts are
+    int gen_layouts = 0;                   // the pool size those tables were made for
+    std::vector<SlotRange> gen_slices;     // per pool slot: the run of slots of its level (the pool slice an env of that level draws from)
     void *d_spawn_tables = nullptr;        // cz_set_spawn: exhausted-respawn counter | spawn areas per (level, agent) | level of every layout
     int spawn_layouts = 0;                 // the pool size those tables were made for
     uint32_t spawn_bits = 5;               // width of the countdown fields the resident records are packed with (spawn_grace_bits)
@@ -473,7 +478,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_reset_words, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -839,7 +844,16 @@ extern "C" int cz_set_layout_group(cz_handle h, int32_t groups, int32_t active) 
     if (groups < 1 || groups > h->n_layouts || active < 0 || active >= groups || h->n_layouts % groups)
         return fail(h, "cz_set_layout_group: need 1 <= groups, 0 <= active < groups, and pool slices that are multiples of groups");
     if (set_device(h)) return 1;
-    if (caller_capturing(h)) return fail(h, "cz_set_layout_group: not inside a stream capture of the caller (it orders copies and waits)");
+    if (caller_capturing(h)) {
+        // only the switch between the parts of a cut that is already in place, with no cz_update_layouts copy to order: one launch
+        if (groups != h->lay_groups || !h->upd_ranges.empty() || h->copy_pending)
+            return fail(h, "cz_set_layout_group: not inside a stream capture of the caller (it orders copies and waits) - unless it only "
+                           "switches the active part of the cut in place and no cz_update_layouts is outstanding");
+        hipLaunchKernelGGL(k_set_layout_active, dim3(1), dim3(64), 0, h->stream, h->d_lay_block, (uint32_t)active);
+        HIPCHK(h, hipGetLastError());
+        h->lay_active = active;
+        return 0;
+    }
     if (flush_updates(h, true)) return 1;
     if (h->copy_pending) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy_done, 0)); h->copy_pending = false; }
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->d_lay_block + LC_GROUPS), groups, 1, h->stream));
@@ -849,6 +863,147 @@ extern "C" int cz_set_layout_group(cz_handle h, int32_t groups, int32_t active) 
 }
 // how many pool slots cz_update_layouts has replaced on this handle so far
 extern "C" int64_t cz_layout_updates(cz_handle h) { return h ? h->n_layout_updates : 0; }
+
+// ---- fresh layouts drawn ON THE DEVICE (cz_generate.h): the level programs, one per level of the batch, and the level of every
+// pool slot.  Checks everything the kernel relies on when it indexes a program: offsets, class codes, candidate counts.
+static int validate_program(cz_handle h, int level, const uint32_t *p, int64_t avail) {
+    const auto bad = [&](const char *what) { return fail(h, "cz_load_level_programs: level %d: %s", level, what); };
+    if (avail < (int64_t)GEN_HEADER_WORDS || p[GH_MAGIC] != GEN_MAGIC) return bad("not a level program");
+    const int64_t words = p[GH_WORDS];
+    const int64_t CW = ((int64_t)h->P.W * h->P.H + 3) / 4;
+    if (words > avail || words < (int64_t)GEN_HEADER_WORDS + CW) return bad("truncated");
+    if ((int)p[GH_W] != h->P.W || (int)p[GH_H] != h->P.H || (int)p[GH_A] != h->P.A || (int)p[GH_F] != h->P.F || (int)p[GH_D] != h->P.D)
+        return bad("compiled for another batch geometry (grid, agents, slots or feature length)");
+    for (int64_t i = 0; i < CW * 4; ++i)
+        if (reinterpret_cast<const uint8_t *>(p + GEN_HEADER_WORDS)[i] > COUNTER) return bad("base grid cells must be Floor or Counter");
+    int64_t pos = p[GH_OFF_ENTRIES];
+    if (pos != (int64_t)GEN_HEADER_WORDS + CW) return bad("entries do not follow the grid");
+    const uint32_t n_sd = p[GH_NSTATIC] + p[GH_NDYN], n_all = n_sd + p[GH_NAGENT];
+    if (p[GH_NSTATIC] > 65535u || p[GH_NDYN] > 65535u || p[GH_NAGENT] > 65535u) return bad("too many entries");
+    for (uint32_t e = 0; e < n_all; ++e) {
+        if (pos + (int64_t)GEN_ENTRY_WORDS > words) return bad("entry table overruns the program");
+        const uint32_t *q = p + pos;
+        const uint32_t cls = q[GE_CLASS], nx = q[GE_NX], ny = q[GE_NY];
+        const bool cls_ok = e < p[GH_NSTATIC] ? (cls > COUNTER && cls <= BLENDER)
+                            : e < n_sd        ? (cls >= GEN_CODE_DYN0 && cls <= GEN_CODE_DYN0 + BREAD) : cls == GEN_CODE_AGENT;
+        if (!cls_ok) return bad("unknown object class");
+        if (nx < 1 || nx > GEN_MAX_CANDIDATES || ny < 1 || ny > GEN_MAX_CANDIDATES || q[GE_COUNT] > 65535u) return bad("1..1024 x and y candidates per entry");
+        if (pos + (int64_t)GEN_ENTRY_WORDS + nx + ny > words) return bad("candidate lists overrun the program");
+        // parsing.py:34, :92, :131 raise on a drawn position < 0 or > width / height (`>`: the far edge itself only never fits)
+        for (uint32_t i = 0; i < nx; ++i) if (q[GEN_ENTRY_WORDS + i] > (uint32_t)h->P.W) return bad("x candidate out of bounds set by the level layout");
+        for (uint32_t i = 0; i < ny; ++i) if (q[GEN_ENTRY_WORDS + nx + i] > (uint32_t)h->P.H) return bad("y candidate out of bounds set by the level layout");
+        pos += (int64_t)GEN_ENTRY_WORDS + nx + ny;
+    }
+    if (pos != (int64_t)p[GH_OFF_EXCL] || pos + (int64_t)p[GH_NEXCL] != (int64_t)p[GH_OFF_META] || (int64_t)p[GH_OFF_META] + 2 * (int64_t)p[GH_NMETA] != words)
+        return bad("sections do not add up to the program length");
+    // the meta table fixes the descriptor: its feature lengths (cooking_env.py:114-117) must add up to F
+    static const int flen_static[7] = {0, 3, 3, 4, 4, 3, 3}, flen_dyn[10] = {3, 5, 5, 5, 6, 5, 6, 5, 5, 5};
+    int64_t F = 0;
+    for (uint32_t i = 0; i < p[GH_NMETA]; ++i) {
+        const uint32_t code = p[p[GH_OFF_META] + 2 * i], num = p[p[GH_OFF_META] + 2 * i + 1];
+        if (num > 65535u) return bad("meta count");
+        if (code <= BLENDER) F += (int64_t)flen_static[code] * num;
+        else if (code >= GEN_CODE_DYN0 && code <= GEN_CODE_DYN0 + BREAD) F += (int64_t)flen_dyn[code - GEN_CODE_DYN0] * num;
+        else if (code == GEN_CODE_AGENT) F += 7 * (int64_t)num;
+        else return bad("unknown class in the meta table");
+    }
+    if (F != h->P.F) return bad("the meta table's feature lengths do not add up to feat_len");
+    return 0;
+}
+
+extern "C" int cz_load_level_programs(cz_handle h, const uint32_t *programs, int64_t words, int32_t n_levels, const uint8_t *level_of_slot) {
+    if (!h) return fail(nullptr, "null handle");
+    if (!h->P.lay_init) return fail(h, "cz_load_level_programs: load the layout pool first (every pool slot is given its level)");
+    if (!programs || words < 1 || n_levels < 1 || n_levels > 255) return fail(h, "cz_load_level_programs: need 1..255 level programs");
+    std::vector<uint32_t> offs;
+    int64_t pos = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        if (validate_program(h, l, programs + pos, words - pos)) return 1;
+        offs.push_back((uint32_t)pos);
+        pos += programs[pos + GH_WORDS];
+    }
+    if (pos != words) return fail(h, "cz_load_level_programs: %lld words given, the %d programs hold %lld", (long long)words, n_levels, (long long)pos);
+    std::vector<uint8_t> levels((size_t)h->n_layouts, 0);
+    for (int i = 0; i < h->n_layouts; ++i) {
+        const int lv = level_of_slot ? level_of_slot[i] : 0;
+        if (lv >= n_levels) return fail(h, "cz_load_level_programs: slot %d is of level %d, but only %d program(s) were given", i, lv, n_levels);
+        levels[(size_t)i] = (uint8_t)lv;
+    }
+    // the pool slice of a slot = the run of consecutive slots of its level (cooking_zoo_amd keeps one contiguous slice per level)
+    h->gen_slices.assign((size_t)h->n_layouts, {0, 0});
+    for (int i = 0; i < h->n_layouts;) {
+        int j = i;
+        while (j < h->n_layouts && levels[(size_t)j] == levels[(size_t)i]) ++j;
+        for (int k = i; k < j; ++k) h->gen_slices[(size_t)k] = {i, j - i};
+        i = j;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_gen_tables) { HIPCHK(h, hipFree(h->d_gen_tables)); h->d_gen_tables = nullptr; }
+    h->gen_layouts = 0;
+    const size_t off_offs = 16, off_prog = off_offs + (((size_t)n_levels * 4 + 15) & ~(size_t)15), off_levels = off_prog + (((size_t)words * 4 + 15) & ~(size_t)15);
+    HIPCHK(h, hipMalloc(&h->d_gen_tables, off_levels + levels.size() + 16));
+    HIPCHK(h, hipMemset(h->d_gen_tables, 0, off_levels + levels.size() + 16));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_prog, programs, (size_t)words * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_levels, levels.data(), levels.size(), hipMemcpyHostToDevice));
+    GenParams &G = h->gen;
+    G.failures = (uint32_t *)h->d_gen_tables;
+    G.prog_off = (const uint32_t *)((char *)h->d_gen_tables + off_offs);
+    G.programs = (const uint32_t *)((char *)h->d_gen_tables + off_prog);
+    G.level_of_slot = (const uint8_t *)h->d_gen_tables + off_levels;
+    G.RW = h->P.RW; G.F = h->P.F; G.W = h->P.W; G.H = h->P.H; G.D = h->P.D; G.A = h->P.A; G.dyn0_off = h->P.dyn0_off;
+    // the image offsets of the handle's kernel instance (soa.Dims.img_layout): the huge one keeps a larger image
+    G.img_obj0 = h->huge ? Img<16>::OBJ0 : Img<1>::OBJ0; G.img_cell0 = h->huge ? Img<16>::CELL0 : Img<1>::CELL0;
+    G.img_ag0 = h->huge ? Img<16>::AG0 : Img<1>::AG0; G.img_zero = h->huge ? Img<16>::ZERO : Img<1>::ZERO;
+    h->gen_layouts = h->n_layouts;
+    return 0;
+}
+
+// Pool slots [first, first + count) drawn anew by ONE launch on the handle's stream (parsing.py:5-151 per slot, then
+// layout.py's init_record / obs_descriptor): stream-ordered with the steps before and after it and with cz_set_layout_group,
+// nothing allocated, copied or waited for - legal inside a stream capture of the caller.
+extern "C" int cz_generate_layouts(cz_handle h, int32_t first, int32_t count, uint64_t seed, uint32_t generation) {
+    if (ready(h)) return 1;
+    if (!h->d_gen_tables || h->gen_layouts != h->n_layouts)
+        return fail(h, "cz_generate_layouts: level programs not loaded for this pool (cz_load_level_programs, again after cz_load_layouts)");
+    if (first < 0 || count < 0 || (int64_t)first + count > h->n_layouts)
+        return fail(h, "cz_generate_layouts: slots [%d, %d) outside the resident pool of %d layouts", first, first + count, h->n_layouts);
+    if (count == 0) return 0;
+    if (h->lay_groups > 1)          // the envs draw from part `active` of every slice: that part must stay as it is
+        for (int s = first; s < first + count; ++s) {
+            const auto &sl = h->gen_slices[(size_t)s];
+            const int part = sl.count / h->lay_groups;
+            if (part > 0 && (s - sl.first) / part == h->lay_active)
+                return fail(h, "cz_generate_layouts: slot %d is in part %d of its pool slice, which the envs draw from (cz_set_layout_group)", s, h->lay_active);
+        }
+    if (set_device(h)) return 1;
+    if (caller_capturing(h)) {
+        if (!h->upd_ranges.empty() || h->copy_pending)
+            return fail(h, "cz_generate_layouts: a cz_update_layouts copy is outstanding, which a stream capture cannot be ordered behind");
+    } else {
+        // in order behind every cz_update_layouts issued so far
+        if (flush_updates(h, true)) return 1;
+        if (h->copy_pending) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_copy_done, 0)); h->copy_pending = false; }
+    }
+    if (h->P.RW > (CELL_WORD0 + 256 + 2 * 255 + 15) / 16 * 16) return fail(h, "cz_generate_layouts: record longer than the generator's staging");
+    GenParams G = h->gen;
+    G.lay_init = h->d_lay_init; G.lay_desc = h->d_lay_desc;
+    G.seed = seed; G.generation = generation; G.first = first;
+    hipLaunchKernelGGL(k_generate_layouts, dim3((unsigned)count), dim3(64), 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    h->n_layout_updates += count;
+    return 0;
+}
+// draws that failed since cz_load_level_programs (the reference raises ValueError there; the slot kept its content); -1 on error
+extern "C" int64_t cz_generate_failures(cz_handle h) {
+    if (!h) return -1;
+    if (!h->d_gen_tables) return 0;
+    uint32_t n = 0;
+    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&n, h->d_gen_tables, 4, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_generate_failures: copy failed"); return -1; }
+    return (int64_t)n;
+}
 
 static int check_range(cz_handle h, int64_t b, int64_t c) {
     if (!h) return fail(nullptr, "null handle");

@@ -366,6 +366,14 @@ class ShardedVecEnv:
     def update_layouts(self, first, layouts):
         self._each(lambda i, env: env.update_layouts(first, layouts))
 
+    def generate_layouts(self, first, count, generation, seed=None, mirror=True):
+        """`CookingVecEnv.generate_layouts` on every shard: the draws are keyed by the slot's index in the whole pool, which every
+        shard holds, so all shards generate the same bytes."""
+        self._each(lambda i, env: env.generate_layouts(first, count, generation, seed=seed, mirror=mirror))
+
+    def generate_failures(self):
+        return self.shards[0].generate_failures()
+
     def set_layout_group(self, groups, active):
         self._each(lambda i, env: env.set_layout_group(groups, active))
 

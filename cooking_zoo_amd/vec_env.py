@@ -172,6 +172,7 @@ class BatchTables:
         self.recipe_ids[:, :self.num_recipes] = rid
 
         # ---- layout pool (per level a contiguous slice)
+        self.layout_seed = int(layout_seed)
         rng = _random.Random(layout_seed)
         self.layouts = []
         self.pool_slices = []
@@ -271,6 +272,9 @@ class CookingVecEnv:
         self._lay_groups, self._lay_active = 1, 0
         self._rot = None                      # rotate_layouts state
         self.rotation_events = []             # (step index, "group", groups, active) / (step index, "layouts", first slot, [Layout])
+                                              # / (step index, "generated", first slot, count, seed, generation)
+        self._programs_for = None             # pool size the level programs on the device were uploaded for (generate_layouts)
+        self._generated = {}                  # slot -> [Layout before, (seed, generation), ...]: device draws `self.layouts` has not caught up with
         if self.spawn_cells is not None:
             self._set_spawn()
             self.spawn = SpawnView(self)
@@ -322,6 +326,7 @@ class CookingVecEnv:
                              "would lose its layout -> level map (use update_layouts, which keeps every slot's level)")
         self.layouts = list(layouts)
         self.pool_slices = [(0, len(self.layouts))]
+        self._programs_for, self._generated = None, {}               # (cz_load_layouts drops the level programs' slot map)
         self._upload_layouts()
         if self.spawn is not None:                                       # (the spawn tables map every layout of the pool to its level)
             self.level_of_layout = np.zeros(len(self.layouts), dtype=np.uint8)
@@ -342,6 +347,69 @@ class CookingVecEnv:
         self._lay_desc[first:first + len(layouts)] = desc
         self.rotation_events.append((self._steps, "layouts", int(first), list(layouts)))
 
+    # ------------------------------------------------------------------ fresh layouts drawn on the device
+    def level_of_slot(self):
+        """uint8 [pool size]: the level (index into `levels`) every pool slot instantiates"""
+        out = np.zeros(len(self.layouts), dtype=np.uint8)
+        for li, (base, count) in enumerate(self.pool_slices):
+            out[base:base + count] = li
+        return out
+
+    def load_level_programs(self):
+        """Compile every level of the batch into a level program (engine/level_program.py) and upload them with the slot ->
+        level map (cz_load_level_programs).  `generate_layouts` does this on first use and after the pool changed size."""
+        from cooking_zoo_amd.cooking_world.engine import level_program as _lp
+        progs = [_lp.compile_level(lv, self.meta, self.num_agents, self.dims) for lv in self.level_objects]
+        words = np.ascontiguousarray(np.concatenate(progs), dtype=np.uint32)
+        los = self.level_of_slot()
+        _native.check(self._h, _native.lib().cz_load_level_programs(self._h, _ptr(words), int(words.size), len(progs), _ptr(los)))
+        self._programs_for = len(self.layouts)
+
+    def keyed_layouts(self, first, count, seed, generation, previous=None):
+        """The host model of `generate_layouts`: ([Layout] of slots [first, first + count) for (seed, generation), failed draws).
+        A failed draw (the reference raises) keeps `previous[k]`, None without `previous`."""
+        from cooking_zoo_amd.cooking_world.engine import level_program as _lp
+        return _lp.keyed_layouts(self.level_objects, self.meta, self.num_agents, self.dims, self.level_of_slot(), seed, generation,
+                                 first, count, previous)
+
+    def generate_layouts(self, first, count, generation, seed=None, mirror=True):
+        """Draw pool slots [first, first + count) anew ON THE DEVICE: one launch on the env's stream (cz_generate_layouts), no
+        host arrays, legal inside a stream capture of the caller.  Every draw comes from the stream keyed by (seed, pool slot,
+        generation) - `seed` defaults to the env's `layout_seed` -, so the result depends on nothing else: not on the batch size,
+        the shard or the timing.  Only slots that no env can draw or is playing on (refused for the part in use once
+        `set_layout_group` has cut the pool).  `mirror=True` also evaluates the host model (`keyed_layouts`) so that
+        `self.layouts` stays what the pool holds; `mirror=False` leaves that to `resolve_layouts()` (until then the slots read None)."""
+        first, count, generation = int(first), int(count), int(generation)
+        seed = int(self.layout_seed if seed is None else seed)
+        if self._programs_for != len(self.layouts):
+            self.load_level_programs()
+        _native.check(self._h, _native.lib().cz_generate_layouts(self._h, first, count, seed, generation))
+        self.rotation_events.append((self._steps, "generated", first, count, seed, generation))
+        for s in range(first, first + count):
+            hist = self._generated.setdefault(s, [self.layouts[s]])       # what the slot held, then the draws since
+            hist.append((seed, generation))
+            self.layouts[s] = None
+        if mirror:
+            self.resolve_layouts()
+
+    def resolve_layouts(self):
+        """Bring `self.layouts` up to date with the device draws issued with `mirror=False` (host model, milliseconds)."""
+        los = self.level_of_slot()
+        from cooking_zoo_amd.cooking_world.engine import level_program as _lp
+        for s, hist in sorted(self._generated.items()):
+            lay = hist[0]
+            for seed, generation in hist[1:]:
+                new, _ = _lp.keyed_layout(self.level_objects[int(los[s])], self.meta, self.num_agents, self.dims, seed, s, generation)
+                lay = new if new is not None else lay            # a failed draw leaves the slot as it was
+            self.layouts[s] = lay
+            self._lay_records[s] = lay.init_record(self.dims, s)
+            self._lay_desc[s] = lay.obs_descriptor(self.meta, self.dims)
+        self._generated = {}
+
+    def generate_failures(self):
+        """device draws that failed (the reference raises there; the slot kept its layout) since the level programs were loaded"""
+        return int(_native.lib().cz_generate_failures(self._h))
+
     def set_layout_group(self, groups, active):
         """From the next step on the envs draw their next episodes from part `active` of their pool slices cut into `groups`
         equal parts (cz_set_layout_group; waits on the device for the updates issued so far)."""
@@ -351,7 +419,7 @@ class CookingVecEnv:
         self._lay_groups, self._lay_active = int(groups), int(active)
         self.rotation_events.append((self._steps, "group", int(groups), int(active)))
 
-    def rotate_layouts(self, every, *, groups=2, seed=0, prefetch=2, blocking=True):
+    def rotate_layouts(self, every, *, groups=2, seed=0, prefetch=2, blocking=True, device=False):
         """Keep the layout pool fresh while the batch steps - the batched counterpart of the reference instantiating a new
         level at every reset (cooking_env.py:191-195, parsing.py:21-151).  The pool slices are cut into `groups` parts; the
         envs draw from one; every `every` steps (at the next call boundary) the next part becomes the one drawn from, and
@@ -362,7 +430,10 @@ class CookingVecEnv:
         `blocking=False` never waits: a refill whose layouts are not ready yet is tried again at the next call boundary (and
         the next switch with it), which keeps the stepping thread free of stalls at the price of a timing-dependent schedule.
         Steps that run as replays of a graph of the CALLER (captured `step_device*` launches) are invisible here: report them with
-        `advance(k)` after every replay - the switches and refills then happen in that call, between replays."""
+        `advance(k)` after every replay - the switches and refills then happen in that call, between replays.
+        `device=True`: the same switch / refill schedule with no process, no threads and no waiting - refill number r (1, 2, ...)
+        is `generate_layouts` of the retired part with generation r under `seed`, a launch on the env's own stream
+        (`rotation_events` then holds "generated" entries; `keyed_layouts` turns them into `Layout`s)."""
         if self._rot is not None:
             raise RuntimeError("rotate_layouts is already running")
         if groups < 2 or any(count % groups for _, count in self.pool_slices):
@@ -373,6 +444,13 @@ class CookingVecEnv:
         start = self._lay_active if self._lay_groups == groups else 0        # the part in use now: the first one to be refilled
         rot = {"groups": int(groups), "every": int(every), "flip_due": self._steps + int(every), "refill_due": None, "n_refills": 0,
                "blocking": bool(blocking), "start": int(start)}
+        if device:
+            if self._programs_for != len(self.layouts):
+                self.load_level_programs()
+            rot["device"], rot["seed"] = True, int(seed)
+            self._rot = rot
+            self.set_layout_group(groups, start)
+            return
 
         # The instantiation is plain Python (engine/load_level.py, the reference's draw order) and takes milliseconds per batch:
         # in a thread it would hold the interpreter lock against the thread that issues the steps, so it runs in a process of
@@ -410,6 +488,8 @@ class CookingVecEnv:
     def stop_rotation(self):
         if self._rot is not None:
             rot, self._rot = self._rot, None
+            if rot.get("device"):
+                return
             rot["stop"].set()
             try:
                 while True:                                   # (a producer blocked on a full queue sees the stop flag within 0.1 s)
@@ -431,7 +511,7 @@ class CookingVecEnv:
 
     def rotation_ready(self):
         """refills the background process has ready right now (a measurement may want to start with a full queue)"""
-        return 0 if self._rot is None else self._rot["ready"].qsize()
+        return 0 if self._rot is None or self._rot.get("device") else self._rot["ready"].qsize()
 
     def _issued(self, k):
         """a device-pointer call of k steps has returned: count them - unless the call was CAPTURED into a graph of the caller
@@ -461,6 +541,13 @@ class CookingVecEnv:
         rot = self._rot
         if rot is None:
             return
+        if rot["refill_due"] is not None and self._steps >= rot["refill_due"] and rot.get("device"):
+            g = (rot["start"] + rot["n_refills"]) % rot["groups"]             # the part retired by the last switch
+            for base, count in self.pool_slices:
+                sub = count // rot["groups"]
+                self.generate_layouts(base + g * sub, sub, rot["n_refills"] + 1, seed=rot["seed"], mirror=False)
+            rot["refill_due"] = None
+            rot["n_refills"] += 1
         if rot["refill_due"] is not None and self._steps >= rot["refill_due"]:
             batch = None
             while batch is None:

@@ -27,7 +27,11 @@
  *   - a scheme1 interaction aimed off the grid (IndexError): no-op;
  *   - max_steps reached while an agent is despawned (IndexError, cooking_env.py:337): the step truncates;
  *   - a respawn that finds no free cell in 1001 tries, or a candidate beyond the grid (ValueError, parsing.py:159,166): the agent stays
- *     where it is and cz_spawn_exhausted counts it.
+ *     where it is and cz_spawn_exhausted counts it;
+ *   - a level draw of cz_generate_layouts that fails - no position for an object in 10 001 tries or for an agent in 1 001, more
+ *     objects of a class than the meta file lists ("Too many X objects loaded"), more object slots than max_dyn (ValueError,
+ *     parsing.py:44,73,99,112,137,149), a second Switch (AttributeError on its first press): the pool slot keeps the layout it held
+ *     and cz_generate_failures counts it.
  * Refused before anything runs: a level with two Switches, action scheme 2, more than 4 agents (the reference's own limits or crashes).
  */
 #ifndef COOKINGZOO_H
@@ -42,7 +46,7 @@ extern "C" {
 
 /* The one place the ABI number lives: cz_abi_version() returns it, cooking_zoo_amd/_native.py parses it from this file
  * and refuses a library that reports another one, __graft_entry__.build() and the tests compare against it. */
-#define CZ_ABI_VERSION 8
+#define CZ_ABI_VERSION 9
 
 typedef struct cz_handle_s *cz_handle;
 
@@ -102,7 +106,8 @@ int cz_set_stream(cz_handle h, void *hip_stream);
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
- * cz_set_layout_group ...) are not; the last two say so, the others fail with HIP's own error.  The captured launches carry the
+ * cz_set_layout_group ...) are not; the last two say so, the others fail with HIP's own error.  (cz_generate_layouts is a pure
+ * launch too, and so is a cz_set_layout_group that only changes the active part: see there.)  The captured launches carry the
  * table pointers of their time: after cz_load_layouts / cz_load_recipes / cz_set_spawn / cz_set_compact_output capture again.
  * cz_stream_capturing: 1 while the handle's stream is a stream of the caller that is being captured, else 0 - a host layer that
  * keeps count of the steps it issued (cooking_zoo_amd: layout rotation schedules) must not count captured launches as steps:
@@ -143,6 +148,36 @@ int cz_load_layouts(cz_handle h, const uint32_t *init_records, const uint32_t *o
 int cz_update_layouts(cz_handle h, int32_t first, int32_t count, const uint32_t *init_records, const uint32_t *obs_desc);
 int cz_set_layout_group(cz_handle h, int32_t groups, int32_t active);
 int64_t cz_layout_updates(cz_handle h);
+
+/* Fresh layouts DRAWN ON THE DEVICE: what parse_level_layout / parse_static_objects / parse_dynamic_objects / parse_agents
+ * (parsing.py:5-18, 21-76, 79-115, 118-151) do at every reset of the reference (cooking_env.py:191-195), one wavefront per pool
+ * slot, followed by what cooking_zoo_amd/cooking_world/layout.py makes of the result (initial record, observation descriptor in
+ * the order get_feature_vector iterates, cooking_env.py:352-373).  No producer process, no host arrays, no PCIe.
+ * DRAWS.  The n-th draw of pool slot s in generation g under `seed`, counted in the reference's call order - one random() per
+ * placement attempt of an OPTIONAL object, then random.sample(X_POSITION, 1), random.sample(Y_POSITION, 1) - is
+ * cz_spawn_uniform(seed, env_global = s, episode = 0, t = g, agent = 0x100, draw = n), and a coordinate is
+ * candidates[(int)(u * n_candidates)].  s is the index in the whole pool, so every shard of a sharded batch generates the same
+ * bytes.  Host model: engine/load_level.py instantiate with level_program.KeyedDraws; tests/golden/layouts_keyed_ref.json holds what
+ * the unmodified reference parser returns under this stream.
+ * cz_load_level_programs: `programs` holds n_levels (1..255) level programs one after the other, `words` uint32 in all - the
+ * level file, the meta file and the batch geometry as flat words (cooking_zoo_amd/cooking_world/engine/level_program.py
+ * compile_level documents them) -; level_of_slot[i] (NULL: all 0) is the level that pool slot i is drawn from, one byte per
+ * slot of the resident pool.  Validates (class codes, offsets, candidates within [0, width] x [0, height] - the reference raises
+ * on a drawn position beyond that, parsing.py:34 - geometry and feature length against the handle) and uploads; call it again
+ * after cz_load_layouts.
+ * cz_generate_layouts: ONE launch on the handle's stream that redraws slots [first, first + count) with generation
+ * `generation`.  Stream-ordered with the steps issued before and after it and with cz_set_layout_group; nothing is allocated,
+ * copied or waited for, so it is legal while the caller captures that stream (as is a cz_set_layout_group that only switches
+ * the active part of a cut already in place, with no cz_update_layouts outstanding).  The rule of cz_update_layouts holds:
+ * never redraw slots that envs can still draw or are still playing on.  Once the pool is cut into groups > 1 parts, a range that
+ * touches the part the envs draw from is refused (the parts are taken per run of slots of one level in level_of_slot - the
+ * pool slices cooking_zoo_amd uses); with one group it is the caller's duty, which allows filling the pool before the first
+ * reset.  Inside a capture the checks see the state at capture time.  Counts into cz_layout_updates (when issued or captured).
+ * A draw that fails (see the deviations above) leaves the slot's record and descriptor as they were;
+ * cz_generate_failures: how many did since cz_load_level_programs (waits for the stream), -1 on error. */
+int cz_load_level_programs(cz_handle h, const uint32_t *programs, int64_t words, int32_t n_levels, const uint8_t *level_of_slot);
+int cz_generate_layouts(cz_handle h, int32_t first, int32_t count, uint64_t seed, uint32_t generation);
+int64_t cz_generate_failures(cz_handle h);
 
 /* Agent despawn / respawn (cooking_world.py:267-290 handle_agent_spawn, despawn_agent, respawn_agent; parsing.py:154-167
  * generate_location) for every world of the batch, evaluated by the step kernels themselves - on every path: cz_step,

@@ -1,0 +1,347 @@
+"""GPU: level instantiation on the device (cz_load_level_programs / cz_generate_layouts, csrc/cz_generate.h) - what the reference
+does at every reset (cooking_env.py:191-195, parsing.py:5-151).  The pool slots a launch redraws must hold, byte for byte, the
+initial record and the observation descriptor of the host model's layouts (load_level.instantiate under
+level_program.KeyedDraws), which tests/golden/layouts_keyed_ref.json pins to the unmodified reference parser; read back through
+reset + cz_get_state + cz_observe, next to a twin env that received the model's layouts over the host path (cz_update_layouts)."""
+import ctypes as C
+import faulthandler
+import json
+import multiprocessing
+import random
+
+import numpy as np
+import pytest
+
+from cooking_zoo_amd import _native, soa
+from cooking_zoo_amd.cooking_world.engine import level_program as lp
+from cooking_zoo_amd.cooking_world.engine import load_level as ll
+from layout_keyed_common import CASES, CASE_IDS, assert_matches_reference, case_tables
+
+pytestmark = pytest.mark.gpu
+
+FOUR = ["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"]
+
+
+@pytest.fixture(autouse=True)
+def time_limit():
+    """every test of this file ends after five minutes, also when it hangs inside a HIP call"""
+    faulthandler.dump_traceback_later(300, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def strip(recs):
+    r = recs.copy()
+    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0          # running returns: device-side statistics only
+    return r
+
+
+def prefilled(n, level, meta, agents, *, pool, max_dyn=None, max_steps=30, **kw):
+    """a batch whose whole pool holds ONE fixed, valid, recognisable layout per level: the host loader's draw under Random(99)"""
+    from cooking_zoo_amd.vec_env import CookingVecEnv
+    levels = [level] if isinstance(level, str) else list(level)
+    m = ll.load_meta_file(meta)
+    fixed = [[ll.instantiate(ll.load_level_file(l), m, agents, random.Random(99))] * pool for l in levels]
+    return CookingVecEnv(n, level, meta, agents, max_steps, FOUR[:max(agents, 1)], action_scheme="scheme3", layouts=fixed,
+                         max_dyn=max_dyn, auto_reset=True, **kw)
+
+
+def read_pool(env, slots):
+    """(records, observations) of the env's first len(slots) worlds reset onto pool slots `slots`"""
+    slots = np.asarray(slots, dtype=np.int32)
+    obs = env.reset(layout_ids=slots, env_begin=0, env_count=len(slots))
+    return env.get_state()[:len(slots)], np.array(obs)
+
+
+def host_update(twin, first, layouts):
+    """the model's layouts over the host path; the switch makes the staged copy land before the next call (cz_set_layout_group)"""
+    twin.update_layouts(first, layouts)
+    twin.set_layout_group(1, 0)
+
+
+def check_pool(env, twin, expected):
+    """every slot of the pool, read back from `env` (device draws) and `twin` (the model's layouts over cz_update_layouts), and
+    directly against Layout.init_record of `expected`"""
+    L, n, dims = len(expected), env.num_envs, env.dims
+    for b in range(0, L, n):
+        slots = np.arange(b, min(b + n, L))
+        rg, og = read_pool(env, slots)
+        rt, ot = read_pool(twin, slots)
+        assert np.array_equal(rg, rt), f"records of slots {b}.."
+        assert np.array_equal(bits(og), bits(ot)), f"observations of slots {b}.."
+        for k, s in enumerate(slots):
+            want = expected[s].init_record(dims, int(s))
+            assert rg[k, soa.W_LAYOUT] == s
+            assert np.array_equal(rg[k, soa.AGENT_WORD0:soa.AGENT_WORD0 + 4], want[soa.AGENT_WORD0:soa.AGENT_WORD0 + 4]), f"agents of slot {s}"
+            assert np.array_equal(rg[k, dims.cells_word0:], want[dims.cells_word0:]), f"cells / dyn0 / dyn1 of slot {s}"
+
+
+def run_case(case, max_dyn, instance):
+    level, meta, A, dims = case_tables(case, max_dyn)
+    L = 208
+    env = prefilled(32, case["level"], case["meta"], A, pool=L, max_dyn=max_dyn)
+    twin = prefilled(32, case["level"], case["meta"], A, pool=L, max_dyn=max_dyn)
+    assert env.dims.as_tuple() == dims.as_tuple() and _native.lib().cz_diag_instance(env._h) == instance
+    expected = list(env.layouts)
+    fixed_key = expected[0].key()
+    failed = 0
+    for ref in case["draws"]:
+        if ref["slot"] >= L:
+            continue
+        first = max(0, ref["slot"] - 3)
+        count = min(8, L - first)
+        env.generate_layouts(first, count, ref["generation"], seed=ref["seed"], mirror=False)
+        lays, f = env.keyed_layouts(first, count, ref["seed"], ref["generation"], previous=expected[first:first + count])
+        failed += f
+        if max_dyn is None:                                   # (the level's own capacity: the draw the reference fixture recorded)
+            assert_matches_reference(lays[ref["slot"] - first], ref)
+        expected[first:first + count] = lays
+        host_update(twin, first, lays)
+    assert sum(l.key() != fixed_key for l in expected) >= 20, "the generated part must differ from the prefill"
+    check_pool(env, twin, expected)
+    assert env.generate_failures() == failed
+    assert _native.lib().cz_layout_updates(env._h) == 8 * sum(r["slot"] < L for r in case["draws"])
+    env.resolve_layouts()
+    assert [l.key() for l in env.layouts] == [l.key() for l in expected]
+    env.close(); twin.close()
+
+
+NATURAL = {"coop_test": 0, "coexistence_test": 0, "switch_test": 0, "crowded_6x5": 0, "dense_8x8": 0, "edge_8x8": 0,
+           "large_16x16": 1, "limit_32x8": 1, "huge_objs_16x16": 2, "huge_32x32": 2}
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_generated_slots_equal_the_model_on_the_natural_instance(case):
+    run_case(case, None, NATURAL[case["level"]])
+
+
+@pytest.mark.parametrize("max_dyn,instance", [(128, 1), (129, 2), (255, 2)])
+def test_one_level_padded_onto_the_larger_instances(max_dyn, instance):
+    """coop_test (12 slots, 49 cells) with its slot capacity padded, as test_gpu_instance_edges.py does: the record is longer and
+    the huge instance keeps another LDS image, so the descriptor's halfword offsets differ"""
+    run_case(next(c for c in CASES if c["level"] == "coop_test" and c["num_agents"] == 2), max_dyn, instance)
+
+
+def test_mixed_level_batch_draws_every_slot_from_its_own_level():
+    """config 3's shape: three levels in one batch, one pool slice each; the whole pool filled before the first reset (one group:
+    the caller's duty, as with cz_update_layouts)"""
+    levels = ["coop_test", "coexistence_test", "switch_test"]
+    env = prefilled(48, levels, "example", 2, pool=16)
+    twin = prefilled(48, levels, "example", 2, pool=16)
+    assert env.pool_slices == [(0, 16), (16, 16), (32, 16)]
+    env.generate_layouts(0, 48, 1, seed=21, mirror=False)
+    lays, failed = env.keyed_layouts(0, 48, 21, 1, previous=list(env.tables.layouts))
+    host_update(twin, 0, lays)
+    check_pool(env, twin, lays)
+    assert env.generate_failures() == failed
+    assert all(l.n_switches() == 1 for l in lays[32:]) and not any(l.n_switches() for l in lays[:32])
+    # coop_test always has three Cutboards, coexistence_test draws each of them with probability 0.7
+    assert all(len(l.static_lists["Cutboard"]) == 3 for l in lays[:16]) and any(len(l.static_lists.get("Cutboard", [])) < 3 for l in lays[16:32])
+    env.close(); twin.close()
+
+
+def test_pools_do_not_depend_on_batch_size_or_shard():
+    a = prefilled(8, "large_16x16", "large_16x16", 4, pool=64)
+    b = prefilled(24, "large_16x16", "large_16x16", 4, pool=64, env_id_base=100000)
+    for e in (a, b):
+        e.generate_layouts(16, 40, 6, seed=(1 << 50) + 3, mirror=False)
+    for s0 in range(0, 64, 8):
+        ra, oa = read_pool(a, np.arange(s0, s0 + 8))
+        rb, ob = read_pool(b, np.arange(s0, s0 + 8))
+        assert np.array_equal(ra, rb) and np.array_equal(bits(oa), bits(ob)), f"slots {s0}.."
+    a.close(); b.close()
+
+
+def test_a_failed_draw_leaves_the_slot_as_it_was(tmp_path):
+    """a program whose meta cap is too small - two Cutboards where coexistence_test draws up to three: "Too many Cutboard objects
+    loaded" in the reference whenever all three OPTIONAL boards come up.  A refused input: those slots keep the prefill."""
+    from cooking_zoo_amd.vec_env import CookingVecEnv
+    meta = json.load(open(ll._resolve("example", "meta_files")))
+    for d in meta:
+        if "Cutboard" in d:
+            d["Cutboard"] = 2
+    path = str(tmp_path / "two_boards.json")
+    json.dump(meta, open(path, "w"))
+    m = ll.load_meta_file(path)
+    level = ll.load_level_file("coexistence_test")
+    dims = soa.Dims(7, 7, ll.level_max_dyn(level), 2, lp.feature_length(m))
+    fixed = next(l for l in (lp.keyed_layout(level, m, 2, dims, 1, s, 0)[0] for s in range(100)) if l is not None)
+    mk = lambda: CookingVecEnv(32, "coexistence_test", path, 2, 30, FOUR[:2], action_scheme="scheme3", layouts=[fixed] * 64, auto_reset=True)
+    env, twin = mk(), mk()
+    env.generate_layouts(8, 48, 3, seed=77, mirror=False)
+    lays, failed = env.keyed_layouts(8, 48, 77, 3, previous=[fixed] * 48)
+    assert 5 <= failed <= 40, failed                                     # (0.7 ** 3 = 0.34 of the draws)
+    host_update(twin, 8, lays)
+    expected = [fixed] * 8 + lays + [fixed] * 8
+    check_pool(env, twin, expected)
+    assert env.generate_failures() == failed
+    assert sum(l is fixed for l in lays) == failed
+    env.close(); twin.close()
+
+
+def test_refusals():
+    env = prefilled(8, "coop_test", "example", 2, pool=16)
+    L, h = _native.lib(), env._h
+    with pytest.raises(_native.NativeError, match="level programs not loaded"):
+        _native.check(h, L.cz_generate_layouts(h, 0, 4, 1, 1))
+    prog = lp.compile_level(env.level_objects[0], env.meta, 2, env.dims)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    bad = prog.copy(); bad[lp.H_W] += 1
+    with pytest.raises(_native.NativeError, match="another batch geometry"):
+        _native.check(h, L.cz_load_level_programs(h, ptr(bad), bad.size, 1, None))
+    bad = prog.copy(); bad[int(prog[lp.H_OFF_ENTRIES]) + lp.ENTRY_HEADER_WORDS] = env.dims.W + 1       # first x candidate beyond the far edge
+    with pytest.raises(_native.NativeError, match="out of bounds"):
+        _native.check(h, L.cz_load_level_programs(h, ptr(bad), bad.size, 1, None))
+    bad = prog.copy(); bad[int(prog[lp.H_OFF_ENTRIES])] = 9
+    with pytest.raises(_native.NativeError, match="unknown object class"):
+        _native.check(h, L.cz_load_level_programs(h, ptr(bad), bad.size, 1, None))
+    with pytest.raises(_native.NativeError, match="truncated|words given"):
+        _native.check(h, L.cz_load_level_programs(h, ptr(prog), prog.size - 1, 1, None))
+    env.load_level_programs()
+    with pytest.raises(_native.NativeError, match="outside the resident pool"):
+        env.generate_layouts(12, 8, 1)
+    env.set_layout_group(2, 1)
+    with pytest.raises(_native.NativeError, match="which the envs draw from"):
+        env.generate_layouts(4, 8, 1)                                     # slots 8..11 are in the part in use
+    env.generate_layouts(0, 8, 1)
+    assert env.generate_failures() == 0
+    env.close()
+
+
+def make_rotating(n, max_steps, num_layouts):
+    from cooking_zoo_amd.vec_env import CookingVecEnv
+    return CookingVecEnv(n, "coop_test", "example", 2, max_steps, ["TomatoLettuceSalad", "CarrotBanana"], action_scheme="scheme3",
+                         num_layouts=num_layouts, layout_seed=11, auto_reset=True)
+
+
+def test_device_rotation_is_bit_exact_and_needs_no_process():
+    """test_gpu_layout_rotation.py's run - 512 envs, 2000 steps, max_steps 20, a 64-slot pool in two parts switched every 50 steps
+    and refilled 22 steps after each switch - with the refills drawn on the device: every output of every step equals the oracle's,
+    which is fed the host model's layouts of every "generated" event at the same step index."""
+    from oracle_binding import VecOracle
+    n, T = 512, 2000
+    env = make_rotating(n, 20, 64)
+    orc = VecOracle.from_vec_env(env)
+    assert np.array_equal(bits(env.reset()), bits(orc.reset()))
+    current = list(env.layouts)
+    keys = {l.key() for l in current}
+    env.rotate_layouts(50, groups=2, seed=3, device=True)
+    assert not [p for p in multiprocessing.active_children() if p.name == "cz-layout-rotation"]
+    seen, played = 0, set()
+    rng = np.random.default_rng(2)
+    actions = []
+    for t in range(T):
+        for ev in env.rotation_events[seen:]:
+            if ev[1] == "generated":
+                _, _, first, count, seed, generation = ev
+                lays, _ = env.keyed_layouts(first, count, seed, generation, previous=current[first:first + count])
+                current[first:first + count] = lays
+                keys |= {l.key() for l in lays}
+                ev = (ev[0], "layouts", first, lays)
+            orc.apply_rotation_event(ev)
+        seen = len(env.rotation_events)
+        acts = rng.integers(0, env.n_actions, size=(n, 2), dtype=np.int32)
+        actions.append(acts)
+        og, rg, tg, ug = env.step(acts)
+        oo, ro, to, uo = orc.step(acts)
+        assert np.array_equal(bits(og), bits(oo)), f"observation at step {t}"
+        assert np.array_equal(bits(rg), bits(ro)) and np.array_equal(tg, to) and np.array_equal(ug, uo), f"rewards / flags at step {t}"
+        if t % 97 == 0:
+            recs = env.get_state()
+            assert np.array_equal(strip(recs), orc.records), f"records at step {t}"
+            played |= {current[i].key() for i in np.unique(recs[:, soa.W_LAYOUT])}
+    final = env.get_state()
+    assert np.array_equal(strip(final), orc.records)
+    refills = [ev for ev in env.rotation_events if ev[1] == "generated"]
+    switches = [ev for ev in env.rotation_events if ev[1] == "group"]
+    assert len(refills) >= 30 and len(switches) >= 35 and not [ev for ev in env.rotation_events if ev[1] == "layouts"]
+    assert [ev[5] for ev in refills] == list(range(1, len(refills) + 1))          # generation = refill number
+    assert len(keys) > 64 + 200, f"the refills brought {len(keys)} distinct layouts into the pool"
+    assert len(played) > 64, f"envs were seen playing on {len(played)} distinct layouts"
+    assert _native.lib().cz_layout_updates(env._h) == 32 * len(refills)
+    assert env.generate_failures() == 0
+    assert not [p for p in multiprocessing.active_children() if p.name == "cz-layout-rotation"]
+    env.resolve_layouts()
+    assert [l.key() for l in env.layouts] == [l.key() for l in current]
+    events = list(env.rotation_events)
+    env.close()
+    # the schedule does not depend on timing: a second run issues the same events at the same steps and ends in the same state
+    again = make_rotating(n, 20, 64)
+    again.reset(return_obs=False)
+    again.rotate_layouts(50, groups=2, seed=3, device=True)
+    for acts in actions:
+        again.step(acts, return_obs=False)
+    assert again.rotation_events == events
+    assert np.array_equal(again.get_state(), final)
+    again.close()
+
+
+def test_generate_steps_and_switch_captured_in_one_graph():
+    """[cz_generate_layouts of the retired part, K steps, cz_set_layout_group] twice - once per part of the pool - captured on a
+    stream of the caller and replayed: state, outputs and pool equal the same calls issued directly"""
+    from test_gpu_capture import Hip, buffers
+    hip = Hip()
+    n, A, K, K2, period, R = 256, 2, 10, 30, 40, 5                      # K2 >= max_steps + 2: a part is retired before it is redrawn
+
+    def make():
+        from cooking_zoo_amd.vec_env import CookingVecEnv
+        return CookingVecEnv(n, "coop_test", "example", 2, 25, ["TomatoLettuceSalad", "CarrotBanana"], action_scheme="scheme3",
+                             num_layouts=16, layout_seed=11, auto_reset=True)
+    env, ref = make(), make()
+    be, br = buffers(env), buffers(ref)
+    ring = np.random.default_rng(5).integers(0, 5, size=(period, n, A), dtype=np.int32)
+    de, dr = env.alloc((period, n, A), np.int32), ref.alloc((period, n, A), np.int32)
+    de.from_host(ring); dr.from_host(ring)
+    stream = C.c_void_p()
+    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
+    for e in (env, ref):
+        e.reset(return_obs=False)
+        e.load_level_programs()
+        e.set_layout_group(2, 0)
+    env.set_stream(stream)
+
+    def round_trip(e, d, b):
+        for part in (1, 0):
+            e.generate_layouts(8 * part, 8, 1 + part, seed=4, mirror=False)          # the part the envs do not draw from
+            e.step_device_ring(K, d, n * A, period, 0, b["obs"], b["rew"], b["term"], b["trunc"])
+            e.set_layout_group(2, part)
+            e.step_device_ring(K2, d, n * A, period, K, b["obs"], b["rew"], b["term"], b["trunc"])
+    graph, gexec = C.c_void_p(), C.c_void_p()
+    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
+    round_trip(env, de, be)
+    with pytest.raises(_native.NativeError, match="not inside a stream capture"):
+        env.set_layout_group(4, 0)                                        # a new cut is not a pure launch
+    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
+    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    assert np.array_equal(env.get_state()[:, soa.W_T], ref.get_state()[:, soa.W_T]), "capturing must not have stepped anything"
+    for _ in range(R):
+        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
+        round_trip(ref, dr, br)
+    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    ref.sync()
+    assert np.array_equal(env.get_state(), ref.get_state())
+    assert env.stats() == ref.stats() and env.stats()["episodes"] > n
+    for k in ("obs", "rew", "term", "trunc"):
+        assert np.array_equal(be[k].to_host().view(np.uint8), br[k].to_host().view(np.uint8)), k
+    assert env.generate_failures() == ref.generate_failures() == 0
+    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
+    env.set_stream(None)
+    hip.lib.hipStreamDestroy(stream)
+    # the pools: equal, and what the model says
+    want, _ = env.keyed_layouts(0, 8, 4, 1)
+    want += env.keyed_layouts(8, 8, 4, 2)[0]
+    twin = make()
+    host_update(twin, 0, want)
+    for e in (env, ref):
+        e.set_layout_group(1, 0)
+    for s0 in (0, 8):
+        re_, oe = read_pool(env, np.arange(s0, s0 + 8))
+        rr, orf = read_pool(ref, np.arange(s0, s0 + 8))
+        rt, ot = read_pool(twin, np.arange(s0, s0 + 8))
+        assert np.array_equal(strip(re_), strip(rr)) and np.array_equal(bits(oe), bits(orf))
+        assert np.array_equal(strip(re_)[:, soa.AGENT_WORD0:], strip(rt)[:, soa.AGENT_WORD0:]) and np.array_equal(bits(oe), bits(ot))
+    env.close(); ref.close(); twin.close()

@@ -1076,6 +1076,7 @@ def main():
             [(1220, "bumper", 100)], args.out)
     sets["api_traces"] = lambda: api_traces(args.out)
     sets["layouts_ref"] = lambda: layout_draws(args.out)
+    sets["layouts_keyed_ref"] = lambda: layout_draws_keyed(args.out)
     sets["aec_traces"] = lambda: aec_traces(args.out)
     sets["symbolic_traces"] = lambda: symbolic_traces(args.out)
     sets["custom_recipes"] = lambda: custom_recipes(args.out)          # (registers recipes in the reference: keep last)
@@ -1426,6 +1427,65 @@ def layout_draws(out_dir):
     with open(path, "w") as f:
         json.dump(out, f)
     print(f"[golden] layouts_ref: {len(out)} cases, {os.path.getsize(path) / 1024:.0f} KiB")
+
+
+def layout_draws_keyed(out_dir):
+    """The layouts the UNMODIFIED reference parser instantiates when every draw of `CookingWorld.load_level` - random.random
+    (the OPTIONAL test, parsing.py:30, :88) and random.sample (x, y: parsing.py:32-33, :90-91, :129-130) - is answered, in call
+    order, with the keyed stream of the device generator: draw n of pool slot `slot`, generation `generation` under `seed` is
+    spawn.uniform(seed, slot, generation, LAYOUT_TAG, n), and sample(pop, 1) -> [pop[int(u * len(pop))]] (the mapping of
+    capture_spawn_keyed_episode).  Nothing of the reference is replaced but the two random sources.  For the host model
+    (load_level.instantiate under level_program.KeyedDraws) and, through it, cz_generate_layouts."""
+    from cooking_zoo.cooking_world.cooking_world import CookingWorld
+    from cooking_zoo.cooking_world.actions import ActionScheme3
+    from cooking_zoo_amd import spawn as czspawn
+    from cooking_zoo_amd.cooking_world.engine.level_program import LAYOUT_TAG
+    L = os.path.join(REPO, "cooking_zoo_amd", "utils", "level")
+    M = os.path.join(REPO, "cooking_zoo_amd", "utils", "meta_files")
+    own = lambda level, meta, A: (os.path.join(L, level + ".json"), os.path.join(M, meta + ".json"), A)
+    # layout_draws' levels (coexistence_test and crowded_6x5 carry OPTIONAL objects), one more OPTIONAL level, the wide one, and
+    # two for the huge kernel instance; agent counts as the meta files allow (edge, limits, huge_objs: 3)
+    cases = [("coop_test", "example", 2), ("coop_test", "example", 1), ("coexistence_test", "example", 2), ("switch_test", "example", 2),
+             own("large_16x16", "large_16x16", 4), own("crowded_6x5", "crowded_6x5", 3), own("dense_8x8", "dense_8x8", 4),
+             own("edge_8x8", "edge", 3), own("limit_32x8", "limits", 3), own("huge_objs_16x16", "huge_objs_16x16", 3),
+             own("huge_32x32", "huge_32x32", 4)]
+    keys = [(3, 0, 0), (3, 1, 5), (12345, 7, 63), ((1 << 40) + 17, 2, 200), (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF, 65534)]
+    out = []
+    orig_random, orig_sample = random.random, random.sample
+    for level, meta, A in cases:
+        draws = []
+        for seed, generation, slot in keys:
+            st = {"n": 0}
+
+            def keyed_random():
+                u = float(czspawn.uniform(seed, slot, generation, LAYOUT_TAG, st["n"]))
+                st["n"] += 1
+                return u
+
+            def keyed_sample(population, k):
+                assert k == 1
+                return [population[int(keyed_random() * len(population))]]
+
+            random.random, random.sample = keyed_random, keyed_sample
+            try:
+                w = CookingWorld(ActionScheme3, meta)
+                w.load_level(level, A)
+            finally:
+                random.random, random.sample = orig_random, orig_sample
+            statics = {k: [[o.location[0], o.location[1]] for o in v] for k, v in w.world_objects.items()
+                       if issubclass(wo.StringToClass[k], StaticObject)}
+            dyn = [[k, [[o.location[0], o.location[1]] for o in v]] for k, v in w.world_objects.items()
+                   if issubclass(wo.StringToClass[k], DynamicObject) and v]
+            draws.append({"seed": seed, "generation": generation, "slot": slot, "n_draws": st["n"], "width": w.width,
+                          "height": w.height, "statics": statics, "dynamics": dyn,
+                          "agents": [[a.location[0], a.location[1]] for a in w.agents]})
+        out.append({"level": os.path.splitext(os.path.basename(level))[0], "meta": os.path.splitext(os.path.basename(meta))[0],
+                    "num_agents": A, "draws": draws})
+    path = os.path.join(out_dir, "layouts_keyed_ref.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print(f"[golden] layouts_keyed_ref: {len(out)} levels x {len(keys)} keys, most draws {max(d['n_draws'] for c in out for d in c['draws'])}, "
+          f"{os.path.getsize(path) / 1024:.0f} KiB")
 
 
 if __name__ == "__main__":
