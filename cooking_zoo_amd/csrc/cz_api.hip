@@ -1052,6 +1052,25 @@ static int ready(cz_handle h) {
     return 0;
 }
 
+// Which kernel a launch gets (the same table is in DESIGN.md section 4).  P.wt is decided by then.
+//   fused, P.actions                  -> ROLLOUT_ACTIONS      (cz_rollout_actions, fused rings)
+//   fused, P.codes without P.obs      -> ROLLOUT_CODES_ONLY   (cz_rollout_compact)
+//   fused, P.codes and P.obs          -> ROLLOUT_CODES        (cz_rollout_compact)
+//   fused, neither                    -> ROLLOUT              (cz_rollout)
+//   one step, P.codes                 -> STEP_CODES           (cz_step_device_compact, cz_set_compact_output)
+//   one step otherwise                -> STEP, and of that the lean kernel when the handle allows it (CZ_LEAN), the instance has one and
+//                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
+//                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
+//   one step without P.actions        -> hipErrorInvalidValue
+static hipError_t choose_step(cz_handle h, const Params &P, bool fused, StepChoice &c) {
+    c.lean = false;
+    if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : !P.codes ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
+    else c.mode = P.codes ? STEP_CODES : STEP;
+    if (c.mode == STEP)
+        c.lean = h->lean_enabled && h->kl.has_lean && P.obs && !P.marks_out && !P.wide && !(P.auto_reset & 2) && P.F <= 128 * OBS_PAIRS && P.wt == 1;
+    return !fused && !P.actions ? hipErrorInvalidValue : hipSuccess;
+}
+
 static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, bool fused = false) {
     if ((P.auto_reset & 2) && h->spawn_layouts != h->n_layouts)
         return fail(h, "despawn / respawn is on, but the layout pool was reloaded since cz_set_spawn (now %d layouts): call cz_set_spawn "
@@ -1089,11 +1108,11 @@ static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, boo
         h->kev_used += 2;
         HIPCHK(h, hipEventRecord(e0, stream));
     }
-    // the lean one-step kernel (k_step_lean, cz_kernels.h) when every setting it fixes at compile time holds for this launch
-    const bool lean = !fused && h->lean_enabled && h->kl.step_lean && P.obs && !P.codes && !P.marks_out && !P.wide && !(P.auto_reset & 2) &&
-                      P.F <= 128 * OBS_PAIRS && P.wt == 1;
-    h->last_step_lean = lean ? 1 : 0;
-    HIPCHK(h, lean ? h->kl.step_lean(P, stream) : h->kl.step(P, stream, fused ? LAUNCH_FUSED : LAUNCH_ONE));
+    StepChoice choice;
+    const hipError_t chosen = choose_step(h, P, fused, choice);
+    h->last_step_lean = choice.lean ? 1 : 0;
+    HIPCHK(h, chosen);
+    HIPCHK(h, h->kl.step(P, stream, choice));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -1189,14 +1208,31 @@ static int set_device(cz_handle h) {
     return 0;
 }
 
-extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term,
-                              uint8_t *d_trunc) {
+// Begins a call that works on device pointers: the handle is ready, the entry point's own arguments are good (`bad_args`: its message
+// otherwise), a fused rollout (`rollout`: the entry point's name) stays inside the span the kernel addresses, the handle's device is
+// current, and a staged layout update whose time may have come is flushed - unless the caller is capturing.
+static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, const char *rollout = nullptr, int32_t T = 0) {
     if (ready(h)) return 1;
-    if (!d_actions) return fail(h, "cz_step_device: actions pointer is null");
+    if (!args_ok) return fail(h, "%s", bad_args);
+    // (the fused kernel addresses rewards / flags / actions with 32-bit offsets from the array base)
+    if (rollout && (uint64_t)T * (uint64_t)h->P.N * (uint64_t)h->P.A * 8ull > 0xFFFFFFFFull)
+        return fail(h, "%s: T * num_envs * num_agents * 8 must stay below 4 GiB (T <= %llu here): split the rollout", rollout,
+                    (unsigned long long)(0xFFFFFFFFull / ((uint64_t)h->P.N * h->P.A * 8ull)));
     if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;      // a staged layout update whose time may have come
+    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
+    return 0;
+}
+// the Params of one call: the handle's with the call's five buffers (one step; a rollout sets T, seed and step0 itself)
+static Params call_params(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
     Params P = h->P;
     P.actions = d_actions; P.obs = d_obs; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
+    return P;
+}
+
+extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term,
+                              uint8_t *d_trunc) {
+    if (begin_device_call(h, d_actions, "cz_step_device: actions pointer is null")) return 1;
+    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
     P.marks_out = h->marks_out_next; h->marks_out_next = nullptr;
     return launch_step(h, P);
 }
@@ -1204,12 +1240,9 @@ extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_o
 // The step with the observation as one byte per feature (and, optionally, the float64 one beside it): see observe() in cz_kernels.h.
 extern "C" int cz_step_device_compact(cz_handle h, const int32_t *d_actions, uint8_t *d_codes, double *d_obs, double *d_rewards,
                                       uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (!d_actions || !d_codes) return fail(h, "cz_step_device_compact: actions and codes pointers must not be null");
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
-    Params P = h->P;
-    P.actions = d_actions; P.obs = d_obs; P.codes = d_codes; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
+    if (begin_device_call(h, d_actions && d_codes, "cz_step_device_compact: actions and codes pointers must not be null")) return 1;
+    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
+    P.codes = d_codes;
     return launch_step(h, P);
 }
 // From now on EVERY one-step launch of the handle (cz_step_device, _many, _ring, cz_step) also writes the compact observation
@@ -1241,13 +1274,8 @@ static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d
 // without K trips through the host language.
 extern "C" int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_actions, int64_t action_stride, int32_t action_period,
                                    double *d_obs, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (!d_actions || K < 1 || action_period < 1) return fail(h, "cz_step_device_many: bad arguments");
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;      // a staged layout update whose time may have come
-    Params P = h->P;
-    P.obs = d_obs; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
-    P.actions = d_actions;
+    if (begin_device_call(h, d_actions && K >= 1 && action_period >= 1, "cz_step_device_many: bad arguments")) return 1;
+    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
     if (ring_fusable(h, P, K, action_stride)) return launch_ring_fused(h, P, K, d_actions, action_stride, action_period, 0);   // cz_set_ring_fused
     for (int32_t k = 0; k < K; ++k) {
         P.actions = d_actions + (int64_t)(k % action_period) * action_stride;
@@ -1343,9 +1371,7 @@ static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d
 // walks the run [first_slot, first_slot + K) piece by piece; launch = false only builds the graphs
 static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot, double *d_obs,
                      double *d_rewards, uint8_t *d_term, uint8_t *d_trunc, bool launch) {
-    Params P = h->P;
-    P.obs = d_obs; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
-    P.actions = d_ring;
+    Params P = call_params(h, d_ring, d_obs, d_rewards, d_term, d_trunc);
     if (ring_fusable(h, P, K, stride)) return launch ? launch_ring_fused(h, P, K, d_ring, stride, period, first_slot) : 0;
     // (inside a capture of the caller: plain launches - a capture of the library's own cannot nest in it)
     const bool graphs = !caller_capturing(h) && ring_select(h, d_ring, stride, period, d_obs, d_rewards, d_term, d_trunc);
@@ -1396,10 +1422,7 @@ extern "C" int cz_ring_prepare(cz_handle h, int32_t K, const int32_t *d_ring, in
 }
 extern "C" int cz_step_device_ring(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot,
                                    double *d_obs, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (!d_ring || K < 1 || period < 1 || first_slot < 0 || first_slot >= period) return fail(h, "cz_step_device_ring: bad arguments");
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;      // a staged layout update whose time may have come
+    if (begin_device_call(h, d_ring && K >= 1 && period >= 1 && first_slot >= 0 && first_slot < period, "cz_step_device_ring: bad arguments")) return 1;
     return ring_walk(h, K, d_ring, stride, period, first_slot, d_obs, d_rewards, d_term, d_trunc, true);
 }
 // Runs of cz_step_device_ring / cz_step_device_many as FUSED launches (opt-in): the K steps of a run whose action slots are densely
@@ -1430,17 +1453,9 @@ extern "C" int cz_launch_counts(cz_handle h, int64_t *graph_kernels, int64_t *di
 
 extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, double *d_obs, double *d_rewards,
                           uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (T < 1) return fail(h, "cz_rollout: T must be >= 1");
-    // (the kernel addresses rewards / flags with 32-bit offsets from the array base)
-    if ((uint64_t)T * (uint64_t)h->P.N * (uint64_t)h->P.A * 8ull > 0xFFFFFFFFull)
-        return fail(h, "cz_rollout: T * num_envs * num_agents * 8 must stay below 4 GiB (T <= %llu here): split the rollout",
-                    (unsigned long long)(0xFFFFFFFFull / ((uint64_t)h->P.N * h->P.A * 8ull)));
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;      // a staged layout update whose time may have come
-    Params P = h->P;
-    P.actions = nullptr; P.obs = d_obs; P.codes = nullptr; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc;
-    P.T = T; P.seed = seed; P.step0 = step0;
+    if (begin_device_call(h, T >= 1, "cz_rollout: T must be >= 1", "cz_rollout", T)) return 1;
+    Params P = call_params(h, nullptr, d_obs, d_rewards, d_term, d_trunc);
+    P.codes = nullptr; P.T = T; P.seed = seed; P.step0 = step0;
     return launch_step(h, P, nullptr, true);
 }
 
@@ -1448,16 +1463,9 @@ extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0,
 // of - or, with d_obs, next to - the float64 one: an eighth of the bytes a learner has to read back
 extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, uint8_t *d_codes, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (T < 1 || !d_codes) return fail(h, "cz_rollout_compact: T must be >= 1 and the codes pointer non-null");
-    if ((uint64_t)T * (uint64_t)h->P.N * (uint64_t)h->P.A * 8ull > 0xFFFFFFFFull)
-        return fail(h, "cz_rollout_compact: T * num_envs * num_agents * 8 must stay below 4 GiB (T <= %llu here): split the rollout",
-                    (unsigned long long)(0xFFFFFFFFull / ((uint64_t)h->P.N * h->P.A * 8ull)));
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
-    Params P = h->P;
-    P.actions = nullptr; P.obs = d_obs; P.codes = d_codes; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc;
-    P.T = T; P.seed = seed; P.step0 = step0;
+    if (begin_device_call(h, T >= 1 && d_codes, "cz_rollout_compact: T must be >= 1 and the codes pointer non-null", "cz_rollout_compact", T)) return 1;
+    Params P = call_params(h, nullptr, d_obs, d_rewards, d_term, d_trunc);
+    P.codes = d_codes; P.T = T; P.seed = seed; P.step0 = step0;
     return launch_step(h, P, nullptr, true);
 }
 
@@ -1466,17 +1474,9 @@ extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_
 // trajectory buffers, and nothing has to be ordered between launches .
 extern "C" int cz_rollout_actions(cz_handle h, int32_t T, const int32_t *d_actions, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
-    if (ready(h)) return 1;
-    if (T < 1 || !d_actions) return fail(h, "cz_rollout_actions: T must be >= 1 and the actions pointer non-null");
-    // (the kernel addresses rewards / flags / actions with 32-bit offsets from the array base)
-    if ((uint64_t)T * (uint64_t)h->P.N * (uint64_t)h->P.A * 8ull > 0xFFFFFFFFull)
-        return fail(h, "cz_rollout_actions: T * num_envs * num_agents * 8 must stay below 4 GiB (T <= %llu here): split the rollout",
-                    (unsigned long long)(0xFFFFFFFFull / ((uint64_t)h->P.N * h->P.A * 8ull)));
-    if (set_device(h)) return 1;
-    if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;      // a staged layout update whose time may have come
-    Params P = h->P;
-    P.actions = d_actions; P.obs = d_obs; P.codes = nullptr; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc;
-    P.T = T; P.seed = 0; P.step0 = 0;
+    if (begin_device_call(h, T >= 1 && d_actions, "cz_rollout_actions: T must be >= 1 and the actions pointer non-null", "cz_rollout_actions", T)) return 1;
+    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
+    P.codes = nullptr; P.T = T; P.seed = 0; P.step0 = 0;
     return launch_step(h, P, nullptr, true);
 }
 
@@ -1489,6 +1489,15 @@ static void *mapped_device_pointer(const void *host) {
         return nullptr;
     }
     return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
+}
+
+// cz_step_device with the recipe marks of every env written to d_marks as well: armed for this one launch, whatever becomes of it
+static int step_device_with_marks(cz_handle h, uint32_t *d_marks, const int32_t *d_actions, double *d_obs, double *d_rewards,
+                                  uint8_t *d_term, uint8_t *d_trunc) {
+    h->marks_out_next = d_marks;
+    const int rc = cz_step_device(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
+    h->marks_out_next = nullptr;
+    return rc;
 }
 
 extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double *rewards, uint8_t *term, uint8_t *trunc) {
@@ -1515,12 +1524,10 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
             HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_stage, h->h_stage, 0));
         }
         memcpy(h->h_stage + o_act, actions, NA * 4);
-        h->marks_out_next = (uint32_t *)(h->d_stage + o_marks);
-        if (cz_step_device(h, (const int32_t *)(h->d_stage + o_act), obs ? (double *)(h->d_stage + o_obs) : nullptr,
-                           (double *)(h->d_stage + o_rew), (uint8_t *)(h->d_stage + o_term), (uint8_t *)(h->d_stage + o_trunc))) {
-            h->marks_out_next = nullptr;
+        if (step_device_with_marks(h, (uint32_t *)(h->d_stage + o_marks), (const int32_t *)(h->d_stage + o_act),
+                                   obs ? (double *)(h->d_stage + o_obs) : nullptr, (double *)(h->d_stage + o_rew),
+                                   (uint8_t *)(h->d_stage + o_term), (uint8_t *)(h->d_stage + o_trunc)))
             return 1;
-        }
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (obs) memcpy(obs, h->h_stage + o_obs, ob);
         memcpy(rewards, h->h_stage + o_rew, NA * 8);
@@ -1540,11 +1547,9 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
                 HIPCHK(h, hipHostMalloc((void **)&h->h_marks, (size_t)h->P.N * 8, hipHostMallocMapped));
                 HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_marks_mapped, h->h_marks, 0));
             }
-            h->marks_out_next = h->d_marks_mapped;
-            if (cz_step_device(h, (const int32_t *)d_act, (double *)d_obs, (double *)d_rew, (uint8_t *)d_term, (uint8_t *)d_trunc)) {
-                h->marks_out_next = nullptr;
+            if (step_device_with_marks(h, h->d_marks_mapped, (const int32_t *)d_act, (double *)d_obs, (double *)d_rew, (uint8_t *)d_term,
+                                       (uint8_t *)d_trunc))
                 return 1;
-            }
             HIPCHK(h, hipStreamSynchronize(h->stream));
             h->last_marks.assign(h->h_marks, h->h_marks + 2 * (size_t)h->P.N);
             return 0;
@@ -1561,12 +1566,9 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
     }
     if (obs && !h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, ob));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, NA * 4, hipMemcpyHostToDevice, h->stream));
-    h->marks_out_next = (uint32_t *)(h->d_small + s_marks);
-    if (cz_step_device(h, h->d_actions, obs ? h->d_obs : nullptr, (double *)(h->d_small + s_rew), (uint8_t *)(h->d_small + s_term),
-                       (uint8_t *)(h->d_small + s_trunc))) {
-        h->marks_out_next = nullptr;
+    if (step_device_with_marks(h, (uint32_t *)(h->d_small + s_marks), h->d_actions, obs ? h->d_obs : nullptr, (double *)(h->d_small + s_rew),
+                               (uint8_t *)(h->d_small + s_term), (uint8_t *)(h->d_small + s_trunc)))
         return 1;
-    }
     HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, s_total, hipMemcpyDeviceToHost, h->stream));
     if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->d_obs, ob, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1625,18 +1627,10 @@ extern "C" int cz_probe_output_only(cz_handle h, void *d_dst, size_t bytes, int3
     return 0;
 }
 
-// Measurement aid for bench.py: a CLOSED loop of K steps - cz_step_device, then a policy kernel that derives every agent's
-// next action from the observation it has just been given, on the same stream - captured into one HIP graph and replayed
-// `reps` times; returns the average time per step (step + policy).  d_actions (int32 [N][A]) is read and rewritten in place.
-extern "C" int cz_probe_closed_loop(cz_handle h, int32_t K, int32_t reps, int32_t *d_actions, double *d_obs, double *d_rewards,
-                                    uint8_t *d_term, uint8_t *d_trunc, float *us_per_step) {
-    if (ready(h)) return 1;
-    if (K < 1 || K > 1024 || reps < 1 || !d_actions || !d_obs || !us_per_step) return fail(h, "cz_probe_closed_loop: bad arguments");
-    if (set_device(h)) return 1;
-    Params P = h->P;
-    P.actions = d_actions; P.obs = d_obs; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
-    const int rows = h->P.N * h->P.A;
-    const uint32_t n_actions = h->P.scheme == 3 ? 5u : 8u;
+// the closed loop of the two probes below: K x [one step, the policy's launch] captured into one HIP graph, which is replayed `reps` times
+// behind a warm-up replay; the average time per step (step + policy)
+template <class Policy>
+static int probe_closed_loop(cz_handle h, Params &P, int32_t K, int32_t reps, float *us_per_step, Policy &&policy) {
     const bool was_timing = h->ktime;
     h->ktime = false;
     hipGraph_t g = nullptr;
@@ -1645,7 +1639,7 @@ extern "C" int cz_probe_closed_loop(cz_handle h, int32_t K, int32_t reps, int32_
     int bad = 0;
     for (int k = 0; k < K && !bad; ++k) {
         bad = launch_step(h, P);
-        if (!bad && !getenv("CZ_PROBE_NO_POLICY")) hipLaunchKernelGGL(k_probe_policy, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_obs, d_actions, rows, h->P.F, n_actions);
+        if (!bad && !getenv("CZ_PROBE_NO_POLICY")) policy();
     }
     const hipError_t ec = hipStreamEndCapture(h->stream, &g);
     h->ktime = was_timing;
@@ -1665,6 +1659,22 @@ extern "C" int cz_probe_closed_loop(cz_handle h, int32_t K, int32_t reps, int32_
     HIPCHK(h, rc);
     *us_per_step = ms * 1e3f / (float)((int64_t)reps * K);
     return 0;
+}
+
+// Measurement aid for bench.py: a CLOSED loop of K steps - cz_step_device, then a policy kernel that derives every agent's
+// next action from the observation it has just been given, on the same stream - captured into one HIP graph and replayed
+// `reps` times; returns the average time per step (step + policy).  d_actions (int32 [N][A]) is read and rewritten in place.
+extern "C" int cz_probe_closed_loop(cz_handle h, int32_t K, int32_t reps, int32_t *d_actions, double *d_obs, double *d_rewards,
+                                    uint8_t *d_term, uint8_t *d_trunc, float *us_per_step) {
+    if (ready(h)) return 1;
+    if (K < 1 || K > 1024 || reps < 1 || !d_actions || !d_obs || !us_per_step) return fail(h, "cz_probe_closed_loop: bad arguments");
+    if (set_device(h)) return 1;
+    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
+    const int rows = h->P.N * h->P.A;
+    const uint32_t n_actions = h->P.scheme == 3 ? 5u : 8u;
+    return probe_closed_loop(h, P, K, reps, us_per_step, [&] {
+        hipLaunchKernelGGL(k_probe_policy, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_obs, d_actions, rows, h->P.F, n_actions);
+    });
 }
 
 // Test / measurement aid: ONE launch of that stand-in policy on the handle's stream - d_actions[env][agent] = hash of four features of
@@ -1690,39 +1700,14 @@ extern "C" int cz_probe_closed_loop_compact(cz_handle h, int32_t K, int32_t reps
     if (ready(h)) return 1;
     if (K < 1 || K > 1024 || reps < 1 || !d_actions || !d_codes || !us_per_step) return fail(h, "cz_probe_closed_loop_compact: bad arguments");
     if (set_device(h)) return 1;
-    Params P = h->P;
-    P.actions = d_actions; P.obs = nullptr; P.codes = d_codes; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
+    Params P = call_params(h, d_actions, nullptr, d_rewards, d_term, d_trunc);
+    P.codes = d_codes;
     const int rows = h->P.N * h->P.A;
     const uint32_t n_actions = h->P.scheme == 3 ? 5u : 8u;
-    const bool was_timing = h->ktime;
-    h->ktime = false;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int bad = 0;
-    for (int k = 0; k < K && !bad; ++k) {
-        bad = launch_step(h, P);
-        if (!bad && !getenv("CZ_PROBE_NO_POLICY")) hipLaunchKernelGGL(k_probe_policy_codes, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_codes, h->d_lut, d_actions, rows,
-                                     h->P.F, codes_pitch(h->P.F), n_actions);
-    }
-    const hipError_t ec = hipStreamEndCapture(h->stream, &g);
-    h->ktime = was_timing;
-    if (bad) { if (g) (void)hipGraphDestroy(g); return 1; }
-    HIPCHK(h, ec);
-    const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    HIPCHK(h, ei);
-    hipError_t rc = hipGraphLaunch(ge, h->stream);                         // warm
-    if (rc == hipSuccess) rc = hipEventRecord(h->ev0, h->stream);
-    for (int r = 0; r < reps && rc == hipSuccess; ++r) rc = hipGraphLaunch(ge, h->stream);
-    if (rc == hipSuccess) rc = hipEventRecord(h->ev1, h->stream);
-    if (rc == hipSuccess) rc = hipEventSynchronize(h->ev1);
-    float ms = 0.f;
-    if (rc == hipSuccess) rc = hipEventElapsedTime(&ms, h->ev0, h->ev1);
-    (void)hipGraphExecDestroy(ge);
-    HIPCHK(h, rc);
-    *us_per_step = ms * 1e3f / (float)((int64_t)reps * K);
-    return 0;
+    return probe_closed_loop(h, P, K, reps, us_per_step, [&] {
+        hipLaunchKernelGGL(k_probe_policy_codes, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_codes, h->d_lut, d_actions, rows,
+                           h->P.F, codes_pitch(h->P.F), n_actions);
+    });
 }
 
 // ---- device memory + timing helpers --------------------------------------------------------------------

@@ -3,5 +3,5 @@
 // (the compiler spills a few hundred SGPRs), so a step costs several times the 7x7 one -- capacity, not speed.
 #include "cz_kernels.h"
 namespace cz {
-Launchers launchers_huge() { return Launchers{&Inst<4, 16>::step, &Inst<4, 16>::reset, &Inst<4, 16>::observe, nullptr}; }
+Launchers launchers_huge() { return Inst<4, 16>::launchers(); }
 }

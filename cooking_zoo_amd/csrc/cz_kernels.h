@@ -1,6 +1,7 @@
 // cz_kernels.h -- kernel templates of the step path (included by the per-size instantiation units).
 #pragma once
 #include "cz_device.h"
+#include <type_traits>
 
 namespace cz {
 
@@ -30,7 +31,7 @@ namespace cz {
 // optimiser cannot see through -- otherwise every one of them is fetched at kernel entry and held in SGPRs for the whole
 // kernel (~30 SGPRs: spills in the non-fused kernel, ~90 spilled SGPRs in the fused one).
 typedef const __attribute__((address_space(4))) Params *KParams;
-struct StepArgsMirror { uint32_t *a; const int32_t *b; const double *c; int32_t i[8]; Params p; };   // (k_step: 7 ints + padding)   // k_step's argument list
+struct StepArgsMirror { uint32_t *a; const int32_t *b; const double *c; int32_t i[8]; Params p; };   // k_step's argument list (7 ints + one of padding)
 __device__ __forceinline__ KParams late_params(unsigned offset) {
     const __attribute__((address_space(4))) char *k =
         (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -38,6 +39,40 @@ __device__ __forceinline__ KParams late_params(unsigned offset) {
     return reinterpret_cast<KParams>(k + offset);
 }
 #define CZ_LATE_STEP() late_params((unsigned)offsetof(StepArgsMirror, p))
+
+// The variants of the step kernel: cz::k_step<OPL, CPL, NA, SCHEME, mode> and, for STEP only, cz::k_step_lean<OPL, CPL, NA, SCHEME>.
+// (choose_step in cz_api.hip says which launch gets which; DESIGN.md section 4 has the same table.)
+enum StepMode : int {
+    STEP = 0,                 // one step, actions from memory
+    ROLLOUT = 1,              // P.T steps, on-device action stream, outputs [t][env] (cz_rollout)
+    ROLLOUT_ACTIONS = 2,      // P.T steps over the caller's actions [t][env][agent] (cz_rollout_actions, fused rings; its own instance so that the
+                              // on-device stream's loop carries none of it: as a run-time branch it cost the random-action rollout 4 %)
+    STEP_CODES = 3,           // one step that also (or only) writes the compact observation (cz_step_device_compact / cz_set_compact_output;
+                              // its own instance as well: compiled into the ordinary one-step kernel the path cost every launch 0.2 us, register
+                              // allocation and a longer prologue, even when unused)
+    ROLLOUT_CODES = 4,        // P.T steps over the on-device action stream with a compact trajectory [t][env][agent][pitch] (cz_rollout_compact)
+    ROLLOUT_CODES_ONLY = 5,   // the same without a float64 trajectory beside it
+};
+template <int MODE, bool LEAN = false>
+struct StepTraits {
+    static_assert(MODE >= STEP && MODE <= ROLLOUT_CODES_ONLY && (!LEAN || MODE == STEP), "no such variant");
+    static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // P.T steps per launch
+    static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS;                         // a fused launch that reads the caller's actions
+    static constexpr bool codes = MODE == STEP_CODES || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // writes the compact observation
+    // a fused rollout that writes codes ONLY (cz_rollout_compact without a float64 trajectory).  Without the float64 path - its six
+    // descriptor registers, its encode - the codes' own descriptor words fit the registers for the whole launch (ROLLOUT_CODES reloads
+    // them every step: held there they cost 136 vector registers, three waves per SIMD)
+    static constexpr bool codes_only = MODE == ROLLOUT_CODES_ONLY;
+    static constexpr bool f64 = !codes_only;                                             // carries the float64 observation path
+    // k_step_lean: the one-step kernel with the handle's uniform settings fixed at compile time - narrow recipe tables, no despawn /
+    // respawn, float64 observations of at most 128 * OBS_PAIRS features with write-through stores, no compact output and no marks
+    // buffer (choose_step in cz_api.hip picks it when all of that holds).  The code is the one-step kernel with those tests folded
+    // away: same results, fewer scalar instructions and registers per wave.
+    static constexpr bool lean = LEAN;
+};
+// (The pieces below the kernel - load_env, all_marks, observe, step_env - are templates over the one or two properties they ask
+// for, fed from the traits by step_kernel: k_reset / k_observe and several variants then share one instance of each, as they always
+// have, and the optimiser's view of a piece - hence the shipped instruction streams - depends on who shares it.)
 
 // LDS image of one env (halfwords, cooking_zoo_amd/soa.py IMG_*): every halfword is a BYTE offset into `lut`
 // Two layouts: up to 128 slots / 256 cells (CPL <= 4), and the "huge" one for up to 256 slots / 1024 cells (CPL = 16).
@@ -261,8 +296,8 @@ typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {                       // v_pk_sub_u16: two 16-bit lanes, no borrow across
     return __builtin_bit_cast(uint32_t, (ushort2_t)(__builtin_bit_cast(ushort2_t, a) - __builtin_bit_cast(ushort2_t, b)));
 }
-// LEAN (k_step_lean, see step_kernel): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
-// time - one chunk, no store-flavour switch, no descriptor reload.
+// LEAN (k_step_lean, see StepTraits): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
+// time - one chunk, no store-flavour switch, no descriptor reload.  F64 = false: the codes-only variant, which carries no float64 path.
 template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false>
 __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
                                         const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
@@ -360,11 +395,11 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
             }
         }
     }
-    if (!F64 || (!LEAN && !out)) { __builtin_amdgcn_wave_barrier(); return; }      // (F64 = false: the codes-only instance carries no float64 path)
+    if (!F64 || (!LEAN && !out)) { __builtin_amdgcn_wave_barrier(); return; }
     decltype(__builtin_amdgcn_make_buffer_rsrc(out, 0, 0, 0)) rs[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) rs[a] = __builtin_amdgcn_make_buffer_rsrc(out + (size_t)a * (uint32_t)P.F, 0, P.F * 8, 0x00020000);
-    const uint32_t wt = LEAN ? 1u : (uint32_t)P.wt;                                     // wave-uniform
+    const uint32_t wt = LEAN ? 1u : (uint32_t)P.wt;                                  // wave-uniform
     for (int chunk = 0; LEAN ? chunk == 0 : chunk * 128 * OBS_PAIRS < P.F; ++chunk) {
         if (chunk > 0) load_desc(P, e.layout, chunk, cx.lane, dsc);
         // branch-free stages so that the LDS reads of all pairs and observers are in flight together
@@ -412,10 +447,10 @@ struct StepOut {
 };
 
 // One accumulated_step (cooking_env.py:243-269) of one env held in registers.
-// HINT (the fused instances): the reset pass and the end of an episode are laid out off the fall-through path - one step in max_steps + 1
+// FUSED (CZ_RARE): the reset pass and the end of an episode are laid out off the fall-through path - one step in max_steps + 1
 // takes them; in the one-step kernels the same hint cost the launches under a cooking policy 1.5 % (profiles/r05/ab_experiments.txt)
 #define CZ_RARE(hint, x) ((hint) ? __builtin_expect(!!(x), 0) : !!(x))
-template <int OPL, int CPL, int NA, int SCHEME, bool HINT = false, bool LEAN = false>
+template <int OPL, int CPL, int NA, int SCHEME, bool FUSED, bool LEAN>
 __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t acts,
                                          int64_t env_global, uint32_t &rowv, Lds<CPL> &lds, uint32_t (&dsc)[OBS_CHUNK], Dirty &dt, StepOut &o) {
     using O = Ops<OPL, CPL, NA, SCHEME>;
@@ -427,7 +462,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
     // P.auto_reset: bit 0 = next-step auto-reset, bit 1 = agent despawn / respawn is on (cz_set_spawn)
     const bool spawning = !LEAN && (P.auto_reset & 2) != 0;
     const SpawnCfg *const spawn_cfg = reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET);
-    if (CZ_RARE(HINT, (e.status & ST_DONE) != 0u)) {
+    if (CZ_RARE(FUSED, (e.status & ST_DONE) != 0u)) {
         o.header = true;
         if (P.auto_reset & 1) {
             // next-step autoreset: reset() of cooking_env.py:178-210 from the layout pool
@@ -530,6 +565,8 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
             constexpr uint64_t NODE_LANES = 0x1FEull | (0x1FEull << 9) | (0x1FEull << 18) | (0x1FEull << 27);
             const bool rel = (nw & 0x2000u) != 0u && seen != 0u, sens = kids != 0u && (mb & kids) == kids;
             // the rewards of recipe r whose marks went from mb_r to ma (cooking_env.py:255-261, recipe.py:36-40)
+            // (the wide path above carries its own copy of this: folded into one function, both forms tried, the compiler commutes
+            // operands of two scalar instructions in every k_step - and the shipped streams are kept instruction for instruction)
             const auto reward_of = [&](int r, uint32_t mb_r, uint32_t ma) {
                 // goals_completed sums (recipe.py:36-40): open goal slots before / after
                 const uint32_t countmask = (uint32_t)((ballot((nw & 0x100u) != 0u) >> (9 * r + 1)) & 0xFFull);
@@ -597,21 +634,14 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
     }
     o.term = done ? 1u : 0u;
     o.trunc = truncated ? 1u : 0u;
-    if (CZ_RARE(HINT, done || truncated)) {
+    if (CZ_RARE(FUSED, done || truncated)) {
         e.status |= ST_DONE | (done ? ST_TERM : 0u) | (truncated ? ST_TRUNC : 0u);
         o.finished = true;
         o.header = true;
     }
 }
 
-// ENVS_PER_WG envs per workgroup (one wavefront each, no cross-wave communication).
-// FUSED = 0: one step, actions from memory.  FUSED = 1: P.T steps, on-device action stream, outputs [t][env].  FUSED = 2: P.T
-// steps over the caller's actions [t][env][agent] (cz_rollout_actions; its own instance so that the on-device stream's loop
-// carries none of it: as a run-time branch it cost the random-action rollout 4 %).  FUSED = 3: one step that also (or only)
-// writes the compact observation (cz_step_device_compact / cz_set_compact_output; its own instance as well: compiled into the
-// ordinary one-step kernel the path cost every launch 0.2 us, register allocation and a longer prologue, even when unused).
-// FUSED = 4: P.T steps over the on-device action stream with a compact trajectory [t][env][agent][pitch] (cz_rollout_compact);
-// FUSED = 5: the same without a float64 trajectory beside it (codes only).
+// ENVS_PER_WG envs per workgroup (one wavefront each, no cross-wave communication); V: the variant (StepTraits).
 // What the very first loads of a wave need travels as leading scalar kernel arguments: the build preloads them into
 // SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count, gfx940+), so the record / action / table loads are issued
 // without waiting for an argument fetch; everything else stays in the by-value block `P0`, fetched meanwhile.
@@ -625,11 +655,7 @@ __host__ __device__ inline Early early_of(const Params &P) {
     return Early{P.state, P.actions, P.lut, P.N, P.RW, P.W, P.H, P.D, P.dyn0_off, P.dyn1_off};
 }
 
-// LEAN (FUSED_MODE 0 only; k_step_lean): the one-step kernel with the handle's uniform settings fixed at compile time - narrow
-// recipe tables, no despawn / respawn, float64 observations of at most 128 * OBS_PAIRS features with write-through stores, no
-// compact output and no marks buffer (launch_step in cz_api.hip picks it when all of that holds).  The code is today's one-step
-// kernel with those tests folded away: same results, fewer scalar instructions and registers per wave.
-template <int OPL, int CPL, int NA, int SCHEME, int FUSED_MODE, bool LEAN = false>
+template <int OPL, int CPL, int NA, int SCHEME, class V>
 __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                             int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
                                             int32_t e_dyn1, const Params &P0) {
@@ -669,28 +695,22 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     CZ_STAMP(0);
     uint32_t *rec = P.state + (uint32_t)env * (uint32_t)P.RW;        // (cz_create: the records of a handle stay below 4 GiB)
     double *retp = reinterpret_cast<double *>(rec + RET_WORD0);
-    constexpr bool FUSED = FUSED_MODE == 1 || FUSED_MODE == 2 || FUSED_MODE == 4 || FUSED_MODE == 5, EXT = FUSED_MODE == 2;
-    constexpr bool CODES = FUSED_MODE == 3 || FUSED_MODE == 4 || FUSED_MODE == 5;
-    // mode 5: a fused rollout that writes codes ONLY (cz_rollout_compact without a float64 trajectory).  Without the float64 path -
-    // its six descriptor registers, its encode - the codes' own descriptor words fit the registers for the whole launch (mode 4 reloads
-    // them every step: held there they cost 136 vector registers, three waves per SIMD)
-    constexpr bool CODES_ONLY = FUSED_MODE == 5;
     int av = 0;
 #ifdef CZ_TIMELINE
     const uint64_t tl_seen = wall_clock64();
 #endif
     // ---- every load of the step is issued here, before anything waits
-    if (!FUSED) av = ldg<int>(P.actions, ((uint32_t)env * (uint32_t)NA + (uint32_t)min(lane, NA - 1)) * 4u);
+    if (!V::fused) av = ldg<int>(P.actions, ((uint32_t)env * (uint32_t)NA + (uint32_t)min(lane, NA - 1)) * 4u);
     double ret = ldg<double>(retp, ((uint32_t)lane & 3u) * 8u);                                       // running episode return, lane a = agent a
     Env<OPL, CPL, NA> e;
-    load_env<OPL, CPL, NA, LEAN>(P, e, cx, rec);
+    load_env<OPL, CPL, NA, V::lean>(P, e, cx, rec);
     init_lds<CPL>(P, cx, lds);
     uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
     uint32_t dsc[OBS_CHUNK];
-    if (!CODES_ONLY && (LEAN || P.obs)) load_desc(P, e.layout, 0, lane, dsc);
+    if (V::f64 && (V::lean || P.obs)) load_desc(P, e.layout, 0, lane, dsc);
     if (!SUBMASK_EARLY) submask = load_submask(P, lane);
     const int64_t env_global = P.env_id_base + env;
-    bool cells_dirty = false, objs_dirty = false, header_dirty = FUSED;
+    bool cells_dirty = false, objs_dirty = false, header_dirty = V::fused;
     bool img_objs = true, img_cells = true;                 // which parts of the LDS image the next encode must rebuild
     if (threadIdx.x < (unsigned)LUT_SIZE) lut[threadIdx.x] = lutv;
     __syncthreads();
@@ -700,25 +720,27 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     // on a late argument in front of the prologue's loads costs every launch 0.4 us - and hidden by the dynamics
     CodesPrefetch cpre;
     cpre.layout = e.layout;
-    if (CODES && (!FUSED || CODES_ONLY)) {
+    // (this fetch is spelled out at its three sites: behind a shared function - tried with and without the layout word - the code
+    // variants come out with a few instructions more or fewer, and the shipped streams are kept instruction for instruction)
+    if (V::codes && (!V::fused || V::codes_only)) {
 #pragma unroll
         for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(P, e.layout, 256u * r + 4u * (uint32_t)lane);
     }
 
-    const int T = FUSED ? P.T : 1;
+    const int T = V::fused ? P.T : 1;
 #ifdef CZ_TIMELINE
     uint32_t tl_dbg = 0u;
 #endif
     // a fused rollout over caller-supplied actions (cz_rollout_actions: [T][N][A] int32): step t's action words are loaded one
     // step ahead, so the round trip hides behind the previous step's work
     const uint32_t act_lane = ((uint32_t)env * (uint32_t)NA + (uint32_t)min(lane, NA - 1)) * 4u;
-    if (EXT) av = ldg<int>(e_actions, act_lane);
+    if (V::ext_actions) av = ldg<int>(e_actions, act_lane);
 #pragma nounroll
     for (int t = 0; t < T; ++t) {
         // The fused kernel re-reads its argument block every step (scalar loads that hit the constant cache): nothing of
         // it then stays live across the loop's back edge, which is what used to spill ~90 SGPRs.
         Params Pt;
-        if (FUSED) {
+        if (V::fused) {
             static_assert(sizeof(Params) % 8 == 0, "copied as 64-bit words");
             typedef uint64_t __attribute__((may_alias)) word_t;
             const __attribute__((address_space(4))) word_t *src = (const __attribute__((address_space(4))) word_t *)CZ_LATE_STEP();
@@ -730,7 +752,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         } else {
             Pt = P;
         }
-        if (CODES && FUSED && !CODES_ONLY) {
+        if (V::codes && V::fused && !V::codes_only) {
             // (a fused rollout fetches the code descriptors again at the top of every step - hidden by the step's dynamics - instead
             // of holding eight more registers across the loop: with them the kernel no longer fits four waves per SIMD)
             cpre.layout = e.layout;
@@ -738,15 +760,15 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(Pt, e.layout, 256u * r + 4u * (uint32_t)lane);
         }
         uint32_t acts;                                             // lane a = action of agent a
-        if (!FUSED) acts = (uint32_t)av;
-        else if (EXT) {
+        if (!V::fused) acts = (uint32_t)av;
+        else if (V::ext_actions) {
             acts = (uint32_t)av;
             // (cz_rollout_actions checks that T * N * A * 4 fits 32 bits; the last step re-reads its own row)
             av = ldg<int>(e_actions, act_lane + (uint32_t)min(t + 1, T - 1) * ((uint32_t)Pt.N * (uint32_t)NA * 4u));
         } else acts = action_hash(Pt.seed, env_global, lane & 3, Pt.step0 + (uint32_t)t, SCHEME == 3 ? 5u : 8u);
         Dirty dt{};
         StepOut o;
-        step_env<OPL, CPL, NA, SCHEME, FUSED, LEAN>(Pt, (unsigned)offsetof(StepArgsMirror, p), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
+        step_env<OPL, CPL, NA, SCHEME, V::fused, V::lean>(Pt, (unsigned)offsetof(StepArgsMirror, p), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
 #ifdef CZ_TIMELINE
         tl_dbg |= o.dbg;
 #endif
@@ -763,7 +785,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         // trip (~1 us after a launch boundary) used to make exactly these waves the last ones of a launch in which nobody acts.
         uint32_t su_old = 0u;
         double sf_old = 0.0, ret_done = 0.0;
-        if (CZ_RARE(FUSED, o.finished)) {
+        if (CZ_RARE(V::fused, o.finished)) {
             const uint32_t *su = kp->stat_u + (size_t)env * SU_WORDS;
             const double *sf = kp->stat_f + (size_t)env * SF_WORDS;
             su_old = ldg<uint32_t>(su, ((uint32_t)lane & 15u) * 4u);
@@ -774,14 +796,14 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         // ---- outputs of this step.  One wave-uniform base pointer per array and a 32-bit per-lane offset (cz_rollout checks
         // that T * N * A * 8 fits): the `global_store v, v_off, s[base]` form, no 64-bit per-lane address arithmetic.  The
         // one-step kernels store unconditionally - the host hands them a scratch row for an array the caller does not want.
-        // (mode 2 with P.step0 & 1 - cz_set_ring_fused: the steps of an action ring fused into one launch - writes every step's
+        // (ROLLOUT_ACTIONS with P.step0 & 1 - cz_set_ring_fused: the steps of an action ring fused into one launch - writes every step's
         // outputs to row `env`, like the one-step launches it stands in for; a wave's stores to one address keep their order)
-        const bool in_place = EXT && (Pt.step0 & 1u) != 0u;
-        const size_t row = FUSED ? ((size_t)(in_place ? 0 : t) * Pt.N + env) : (size_t)env;
+        const bool in_place = V::ext_actions && (Pt.step0 & 1u) != 0u;
+        const size_t row = V::fused ? ((size_t)(in_place ? 0 : t) * Pt.N + env) : (size_t)env;
         // (the compact path's descriptor words were fetched long ago; waiting for them HERE costs nothing, while behind the
         // stores below the same wait would also stand for those stores' acknowledgement - one counter for loads and stores)
-        if (CODES) {
-            if (CZ_RARE(FUSED, cpre.layout != e.layout)) {                 // a reset pass has moved the env to another layout
+        if (V::codes) {
+            if (CZ_RARE(V::fused, cpre.layout != e.layout)) {                 // a reset pass has moved the env to another layout
                 cpre.layout = e.layout;
 #pragma unroll
                 for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(Pt, e.layout, 256u * r + 4u * (uint32_t)lane);
@@ -794,9 +816,9 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             double *const rewards = kp->rewards;
             uint8_t *const term = kp->term, *const trunc = kp->trunc;
             if (lane < NA) {
-                if (!FUSED || rewards) stg<double>(rewards, oidx * 8u, myrew);
-                if (!FUSED || term) stg<uint8_t>(term, oidx, (uint8_t)o.term);
-                if (!FUSED || trunc) {
+                if (!V::fused || rewards) stg<double>(rewards, oidx * 8u, myrew);
+                if (!V::fused || term) stg<uint8_t>(term, oidx, (uint8_t)o.term);
+                if (!V::fused || trunc) {
                     stg<uint8_t>(trunc, oidx, (uint8_t)o.trunc);
                     // whoever was despawned in this step is reported truncated once (cooking_env.py:344-349): a second store by
                     // those lanes, on the rare steps on which somebody leaves
@@ -804,25 +826,25 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
                 }
             }
         }
-        if (!FUSED && !LEAN) {
+        if (!V::fused && !V::lean) {
             uint32_t *const marks_out = kp->marks_out;
             if (marks_out && lane < 2) stg<uint32_t>(marks_out, (2u * (uint32_t)env + (uint32_t)lane) * 4u, lane == 0 ? e.marks : e.marks_hi);   // infos["recipe_done"] of the host API
         }
         CZ_STAMP(5);
         img_objs |= (dt.touched | dt.moved) != 0;
         img_cells |= dt.cells != 0;
-        if (LEAN || Pt.obs || CODES) {
+        if (V::lean || Pt.obs || V::codes) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
-            uint8_t *const codes = CODES ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
-            double *const obs_row = !CODES_ONLY && Pt.obs ? Pt.obs + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F) : nullptr;
-            observe<OPL, CPL, NA, !CODES_ONLY, LEAN>(Pt, e, cx, lds, lut, dsc, submask, obs_row, img_objs, img_cells, codes, CODES ? &cpre : nullptr);
+            uint8_t *const codes = V::codes ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
+            double *const obs_row = V::f64 && Pt.obs ? Pt.obs + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F) : nullptr;
+            observe<OPL, CPL, NA, V::f64, V::lean>(Pt, e, cx, lds, lut, dsc, submask, obs_row, img_objs, img_cells, codes, V::codes ? &cpre : nullptr);
             img_objs = false; img_cells = false;
         }
-        if (CZ_RARE(FUSED, o.finished)) {      // (the state is still that of the finished episode: the reset is the next pass)
+        if (CZ_RARE(V::fused, o.finished)) {      // (the state is still that of the finished episode: the reset is the next pass)
             uint32_t *su = kp->stat_u + (size_t)env * SU_WORDS;
             double *sf = kp->stat_f + (size_t)env * SF_WORDS;
             const uint32_t a_of = (uint32_t)lane - SU_COMPLETED0;               // lane SU_COMPLETED0 + a: recipe a completed?
-            const uint32_t root = !LEAN && Pt.wide ? (((a_of < 2u ? e.marks : e.marks_hi) >> (16u * (a_of & 1u))) & 1u) : ((e.marks >> (8u * (a_of & 3u))) & 1u);
+            const uint32_t root = !V::lean && Pt.wide ? (((a_of < 2u ? e.marks : e.marks_hi) >> (16u * (a_of & 1u))) & 1u) : ((e.marks >> (8u * (a_of & 3u))) & 1u);
             const uint32_t inc = lane == (int)SU_EPISODES ? 1u : lane == (int)SU_LENSUM ? e.t : lane == (int)SU_TRUNC ? (uint32_t)o.trunc
                                  : lane == (int)SU_TERM ? (uint32_t)o.term : a_of < (uint32_t)NA ? root : 0u;
             if (lane < (int)SU_COMPLETED0 + NA && lane != (int)SU_STEPS) stg<uint32_t>(su, (uint32_t)lane * 4u, su_old + inc);
@@ -855,22 +877,22 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
 // waves - and forcing that one to six (80 registers, 3 spilled) changed nothing: 195 against 197 M env-steps/s,
 // profiles/r03/wpe_ab.txt)
 #ifdef CZ_STEP_MIN_WPE
-#define CZ_STEP_ATTR __attribute__((amdgpu_waves_per_eu(((FUSED == 0 || FUSED == 3) && OPL <= 2) ? CZ_STEP_MIN_WPE : 1)))
+#define CZ_STEP_ATTR __attribute__((amdgpu_waves_per_eu((!StepTraits<FUSED>::fused && OPL <= 2) ? CZ_STEP_MIN_WPE : 1)))
 #else
 #define CZ_STEP_ATTR
 #endif
-template <int OPL, int CPL, int NA, int SCHEME, int FUSED>
+template <int OPL, int CPL, int NA, int SCHEME, int FUSED /* a StepMode */>
 __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) CZ_STEP_ATTR void k_step(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                                           int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
                                                           int32_t e_dyn1, const Params P0) {
-    step_kernel<OPL, CPL, NA, SCHEME, FUSED>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
+    step_kernel<OPL, CPL, NA, SCHEME, StepTraits<FUSED>>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
 }
-// the lean one-step kernel (see step_kernel; small instance only: launchers_small)
+// the lean one-step kernel (see StepTraits; small instance only: launchers_small)
 template <int OPL, int CPL, int NA, int SCHEME>
 __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                                                        int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
                                                                        int32_t e_dyn1, const Params P0) {
-    step_kernel<OPL, CPL, NA, SCHEME, 0, true>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
+    step_kernel<OPL, CPL, NA, SCHEME, StepTraits<STEP, true>>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
 }
 // reset(): cooking_env.py:178-210 for envs [env_begin, env_begin + count)
 template <int OPL, int CPL, int NA>
@@ -924,96 +946,75 @@ __global__ __launch_bounds__(64) void k_observe(const Params P, int64_t env_begi
 }
 
 // launchers exported by each instantiation unit
-enum : int { LAUNCH_ONE = 0, LAUNCH_FUSED = 1 };
+struct StepChoice { StepMode mode; bool lean; };       // which variant a launch takes (choose_step, cz_api.hip)
 struct Launchers {
-    // mode: LAUNCH_ONE = one step; LAUNCH_FUSED = P.T steps per launch (actions: P.actions, or the on-device stream when null)
-    hipError_t (*step)(const Params &, hipStream_t, int mode);
+    // lean: k_step_lean (mode STEP, and only where has_lean); otherwise k_step<..., mode>.  Fused modes run P.T steps per launch
+    hipError_t (*step)(const Params &, hipStream_t, StepChoice);
     hipError_t (*reset)(const Params &, hipStream_t, int64_t, int, const int32_t *, const uint32_t *, const uint32_t *, double *);
     hipError_t (*observe)(const Params &, hipStream_t, int64_t, int, double *, uint8_t *);
-    // one step with k_step_lean (null: the instance has none).  Only for launches that satisfy every condition of the lean
-    // kernel (launch_step, cz_api.hip); same results as `step` with LAUNCH_ONE
-    hipError_t (*step_lean)(const Params &, hipStream_t);
+    bool has_lean;             // the instance carries the k_step_lean kernels
 };
 
-template <int OPL, int CPL>
+// the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
+template <class F>
+inline hipError_t with_agents(int A, F &&f) {
+    switch (A) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 4>{});
+    }
+}
+template <class F>
+inline hipError_t with_scheme(int scheme, F &&f) {
+    return scheme == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
+}
+// one launch of a step kernel: one wavefront per env, the leading scalar arguments spelled out for the preload (Early)
+template <int CPL, class K>
+inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) {
+    constexpr int EPW = envs_per_wg<CPL>();
+    const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
+    const Early E = early_of(P);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
+    return hipGetLastError();
+}
+
+template <int OPL, int CPL, bool HAS_LEAN = false>
 struct Inst {
-    template <int NA>
-    static hipError_t step_na(const Params &P, hipStream_t st, int mode) {
-        const bool fused = mode == LAUNCH_FUSED;
-        constexpr int EPW = envs_per_wg<CPL>();
-        const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
-        const Early E = early_of(P);
-#define CZ_LAUNCH_STEP(S, F) \
-    hipLaunchKernelGGL((k_step<OPL, CPL, NA, S, F>), grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P)
-        if (fused && P.actions) {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 2);
-            else CZ_LAUNCH_STEP(1, 2);
-        } else if (fused && P.codes && !P.obs) {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 5);
-            else CZ_LAUNCH_STEP(1, 5);
-        } else if (fused && P.codes) {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 4);
-            else CZ_LAUNCH_STEP(1, 4);
-        } else if (fused) {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 1);
-            else CZ_LAUNCH_STEP(1, 1);
-        } else if (!P.actions) {
-            return hipErrorInvalidValue;
-        } else if (P.codes) {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 3);
-            else CZ_LAUNCH_STEP(1, 3);
-        } else {
-            if (P.scheme == 3) CZ_LAUNCH_STEP(3, 0);
-            else CZ_LAUNCH_STEP(1, 0);
-        }
-#undef CZ_LAUNCH_STEP
-        return hipGetLastError();
-    }
-    template <int NA>
-    static hipError_t step_lean_na(const Params &P, hipStream_t st) {
-        constexpr int EPW = envs_per_wg<CPL>();
-        const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
-        const Early E = early_of(P);
-        if (!P.actions) return hipErrorInvalidValue;
-        if (P.scheme == 3) hipLaunchKernelGGL((k_step_lean<OPL, CPL, NA, 3>), grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
-        else hipLaunchKernelGGL((k_step_lean<OPL, CPL, NA, 1>), grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
-        return hipGetLastError();
-    }
-    static hipError_t step_lean(const Params &P, hipStream_t st) {
-        switch (P.A) {
-        case 1: return step_lean_na<1>(P, st);
-        case 2: return step_lean_na<2>(P, st);
-        case 3: return step_lean_na<3>(P, st);
-        default: return step_lean_na<4>(P, st);
-        }
-    }
-    static hipError_t step(const Params &P, hipStream_t st, int mode) {
-        switch (P.A) {
-        case 1: return step_na<1>(P, st, mode);
-        case 2: return step_na<2>(P, st, mode);
-        case 3: return step_na<3>(P, st, mode);
-        default: return step_na<4>(P, st, mode);
-        }
+    static hipError_t step(const Params &P, hipStream_t st, StepChoice c) {
+        return with_agents(P.A, [&](auto na) {
+            return with_scheme(P.scheme, [&](auto scheme) {
+                constexpr int NA = decltype(na)::value, S = decltype(scheme)::value;
+                if (c.lean) {
+                    if constexpr (HAS_LEAN) return launch_step_kernel<CPL>(k_step_lean<OPL, CPL, NA, S>, P, st);
+                    return hipErrorInvalidValue;
+                }
+                switch (c.mode) {
+                case STEP: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP>, P, st);
+                case ROLLOUT: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT>, P, st);
+                case ROLLOUT_ACTIONS: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_ACTIONS>, P, st);
+                case STEP_CODES: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_CODES>, P, st);
+                case ROLLOUT_CODES: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES>, P, st);
+                case ROLLOUT_CODES_ONLY: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES_ONLY>, P, st);
+                }
+                return hipErrorInvalidValue;
+            });
+        });
     }
     static hipError_t reset(const Params &P, hipStream_t st, int64_t b, int n, const int32_t *lay, const uint32_t *rec,
                             const uint32_t *pool, double *obs) {
-        switch (P.A) {
-        case 1: hipLaunchKernelGGL((k_reset<OPL, CPL, 1>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs); break;
-        case 2: hipLaunchKernelGGL((k_reset<OPL, CPL, 2>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs); break;
-        case 3: hipLaunchKernelGGL((k_reset<OPL, CPL, 3>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs); break;
-        default: hipLaunchKernelGGL((k_reset<OPL, CPL, 4>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs); break;
-        }
-        return hipGetLastError();
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_reset<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs);
+            return hipGetLastError();
+        });
     }
     static hipError_t observe(const Params &P, hipStream_t st, int64_t b, int n, double *obs, uint8_t *codes) {
-        switch (P.A) {
-        case 1: hipLaunchKernelGGL((k_observe<OPL, CPL, 1>), dim3(n), dim3(64), 0, st, P, b, obs, codes); break;
-        case 2: hipLaunchKernelGGL((k_observe<OPL, CPL, 2>), dim3(n), dim3(64), 0, st, P, b, obs, codes); break;
-        case 3: hipLaunchKernelGGL((k_observe<OPL, CPL, 3>), dim3(n), dim3(64), 0, st, P, b, obs, codes); break;
-        default: hipLaunchKernelGGL((k_observe<OPL, CPL, 4>), dim3(n), dim3(64), 0, st, P, b, obs, codes); break;
-        }
-        return hipGetLastError();
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_observe<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, obs, codes);
+            return hipGetLastError();
+        });
     }
+    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN}; }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

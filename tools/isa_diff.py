@@ -12,7 +12,8 @@ def kernels(path):
     txt = open(path).read()
     out = {}
     for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", txt, flags=re.S | re.M):
-        ins = [re.sub(r"\s*;.*$", "", l.strip()) for l in m.group(2).split("\n")
+        # (a branch target is .LBB<index of the function in its listing>_<block>: the index moves with the order of instantiation)
+        ins = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", l.strip())) for l in m.group(2).split("\n")
                if l.startswith("\t") and not l.strip().startswith((".", ";"))]
         out[m.group(1)] = ins
     return out
