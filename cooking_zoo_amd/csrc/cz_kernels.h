@@ -206,10 +206,15 @@ __device__ __forceinline__ void store_env(const Params &P, const Env<OPL, CPL, N
 
 // the recipe rows of this env, one word per lane: lane 9r + i = word i of the row of recipe r (which r, i a lane stands for is
 // a constant of the lane, made by the host: 8 r | 4 i << 8; lanes past the rows repeat the last word)
-__device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t recipes, int lane) {
-    const uint32_t sel = ldg<uint32_t>(P.lut, ROWSEL_TABLE_OFFSET + (uint32_t)lane * 4u);
+// (the selector does not depend on the record: step_kernel fetches it with its first loads, load_row_selector, and hands it over -
+// fetched here, behind the wait for the header's `recipes`, it is a second memory round trip in front of the row's load)
+__device__ __forceinline__ uint32_t load_row_selector(const Params &P, int lane) { return ldg<uint32_t>(P.lut, ROWSEL_TABLE_OFFSET + (uint32_t)lane * 4u); }
+__device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t recipes, uint32_t sel) {
     const uint32_t id = (recipes >> (sel & 0xFFu)) & 0xFFu;
     return ldg<uint32_t>(P.recipes, __umul24(id, (1u + MAX_NODES) * 4u) + (sel >> 8));
+}
+__device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t recipes, int lane) {
+    return load_recipe_rows(P, recipes, load_row_selector(P, lane));
 }
 
 // every recipe of the env from scratch (reset): sets e.marks (and e.marks_hi for wide tables)
@@ -243,10 +248,31 @@ __device__ __forceinline__ void init_lut(const Params &P, double *lut, int tid, 
 }
 
 // once per kernel and env: the constant part of the image (cell coordinates: a host-made table, one word per cell)
+// (the table's words are constants of the lane, load_coord_words: step_kernel fetches them with its first loads and hands them over;
+// k_reset and k_observe, which wait for nothing in front of this, fetch them here)
+template <int CPL> struct CoordWords { uint32_t w[CPL]; };
+template <int CPL>
+__device__ __forceinline__ CoordWords<CPL> load_coord_words(const Params &P, int lane) {
+    CoordWords<CPL> cw;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) cw.w[k] = ldg<uint32_t>(P.lut, COORD_TABLE_OFFSET + (uint32_t)(lane + 64 * k) * 4u);
+    return cw;
+}
+template <int CPL>
+__device__ __forceinline__ void init_lds(const Ctx &cx, Lds<CPL> &s, const CoordWords<CPL> &cw) {
+    const int lane = cx.lane;
+    s.img[Img<CPL>::ZERO] = (uint16_t)(LUT_ABSENT * 8);           // (every lane, same value: cheaper than switching lanes off)
+    uint32_t *img32 = reinterpret_cast<uint32_t *>(s.img);
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const uint32_t c = (uint32_t)(lane + 64 * k);
+        img32[(Img<CPL>::CELL0 >> 1) + 2 * c] = cw.w[k];
+    }
+}
 template <int CPL>
 __device__ __forceinline__ void init_lds(const Params &P, const Ctx &cx, Lds<CPL> &s) {
     const int lane = cx.lane;
-    s.img[Img<CPL>::ZERO] = (uint16_t)(LUT_ABSENT * 8);           // (every lane, same value: cheaper than switching lanes off)
+    s.img[Img<CPL>::ZERO] = (uint16_t)(LUT_ABSENT * 8);
     uint32_t *img32 = reinterpret_cast<uint32_t *>(s.img);
 #pragma unroll
     for (int k = 0; k < CPL; ++k) {
@@ -690,6 +716,18 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     constexpr bool SUBMASK_EARLY = CPL == 1;
     uint32_t submask = 0;
     if (SUBMASK_EARLY) submask = load_submask(P, (int)(threadIdx.x & 63u));
+    // The other two constants of the lane - the coordinate words of its cells (init_lds) and its recipe-row selector
+    // (load_recipe_rows) - go out here as well, in front of load_env: none of them needs the record, and behind load_env's fence
+    // the scheduler is free to put them behind the wait for the header words, where they are a second round trip into a cold L2
+    // in front of the workgroup's barrier (k_step_lean was built that way until round 9).  The small instance only, like the
+    // submask: the larger ones would hold up to 16 more registers across the record's loads, and their launches are bound by HBM.
+    constexpr bool TABLES_EARLY = CPL == 1;
+    CoordWords<CPL> coordw{};
+    uint32_t rowsel = 0;
+    if (TABLES_EARLY) {
+        coordw = load_coord_words<CPL>(P, lane);
+        rowsel = load_row_selector(P, lane);
+    }
     Lds<CPL> &lds = lds_all[wave];
     Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
     CZ_STAMP(0);
@@ -704,8 +742,8 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     double ret = ldg<double>(retp, ((uint32_t)lane & 3u) * 8u);                                       // running episode return, lane a = agent a
     Env<OPL, CPL, NA> e;
     load_env<OPL, CPL, NA, V::lean>(P, e, cx, rec);
-    init_lds<CPL>(P, cx, lds);
-    uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
+    if (TABLES_EARLY) init_lds<CPL>(cx, lds, coordw); else init_lds<CPL>(P, cx, lds);
+    uint32_t rowv = TABLES_EARLY ? load_recipe_rows(P, e.recipes, rowsel) : load_recipe_rows(P, e.recipes, lane);
     uint32_t dsc[OBS_CHUNK];
     if (V::f64 && (V::lean || P.obs)) load_desc(P, e.layout, 0, lane, dsc);
     if (!SUBMASK_EARLY) submask = load_submask(P, lane);

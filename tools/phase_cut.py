@@ -9,7 +9,8 @@ assembler COMMENT there (and the listing cz_inst_small_mark.s); comments are not
 so this "marker build" is the shipped code up to a handful of instructions (tools/isa_diff.py says how many: 3893 against 3895
 static instructions for k_step<1,1,2,3,0> in round 5).
 
-    python3 tools/phase_cut.py make [KERNEL_SUBSTRING]     # build container or GPU box: writes cooking_zoo_amd/csrc/cuts/libcz_cut_<i>.so
+    python3 tools/phase_cut.py make [KERNEL_SUBSTRING [LIB LISTING OUTDIR]]   # build container or GPU box: writes OUTDIR/libcz_cut_<i>.so
+                                                           # (defaults: k_step<1,1,2,3,0>, the marker build in csrc/, csrc/cuts/)
     bash tools/phase_cut.sh                                # GPU box: runs them (tools/phase_cut_run.py) under rocprofv3
     python3 tools/phase_cut.py table DIR                   # the table from DIR/cut_<i>/...
 """
@@ -65,13 +66,14 @@ def listing_positions(listing, mangled):
     return mn, marks
 
 
-def make(kernel_sub):
-    lib = os.path.join(CSRC, "libcookingzoo_hip_mark.so")
-    listing = os.path.join(CSRC, "cz_inst_small_mark.s")
+def make(kernel_sub, lib=None, listing=None, outdir=None):
+    lib = lib or os.path.join(CSRC, "libcookingzoo_hip_mark.so")
+    listing = listing or os.path.join(CSRC, "cz_inst_small_mark.s")
+    outdir = outdir or os.path.join(CSRC, "cuts")
     if not (os.path.exists(lib) and os.path.exists(listing)):
         subprocess.check_call(["make", "-C", CSRC, "markers"])
     blob = open(lib, "rb").read()
-    names = re.findall(r"^(_ZN2cz6k_step\w+):", open(listing).read(), flags=re.M)
+    names = re.findall(r"^(_ZN2cz\d+k_step\w+):", open(listing).read(), flags=re.M)
     dem = subprocess.run(["c++filt"], input="\n".join(names), text=True, capture_output=True).stdout.split("\n")
     mangled = [n for n, d in zip(names, dem) if kernel_sub in d.replace(" ", "")]
     assert len(mangled) == 1, (kernel_sub, mangled)
@@ -106,7 +108,7 @@ def make(kernel_sub):
     sec = subprocess.run([OBJDUMP.replace("objdump", "readelf"), "-S", tmp], capture_output=True, text=True).stdout
     t = re.search(r"\]\s+\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", sec)
     vma, off, size = int(t.group(1), 16), int(t.group(2), 16), int(t.group(3), 16)
-    os.makedirs(os.path.join(CSRC, "cuts"), exist_ok=True)
+    os.makedirs(outdir, exist_ok=True)
     meta = {"kernel": kernel_sub, "static_instructions": len(mn_s), "cuts": {}}
     for i, pos in sorted(marks.items()):
         if i not in PHASES:
@@ -118,11 +120,11 @@ def make(kernel_sub):
         assert vma <= addr < vma + size
         patched = bytearray(blob)
         patched[fo:fo + 4] = S_ENDPGM
-        out = os.path.join(CSRC, "cuts", f"libcz_cut_{i}.so")
+        out = os.path.join(outdir, f"libcz_cut_{i}.so")
         open(out, "wb").write(patched)
         os.chmod(out, 0o755)
         meta["cuts"][i] = {"listing_index": marks[i], "address": hex(addr), "was": ins[amap[pos]][1]}
-    json.dump(meta, open(os.path.join(CSRC, "cuts", "cuts.json"), "w"), indent=1)
+    json.dump(meta, open(os.path.join(outdir, "cuts.json"), "w"), indent=1)
     print(json.dumps(meta, indent=1))
 
 
@@ -134,12 +136,12 @@ def table(root):
         c = collections.defaultdict(list)
         for f in glob.glob(d + "/**/*counter_collection.csv", recursive=True):
             for r in csv.DictReader(open(f)):
-                if "k_step<" in r["Kernel_Name"]:
+                if "k_step" in r["Kernel_Name"]:
                     c[r["Counter_Name"]].append(float(r["Counter_Value"]) / (int(r["Grid_Size"]) // 64))
         dur = []
         for f in glob.glob(d + "/**/*kernel_trace.csv", recursive=True):
             for r in csv.DictReader(open(f)):
-                if "k_step<" in r["Kernel_Name"]:
+                if "k_step" in r["Kernel_Name"]:
                     dur.append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
         rows[i] = {k: sum(v) / len(v) for k, v in c.items()}
         if dur:
@@ -176,6 +178,6 @@ def table(root):
 
 if __name__ == "__main__":
     if sys.argv[1] == "make":
-        make(sys.argv[2] if len(sys.argv) > 2 else "k_step<1,1,2,3,0>")
+        make(sys.argv[2] if len(sys.argv) > 2 else "k_step<1,1,2,3,0>", *sys.argv[3:6])
     else:
         table(sys.argv[2])
