@@ -196,6 +196,7 @@ struct cz_handle_s {
     double *d_lut = nullptr;
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
+    float *obs32 = nullptr;            // cz_set_f32_output (or the one call of cz_step_device_f32): one-step launches write float32 rows here
     void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
     void *d_dump = nullptr;            // [N][4] doubles: where a one-step launch writes an output array the caller passed as NULL
     // staging for the host-pointer API
@@ -273,7 +274,7 @@ static int fail(cz_handle h, const char *fmt, ...) {
 extern "C" const char *cz_last_error(cz_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 // Is the stream this handle's work goes to (a stream of the caller, cz_set_stream) being captured - hipStreamBeginCapture,
-// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _many, _ring, cz_rollout*) are then pure
+// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*) are then pure
 // kernel launches: nothing that queries or synchronises (a staged layout update stays staged until the first call outside the
 // capture; no graphs of the library's own inside the caller's), so the capture stays valid and replays do what the launches did.
 static bool caller_capturing(cz_handle h) {
@@ -1057,15 +1058,17 @@ static int ready(cz_handle h) {
 //   fused, P.codes without P.obs      -> ROLLOUT_CODES_ONLY   (cz_rollout_compact)
 //   fused, P.codes and P.obs          -> ROLLOUT_CODES        (cz_rollout_compact)
 //   fused, neither                    -> ROLLOUT              (cz_rollout)
+//   one step, f32 (the handle's       -> STEP_F32             (cz_step_device_f32, cz_set_f32_output; launch_step has refused P.obs or
+//     float32 buffer is set)                                  P.codes beside it and puts the buffer into the slot P.codes shares)
 //   one step, P.codes                 -> STEP_CODES           (cz_step_device_compact, cz_set_compact_output)
 //   one step otherwise                -> STEP, and of that the lean kernel when the handle allows it (CZ_LEAN), the instance has one and
 //                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
 //                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
 //   one step without P.actions        -> hipErrorInvalidValue
-static hipError_t choose_step(cz_handle h, const Params &P, bool fused, StepChoice &c) {
+static hipError_t choose_step(cz_handle h, const Params &P, bool fused, bool f32, StepChoice &c) {
     c.lean = false;
     if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : !P.codes ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
-    else c.mode = P.codes ? STEP_CODES : STEP;
+    else c.mode = f32 ? STEP_F32 : P.codes ? STEP_CODES : STEP;
     if (c.mode == STEP)
         c.lean = h->lean_enabled && h->kl.has_lean && P.obs && !P.marks_out && !P.wide && !(P.auto_reset & 2) && P.F <= 128 * OBS_PAIRS && P.wt == 1;
     return !fused && !P.actions ? hipErrorInvalidValue : hipSuccess;
@@ -1076,13 +1079,22 @@ static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, boo
         return fail(h, "despawn / respawn is on, but the layout pool was reloaded since cz_set_spawn (now %d layouts): call cz_set_spawn "
                        "again (it maps every layout to the level whose spawn areas it uses)", h->n_layouts);
     if (!stream) stream = h->stream;
+    const bool f32 = !fused && h->obs32;
+    if (f32) {          // the float32 rows stand in for the float64 ones and exclude the compact form (k_step<..., STEP_F32> writes nothing else)
+        if (P.codes) return fail(h, "a float32 output (cz_set_f32_output / cz_step_device_f32) and a compact output (cz_set_compact_output / "
+                                    "cz_step_device_compact) are both set: switch one of them off");
+        if (P.obs) return fail(h, "float32 observation rows are switched on (cz_set_f32_output): pass d_obs = NULL, or switch them off "
+                                  "with cz_set_f32_output(h, NULL) to get float64 rows");
+    }
     // write-through observation stores pay when the launch is short enough for the end-of-kernel L2 write-back to be
     // exposed: one step of a batch of up to ~10 000 envs, whatever its rows weigh (round 6, profiles/r06/wt_sizes.txt: the 2.2 KB
     // rows of the 7x7 levels cross over between 10 240 and 12 288 envs - 43 / 52 MiB -, the 6.7 KB rows of large_16x16 are still
     // ahead at 8192 envs = 210 MiB; until round 5 the rule was "up to 128 MiB", which cost the 7x7 levels 5-9 % from 12 288 to
     // 24 576 envs and large_16x16 2-7 % from 6144 to 8192); streaming stores when one launch's observations do not fit the
     // memory-side cache (256 MiB) any more.  (CZ_WT=0/1/2 overrides, for experiments.)
-    const size_t obs_bytes = (size_t)P.N * P.A * P.F * 8;
+    // Float32 rows (STEP_F32) take the same rule with 4 bytes per feature.  Its crossover points were measured for float64 rows only:
+    // for float32 rows the rule is UNMEASURED (profiles/r10/README.md; tools/f32_sizes.py has the CZ_WT sweep that would settle it).
+    const size_t obs_bytes = (size_t)P.N * P.A * P.F * (f32 ? 4 : 8);
     if (!fused) P.wt = obs_bytes > ((size_t)224 << 20) ? 2 : P.N <= 10240 ? 1 : 0;
     // (fused: streaming stores only when an agent's row fills whole DRAM pages - 4 KiB and more, config 5: +8 %; with the
     // 2.2 KB rows of the 7x7 levels they lose 15 % against the cache's own write-back order, profiles/r03/wt_ab2.txt)
@@ -1109,10 +1121,18 @@ static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, boo
         HIPCHK(h, hipEventRecord(e0, stream));
     }
     StepChoice choice;
-    const hipError_t chosen = choose_step(h, P, fused, choice);
+    const hipError_t chosen = choose_step(h, P, fused, f32, choice);
     h->last_step_lean = choice.lean ? 1 : 0;
     HIPCHK(h, chosen);
-    HIPCHK(h, h->kl.step(P, stream, choice));
+    if (f32) {
+        // the buffer goes into the slot P.codes shares, in a copy: callers launch the same P again and again (ring runs, _many), and a
+        // pointer left in their P would be taken for a compact output by the next launch's test above
+        Params Q = P;
+        Q.obs32 = h->obs32;
+        HIPCHK(h, h->kl.step(Q, stream, choice));
+    } else {
+        HIPCHK(h, h->kl.step(P, stream, choice));
+    }
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -1249,11 +1269,54 @@ extern "C" int cz_step_device_compact(cz_handle h, const int32_t *d_actions, uin
 // to d_codes (uint8 [N][A][pitch]); NULL switches it off.  With d_obs = NULL in those calls the launches write codes only.
 extern "C" int cz_set_compact_output(cz_handle h, uint8_t *d_codes) {
     if (!h) return fail(nullptr, "null handle");
+    if (d_codes && h->obs32) return fail(h, "cz_set_compact_output: a float32 output is set (cz_set_f32_output): switch it off first");
     h->P.codes = d_codes;
     h->tables_version++;                  // (graphs captured for the ring carry the pointer)
     return 0;
 }
 extern "C" int32_t cz_codes_pitch(cz_handle h) { return h ? codes_pitch(h->P.F) : 0; }
+
+// The step with the observation as FLOAT32 rows (cooking_env.py:271,352-373 in the dtype a policy network takes): d_obs32 float
+// [N][A][F], dense, every value np.float32 of the reference's float64 feature (round to nearest even) - a gather from the
+// 256-entry table rounded once (cz_obs_table_f32), no arithmetic on values.  Half the observation bytes and no second pass.
+extern "C" int cz_step_device_f32(cz_handle h, const int32_t *d_actions, float *d_obs32, double *d_rewards, uint8_t *d_term,
+                                  uint8_t *d_trunc) {
+    if (begin_device_call(h, d_actions && d_obs32, "cz_step_device_f32: actions and float32 observation pointers must not be null")) return 1;
+    Params P = call_params(h, d_actions, nullptr, d_rewards, d_term, d_trunc);
+    float *const saved = h->obs32;
+    h->obs32 = d_obs32;               // for this one launch (cz_step_compact does the same with the codes)
+    const int rc = launch_step(h, P);
+    h->obs32 = saved;
+    return rc;
+}
+// From now on EVERY one-step launch of the handle (cz_step_device, _many, _ring, cz_step) called with d_obs = NULL writes the
+// float32 rows to d_obs32; NULL switches it off.  Excludes a compact output and a float64 buffer in those calls (launch_step says so).
+extern "C" int cz_set_f32_output(cz_handle h, float *d_obs32) {
+    if (!h) return fail(nullptr, "null handle");
+    if (d_obs32 && h->P.codes) return fail(h, "cz_set_f32_output: a compact output is set (cz_set_compact_output): switch it off first");
+    h->obs32 = d_obs32;
+    h->tables_version++;                  // (graphs captured for the ring carry the pointer)
+    return 0;
+}
+// observe() of the current state as float32 rows [env_count][A][F] into a DEVICE buffer: the first observation of a float32
+// consumer after cz_reset / cz_set_state.  Stream-ordered, nothing is synchronised (legal inside a stream capture of the caller).
+extern "C" int cz_observe_device_f32(cz_handle h, int64_t b, int64_t c, float *d_obs32) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (c == 0) return 0;
+    if (!d_obs32) return fail(h, "cz_observe_device_f32: the output pointer is null");
+    if (set_device(h)) return 1;
+    Params P = h->P;
+    P.wt = 0;
+    HIPCHK(h, h->kl.observe_f32(P, h->stream, b, (int)c, d_obs32));
+    return 0;
+}
+// host mirror of the table the float32 rows are gathered from: what the kernels make of the float64 table while they stage it
+// (v_cvt_f32_f64, round to nearest even) is what this conversion makes of the host copy
+extern "C" int cz_obs_table_f32(cz_handle h, float *table) {
+    if (!h || !table) return fail(h, "cz_obs_table_f32: null argument");
+    for (int i = 0; i < LUT_SIZE; ++i) table[i] = (float)h->obs_table[i];
+    return 0;
+}
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_lean_step.py): 1 if the most recent step launch issued or captured by the
 // handle was the lean one-step kernel, 0 if another kernel, -1 before the first
 extern "C" int32_t cz_diag_last_step_lean(cz_handle h) { return h ? h->last_step_lean : -1; }
@@ -1347,7 +1410,7 @@ static int ring_graph(cz_handle h, Params &P, const int32_t *d_ring, int64_t str
 // cz_set_ring_fused: the run as fused launches over the ring's own action rows (cz_rollout_actions' kernel, every step's outputs
 // written in place), one launch per stretch of consecutive slots.  Needs densely packed slots (stride = num_envs * num_agents).
 static bool ring_fusable(cz_handle h, const Params &P, int32_t K, int64_t stride) {
-    return h->ring_fused && K >= 2 && !h->ktime && !P.codes && stride == (int64_t)P.N * P.A;
+    return h->ring_fused && K >= 2 && !h->ktime && !P.codes && !h->obs32 && stride == (int64_t)P.N * P.A;
 }
 static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot) {
     // (the kernel addresses the action rows with 32-bit byte offsets from the first row of the launch)

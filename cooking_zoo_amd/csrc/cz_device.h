@@ -65,7 +65,10 @@ struct Params {
     double *rewards;               // [N][A] / [T][N][A] / nullptr
     uint8_t *term, *trunc;         // likewise
     uint32_t *marks_out;           // [N] recipe-node marks after the step (host-pointer cz_step only), or nullptr
-    uint8_t *codes;                // [N][A][Fp] compact observation (cz_step_device_compact): one table index per feature, or nullptr
+    union {                        // (one slot: a launch writes one of the two at most, and the block must not grow - see below)
+        uint8_t *codes;            // [N][A][Fp] compact observation (cz_step_device_compact): one table index per feature, or nullptr
+        float *obs32;              // k_step<..., STEP_F32> only (launch_step in cz_api.hip puts it here): [N][A][F] dense float32 rows
+    };
     uint32_t *stat_u;              // [N][SU_WORDS]
     double *stat_f;                // [N][SF_WORDS]
     int64_t env_id_base;
@@ -81,6 +84,7 @@ struct Params {
     int32_t walk_touches;          // 1 if carrying an object across cells can change a recipe mark (see cz_load_recipes)
     int32_t wide;                  // 1: wide recipe tables (up to 16 nodes per graph, marks in record words 1 and 7)
     // (the argument block: 56 bytes of leading scalars + this struct, within five 64-byte lines; a sixth line costs every launch)
+    // (and a field more changes the register allocation of every kernel that takes the block, the ones that never read it included)
 #ifdef CZ_PROFILE
     unsigned long long *stamps;    // diagnostic build only: [N][8] s_memtime stamps
 #endif

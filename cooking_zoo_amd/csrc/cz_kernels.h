@@ -52,10 +52,12 @@ enum StepMode : int {
                               // allocation and a longer prologue, even when unused)
     ROLLOUT_CODES = 4,        // P.T steps over the on-device action stream with a compact trajectory [t][env][agent][pitch] (cz_rollout_compact)
     ROLLOUT_CODES_ONLY = 5,   // the same without a float64 trajectory beside it
+    STEP_F32 = 6,             // one step that writes the observation as dense float32 rows float[N][A][F] (cz_step_device_f32 / cz_set_f32_output)
+                              // and nothing else: its own instance for the reason STEP_CODES is one
 };
 template <int MODE, bool LEAN = false>
 struct StepTraits {
-    static_assert(MODE >= STEP && MODE <= ROLLOUT_CODES_ONLY && (!LEAN || MODE == STEP), "no such variant");
+    static_assert(MODE >= STEP && MODE <= STEP_F32 && (!LEAN || MODE == STEP), "no such variant");
     static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // P.T steps per launch
     static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS;                         // a fused launch that reads the caller's actions
     static constexpr bool codes = MODE == STEP_CODES || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // writes the compact observation
@@ -63,7 +65,10 @@ struct StepTraits {
     // descriptor registers, its encode - the codes' own descriptor words fit the registers for the whole launch (ROLLOUT_CODES reloads
     // them every step: held there they cost 136 vector registers, three waves per SIMD)
     static constexpr bool codes_only = MODE == ROLLOUT_CODES_ONLY;
-    static constexpr bool f64 = !codes_only;                                             // carries the float64 observation path
+    // the float32 rows: np.float32 of the float64 feature (round to nearest even), gathered from a float32 copy of the table that the
+    // workgroup makes while it stages the table into LDS - no arithmetic on values, no float64 path beside it
+    static constexpr bool f32 = MODE == STEP_F32;
+    static constexpr bool f64 = !codes_only && !f32;                                     // carries the float64 observation path
     // k_step_lean: the one-step kernel with the handle's uniform settings fixed at compile time - narrow recipe tables, no despawn /
     // respawn, float64 observations of at most 128 * OBS_PAIRS features with write-through stores, no compact output and no marks
     // buffer (choose_step in cz_api.hip picks it when all of that holds).  The code is the one-step kernel with those tests folded
@@ -324,7 +329,11 @@ __device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {        
 }
 // LEAN (k_step_lean, see StepTraits): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
 // time - one chunk, no store-flavour switch, no descriptor reload.  F64 = false: the codes-only variant, which carries no float64 path.
-template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false>
+// F32 (STEP_F32, k_observe_f32): `out` is float[A][F] of this env - dense rows, no pitch - and `lut` the FLOAT32 table (256 floats: every
+// entry the float64 one rounded to nearest even), neither float64 rows nor codes.  Shaped like the codes path: a lane takes four adjacent
+// features per round of 256, one descriptor b128 load (`pre` holds the first rounds'), and one 16-byte store per observer whose range,
+// F * 4 bytes from the row's base, drops what lies past the row - nothing is written behind a row, there is no padding.
+template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false, bool F32 = false>
 __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
                                         const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
                                         bool objs_changed = true, bool cells_changed = true, uint8_t *__restrict__ codes = nullptr /* [A][Fp] */,
@@ -385,6 +394,47 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
     const char *lutb = reinterpret_cast<const char *>(lut);
     const char *imgb = reinterpret_cast<const char *>(s.img);
     const char *subb = reinterpret_cast<const char *>(s.sub);
+    if constexpr (F32) {
+        float *const out32 = reinterpret_cast<float *>(out);
+        decltype(__builtin_amdgcn_make_buffer_rsrc(out32, 0, 0, 0)) r32[NA];
+        // (a row starts wherever the rows before it end: 4-byte aligned when F is odd.  Buffer stores of several dwords need dword
+        // alignment only, and the range check works dword by dword - what the float64 rows of an odd F, 8-byte aligned, rely on too)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) r32[a] = __builtin_amdgcn_make_buffer_rsrc(out32 + (size_t)a * (uint32_t)P.F, 0, P.F * 4, 0x00020000);
+        const uint32_t wt = (uint32_t)P.wt;                                              // wave-uniform
+        for (int f0 = 0; f0 < P.F; f0 += 256) {
+            const uint32_t f = (uint32_t)f0 + 4u * (uint32_t)cx.lane;                       // this lane's first feature
+            uint4_t d;
+            if (pre && f0 < 256 * CODES_PREFETCH) d = f0 == 0 ? pre->d[0] : pre->d[1];
+            else d = load_desc4(P, e.layout, f);
+            const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
+            uint32_t b[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const uint16_t *>(imgb + (dw[k] & 0xFFFFu));
+            int sb[NA][4];
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sb[a][k] = *reinterpret_cast<const int32_t *>(subb + 64 * a + (dw[k] >> 16));
+            // image halfword - subtrahend: the byte offset into the float64 table (a multiple of 8); halved, into the float32 one
+            uint4_t v[NA];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                uint32_t w[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const uint32_t *>(lutb + (((int)b[k] - sb[a][k]) >> 1));
+                v[a].x = w[0]; v[a].y = w[1]; v[a].z = w[2]; v[a].w = w[3];
+            }
+#define CZ_OBS_WRITE_ROWS32(AUX)                                                                                             \
+    _Pragma("unroll") for (int a = 0; a < NA; ++a) __builtin_amdgcn_raw_buffer_store_b128(v[a], r32[a], f * 4u, 0, AUX)
+            if (wt == 1u) { CZ_OBS_WRITE_ROWS32(16); }          // sc1: write-through
+            else if (wt == 2u) { CZ_OBS_WRITE_ROWS32(2); }      // nt: streaming
+            else { CZ_OBS_WRITE_ROWS32(0); }
+#undef CZ_OBS_WRITE_ROWS32
+        }
+        __builtin_amdgcn_wave_barrier();
+        return;
+    }
     if (codes) {
         const int Fp = codes_pitch(P.F);
         decltype(__builtin_amdgcn_make_buffer_rsrc(codes, 0, 0, 0)) rc[NA];
@@ -750,7 +800,10 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     const int64_t env_global = P.env_id_base + env;
     bool cells_dirty = false, objs_dirty = false, header_dirty = V::fused;
     bool img_objs = true, img_cells = true;                 // which parts of the LDS image the next encode must rebuild
-    if (threadIdx.x < (unsigned)LUT_SIZE) lut[threadIdx.x] = lutv;
+    // (STEP_F32: the same array holds the float32 table - every entry rounded to nearest even, v_cvt_f32_f64 in the default rounding
+    // mode, which is what cz_obs_table_f32 hands the host - so the float32 form adds no load to the prologue)
+    if (V::f32) { if (threadIdx.x < (unsigned)LUT_SIZE) reinterpret_cast<float *>(lut)[threadIdx.x] = (float)lutv; }
+    else if (threadIdx.x < (unsigned)LUT_SIZE) lut[threadIdx.x] = lutv;
     __syncthreads();
     if (env_raw >= P.N) return;
     CZ_STAMP(1);
@@ -760,7 +813,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     cpre.layout = e.layout;
     // (this fetch is spelled out at its three sites: behind a shared function - tried with and without the layout word - the code
     // variants come out with a few instructions more or fewer, and the shipped streams are kept instruction for instruction)
-    if (V::codes && (!V::fused || V::codes_only)) {
+    if ((V::codes || V::f32) && (!V::fused || V::codes_only)) {
 #pragma unroll
         for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(P, e.layout, 256u * r + 4u * (uint32_t)lane);
     }
@@ -840,7 +893,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         const size_t row = V::fused ? ((size_t)(in_place ? 0 : t) * Pt.N + env) : (size_t)env;
         // (the compact path's descriptor words were fetched long ago; waiting for them HERE costs nothing, while behind the
         // stores below the same wait would also stand for those stores' acknowledgement - one counter for loads and stores)
-        if (V::codes) {
+        if (V::codes || V::f32) {
             if (CZ_RARE(V::fused, cpre.layout != e.layout)) {                 // a reset pass has moved the env to another layout
                 cpre.layout = e.layout;
 #pragma unroll
@@ -871,7 +924,11 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         CZ_STAMP(5);
         img_objs |= (dt.touched | dt.moved) != 0;
         img_cells |= dt.cells != 0;
-        if (V::lean || Pt.obs || V::codes) {
+        if constexpr (V::f32) {
+            // (choose_step takes this variant only with a float32 buffer: the rows are written unconditionally)
+            float *const obs_row = Pt.obs32 + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F);
+            observe<OPL, CPL, NA, false, false, true>(Pt, e, cx, lds, lut, dsc, submask, reinterpret_cast<double *>(obs_row), img_objs, img_cells, nullptr, &cpre);
+        } else if (V::lean || Pt.obs || V::codes) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
             uint8_t *const codes = V::codes ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
             double *const obs_row = V::f64 && Pt.obs ? Pt.obs + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F) : nullptr;
@@ -983,6 +1040,24 @@ __global__ __launch_bounds__(64) void k_observe(const Params P, int64_t env_begi
             codes_out ? codes_out + (size_t)i * NA * codes_pitch(P.F) : nullptr);
 }
 
+// ... as float32 rows float[count][A][F] (cz_observe_device_f32): the form of STEP_F32, for the first observation after cz_reset /
+// cz_set_state.  A kernel of its own, so that k_observe stays the code it was.
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_begin, float *obs_out) {
+    __shared__ Lds<CPL> lds;
+    __shared__ float lutf[LUT_SIZE];
+    for (int i = (int)threadIdx.x; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
+    const int i = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    init_lds<CPL>(P, cx, lds);
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, P.state + (size_t)(env_begin + i) * P.RW);
+    uint32_t dsc[OBS_CHUNK] = {};
+    observe<OPL, CPL, NA, false, false, true>(P, e, cx, lds, reinterpret_cast<const double *>(lutf), dsc, load_submask(P, lane),
+                                              reinterpret_cast<double *>(obs_out + (size_t)i * NA * P.F));
+}
+
 // launchers exported by each instantiation unit
 struct StepChoice { StepMode mode; bool lean; };       // which variant a launch takes (choose_step, cz_api.hip)
 struct Launchers {
@@ -991,6 +1066,7 @@ struct Launchers {
     hipError_t (*reset)(const Params &, hipStream_t, int64_t, int, const int32_t *, const uint32_t *, const uint32_t *, double *);
     hipError_t (*observe)(const Params &, hipStream_t, int64_t, int, double *, uint8_t *);
     bool has_lean;             // the instance carries the k_step_lean kernels
+    hipError_t (*observe_f32)(const Params &, hipStream_t, int64_t, int, float *);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1034,6 +1110,7 @@ struct Inst {
                 case STEP_CODES: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_CODES>, P, st);
                 case ROLLOUT_CODES: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES>, P, st);
                 case ROLLOUT_CODES_ONLY: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES_ONLY>, P, st);
+                case STEP_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_F32>, P, st);
                 }
                 return hipErrorInvalidValue;
             });
@@ -1052,7 +1129,13 @@ struct Inst {
             return hipGetLastError();
         });
     }
-    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN}; }
+    static hipError_t observe_f32(const Params &P, hipStream_t st, int64_t b, int n, float *obs) {
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_observe_f32<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, obs);
+            return hipGetLastError();
+        });
+    }
+    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32}; }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

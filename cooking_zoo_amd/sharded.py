@@ -273,6 +273,9 @@ class ShardedVecEnv:
     def obs_table(self):
         return self.shards[0].obs_table()
 
+    def obs_table_f32(self):
+        return self.shards[0].obs_table_f32()
+
     @property
     def codes_pitch(self):
         return self.shards[0].codes_pitch
@@ -296,6 +299,19 @@ class ShardedVecEnv:
     def step_device_compact(self, d_actions, d_codes, d_rewards, d_term, d_trunc, d_obs=None):
         P = self._part
         self._each(lambda i, env: env.step_device_compact(P(d_actions, i), P(d_codes, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i), P(d_obs, i)))
+
+    def step_device_f32(self, d_actions, d_obs32, d_rewards, d_term, d_trunc):
+        P = self._part
+        self._each(lambda i, env: env.step_device_f32(P(d_actions, i), P(d_obs32, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))
+
+    def set_f32_output(self, d_obs32=None):
+        """`CookingVecEnv.set_f32_output` on every shard (d_obs32: a ShardedBuffer of float32 [envs of the shard, A, F], or None)"""
+        self._each(lambda i, env: env.set_f32_output(self._part(d_obs32, i)))
+
+    def observe_device(self, d_obs=None, d_codes=None, d_obs32=None):
+        """the current observation of every shard into its part of the device buffers (`CookingVecEnv.observe_device`)"""
+        P = self._part
+        self._each(lambda i, env: env.observe_device(P(d_obs, i), P(d_codes, i), d_obs32=P(d_obs32, i)))
 
     def step_device_ring(self, K, d_ring, action_period, first_slot, d_obs, d_rewards, d_term, d_trunc):
         """K steps; step k reads slot (first_slot + k) % action_period of `d_ring` (ShardedBuffer with leading = (action_period,))"""

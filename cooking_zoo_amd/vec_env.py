@@ -688,11 +688,14 @@ class CookingVecEnv:
         _native.check(self._h, _native.lib().cz_observe_compact(self._h, env_begin, n, _ptr(codes)))
         return codes
 
-    def observe_device(self, d_obs=None, d_codes=None, env_begin=0, env_count=None):
-        """the current observation into device buffers (float64 [n, A, F] and / or codes uint8 [n, A, codes_pitch]), stream-ordered:
-        what a device-resident consumer reads before its first step"""
+    def observe_device(self, d_obs=None, d_codes=None, env_begin=0, env_count=None, d_obs32=None):
+        """the current observation into device buffers (float64 [n, A, F] and / or codes uint8 [n, A, codes_pitch] and / or float32
+        [n, A, F] rows, the form of `step_device_f32`), stream-ordered: what a device-resident consumer reads before its first step"""
         n = self.num_envs if env_count is None else int(env_count)
-        _native.check(self._h, _native.lib().cz_observe_device(self._h, env_begin, n, _dev_ptr(d_obs), _dev_ptr(d_codes)))
+        if d_obs is not None or d_codes is not None or d_obs32 is None:
+            _native.check(self._h, _native.lib().cz_observe_device(self._h, env_begin, n, _dev_ptr(d_obs), _dev_ptr(d_codes)))
+        if d_obs32 is not None:
+            _native.check(self._h, _native.lib().cz_observe_device_f32(self._h, env_begin, n, _dev_ptr(d_obs32)))
 
     # ------------------------------------------------------------------ device-resident API
     def alloc(self, shape, dtype):
@@ -743,6 +746,25 @@ class CookingVecEnv:
         """every one-step launch from now on (step_device, step_device_ring, step) also writes the compact observation to d_codes
         (uint8 [N, A, codes_pitch]); None switches it off.  Pass d_obs=None to those calls for codes only."""
         _native.check(self._h, _native.lib().cz_set_compact_output(self._h, _dev_ptr(d_codes)))
+
+    def step_device_f32(self, d_actions, d_obs32, d_rewards, d_term, d_trunc):
+        """Device-resident step whose observation is float32: d_obs32 float32 [N, A, F], contiguous (e.g. a torch.float32 tensor of
+        that shape), receives np.float32 of every float64 feature bit for bit - what `obs64.float()` gives, without the float64 rows
+        and the second pass.  Rewards stay float64."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_step_device_f32(self._h, p(d_actions), p(d_obs32), p(d_rewards), p(d_term), p(d_trunc)))
+        self._issued(1)
+
+    def set_f32_output(self, d_obs32=None):
+        """every one-step launch from now on (step_device, step_device_ring, step) called with d_obs=None writes the float32 rows to
+        d_obs32 (float32 [N, A, F]); None switches it off.  Excludes a compact output, and a float64 buffer in those calls."""
+        _native.check(self._h, _native.lib().cz_set_f32_output(self._h, _dev_ptr(d_obs32)))
+
+    def obs_table_f32(self):
+        """the 256 float32 values the float32 rows are gathered from: `obs_table().astype(np.float32)`, as the device rounds them"""
+        t = np.empty(256, dtype=np.float32)
+        _native.check(self._h, _native.lib().cz_obs_table_f32(self._h, _ptr(t)))
+        return t
 
     @property
     def codes_pitch(self):

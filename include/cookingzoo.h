@@ -46,7 +46,7 @@ extern "C" {
 
 /* The one place the ABI number lives: cz_abi_version() returns it, cooking_zoo_amd/_native.py parses it from this file
  * and refuses a library that reports another one, __graft_entry__.build() and the tests compare against it. */
-#define CZ_ABI_VERSION 9
+#define CZ_ABI_VERSION 10
 
 typedef struct cz_handle_s *cz_handle;
 
@@ -101,14 +101,15 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
  * stream.  The stream must belong to the handle's device and outlive its use here. */
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
- * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_many / _ring, cz_rollout*, cz_observe_device,
- * cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
+ * cz_observe_device, cz_observe_device_f32, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
  * cz_set_layout_group ...) are not; the last two say so, the others fail with HIP's own error.  (cz_generate_layouts is a pure
  * launch too, and so is a cz_set_layout_group that only changes the active part: see there.)  The captured launches carry the
- * table pointers of their time: after cz_load_layouts / cz_load_recipes / cz_set_spawn / cz_set_compact_output capture again.
+ * table pointers of their time: after cz_load_layouts / cz_load_recipes / cz_set_spawn / cz_set_compact_output /
+ * cz_set_f32_output capture again.
  * cz_stream_capturing: 1 while the handle's stream is a stream of the caller that is being captured, else 0 - a host layer that
  * keeps count of the steps it issued (cooking_zoo_amd: layout rotation schedules) must not count captured launches as steps:
  * they run when the caller's graph is replayed, as often as it is replayed. */
@@ -228,6 +229,9 @@ int cz_observe_compact(cz_handle h, int64_t env_begin, int64_t env_count, uint8_
  * the first observation of a consumer that stays on the device, after cz_reset / cz_set_state.  Stream-ordered, nothing is
  * synchronised. */
 int cz_observe_device(cz_handle h, int64_t env_begin, int64_t env_count, double *d_obs, uint8_t *d_codes);
+/* ... and as FLOAT32 rows (cooking_env.py:271,352-373 in the dtype of cz_step_device_f32): device buffer float [env_count][A][F],
+ * dense.  Stream-ordered, nothing is synchronised. */
+int cz_observe_device_f32(cz_handle h, int64_t env_begin, int64_t env_count, float *d_obs32);
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
@@ -266,6 +270,24 @@ int32_t cz_codes_pitch(cz_handle h);
 int cz_obs_table(cz_handle h, double table[256]);
 const void *cz_obs_table_device(cz_handle h);
 
+/* The same step with the observation of observe() / get_feature_vector (cooking_env.py:271,352-373) as FLOAT32 rows, the dtype a
+ * policy network takes: d_obs32 float [N][A][F], dense (no pitch: a float32 tensor of that shape is contiguous), every element
+ * (float) of the reference's float64 feature, rounded to nearest even - bit for bit np.float32(x), what torch's .float() gives.
+ * The values are gathered from a second 256-entry table, the float64 one rounded once (cz_obs_table_f32 is its host mirror):
+ * half the observation bytes of cz_step_device and no conversion pass behind it.  d_obs32 must not be NULL; rewards stay
+ * float64.  Asynchronous on the handle's stream. */
+int cz_step_device_f32(cz_handle h, const int32_t *d_actions, float *d_obs32, double *d_rewards, uint8_t *d_terminations,
+                       uint8_t *d_truncations);
+/* ... or as a setting of the handle (cooking_env.py:271,352-373 for every launch that follows): from now on every one-step
+ * launch (cz_step_device, _many, _ring, cz_step) called with d_obs = NULL writes the float32 rows to d_obs32; NULL switches it
+ * off.  Refused: setting it while a compact output is set (and the reverse), and a one-step call with d_obs != NULL while it is
+ * set.  Ring graphs built before the call are dropped; fused ring runs (cz_set_ring_fused) are issued as one-step launches
+ * while it is set.  The fused rollouts (cz_rollout*) ignore it: their float32-sized form is the compact trajectory. */
+int cz_set_f32_output(cz_handle h, float *d_obs32);
+/* host mirror of the table those rows are gathered from (cooking_env.py:352-373: every feature is one of these values):
+ * table[i] == (float)cz_obs_table[i], and d_obs32[e][a][f] == table[codes[e][a][f]] bit for bit. */
+int cz_obs_table_f32(cz_handle h, float table[256]);
+
 /* K consecutive steps, one launch each, issued from C: step k reads its actions at d_actions + (k % action_period) *
  * action_stride (in int32 elements) and overwrites the same output buffers.  Equivalent to K cz_step_device calls. */
 int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_actions, int64_t action_stride, int32_t action_period,
@@ -291,7 +313,7 @@ int cz_ring_prepare(cz_handle h, int32_t K, const int32_t *d_ring, int64_t actio
  * output buffers and statistics are bit for bit what K one-step launches leave (cooking_env.py:243-269 K times) - at the cost
  * per step of a fused rollout, without launch boundaries.  Open loop by nature (the actions
  * of the whole run are read by one launch).  Runs with other strides, a compact
- * output (cz_set_compact_output) or kernel timing switched on are issued as before.  Returns the previous setting, -1 for a
+ * output (cz_set_compact_output), a float32 output (cz_set_f32_output) or kernel timing switched on are issued as before.  Returns the previous setting, -1 for a
  * null handle; cz_ring_fused_steps: env steps issued this way so far (reset != 0: zero the count after reading). */
 int cz_set_ring_fused(cz_handle h, int32_t enabled);
 int64_t cz_ring_fused_steps(cz_handle h, int32_t reset);

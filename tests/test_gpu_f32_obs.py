@@ -1,0 +1,395 @@
+"""GPU: the observation as float32 rows (cz_step_device_f32 / cz_set_f32_output / cz_observe_device_f32): float [N][A][F], dense,
+every element np.float32 of the reference's float64 feature (cooking_env.py:352-373; round to nearest even) - compared bit for bit
+as uint32 against the oracle's rows on every level family / kernel instance / scheme / agent count, with a sentinel pattern under
+the rows and a guard region behind them (a 16-byte store that ran past its row would show), on despawning mixed-level batches and
+a wide user book, through ring runs (graph replay and direct launches), with fused ring runs switched on, as the first observation
+after reset / set_state, over two shards, and inside a stream capture of the caller."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cooking_zoo_amd import _native, soa
+from test_gpu_compact_obs import CASES, make, strip
+
+pytestmark = pytest.mark.gpu
+
+SENTINEL = 0x7FC0BEEF            # a quiet NaN no table entry equals
+GUARD = 1024                     # float32 words behind the last row
+
+
+def bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def want32(obs64):
+    """what the float32 rows must hold, as uint32"""
+    return np.ascontiguousarray(obs64, dtype=np.float64).astype(np.float32).view(np.uint32)
+
+
+class GuardedRows:
+    """float32 rows [n][A][F] with GUARD sentinel words behind the last one"""
+
+    def __init__(self, env, n=None):
+        self.n = env.num_envs if n is None else n
+        self.shape = (self.n, env.num_agents, env.F)
+        self.words = int(np.prod(self.shape))
+        self.buf = env.alloc((self.words + GUARD,), np.uint32)
+        self.ptr = self.buf.ptr
+        self.fill()
+
+    def fill(self):
+        self.buf.from_host(np.full(self.words + GUARD, SENTINEL, dtype=np.uint32))
+
+    def rows(self):
+        """the rows as uint32 [n][A][F]; asserts the guard is untouched"""
+        got = self.buf.to_host()
+        assert (got[self.words:] == SENTINEL).all(), "a store went past the last row"
+        return got[:self.words].reshape(self.shape)
+
+
+def test_the_cases_are_the_thirteen_of_the_compact_test():
+    assert len(CASES) == 13 and any(c[4] == "example_odd" for c in CASES)
+
+
+@pytest.mark.parametrize("scheme,level,agents,recipes,meta", CASES)
+def test_float32_rows_are_the_rounded_oracle_observation(scheme, level, agents, recipes, meta):
+    from oracle_binding import VecOracle
+    n, T = 48, 70
+    env, twin = make(n, level, meta, agents, recipes, scheme), make(n, level, meta, agents, recipes, scheme)
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    twin.reset(return_obs=False)
+    orc.reset()
+    A, F = agents, env.F
+    if meta == "example_odd":
+        assert F == 283
+    t32 = env.obs_table_f32()
+    assert t32.dtype == np.float32 and np.array_equal(t32.view(np.uint32), env.obs_table().astype(np.float32).view(np.uint32))
+    d_act, rows = env.alloc((n, A), np.int32), GuardedRows(env)
+    d_rew, d_t, d_u = env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
+    w_act, w_obs = twin.alloc((n, A), np.int32), twin.alloc((n, A, F), np.float64)
+    rng = np.random.default_rng(5)
+    for t in range(T):
+        acts = rng.integers(0, env.n_actions, size=(n, A), dtype=np.int32)
+        d_act.from_host(acts)
+        rows.fill()
+        env.step_device_f32(d_act, rows, d_rew, d_t, d_u)
+        env.sync()
+        oo, ro, to, uo = orc.step(acts)
+        got = rows.rows()
+        assert np.array_equal(got, want32(oo)), f"float32 observation at step {t}"
+        assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)), f"rewards at step {t}"
+        assert np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), f"flags at step {t}"
+        # the twin walks the same trajectory; every third step through float64 rows, checked against the oracle too
+        w_act.from_host(acts)
+        twin.step_device(w_act, w_obs if t % 3 == 0 else None, None, None, None)
+        if t % 3 == 0:
+            twin.sync()
+            assert np.array_equal(bits64(w_obs.to_host()), bits64(oo)), f"float64 observation of the twin at step {t}"
+            assert np.array_equal(strip(twin.get_state()), orc.records) and np.array_equal(strip(env.get_state()), orc.records), t
+    assert np.array_equal(strip(env.get_state()), orc.records)
+    assert int(env.get_state()[:, soa.W_EPISODE].min()) >= 1          # reset passes were encoded too
+    env.close()
+    twin.close()
+
+
+def test_despawn_respawn_on_a_mixed_level_batch():
+    from cooking_zoo_amd.vec_env import CookingVecEnv
+    from oracle_binding import VecOracle
+    n, A = 96, 2
+    kw = dict(action_scheme="scheme3", num_layouts=6, auto_reset=True, agent_despawn_rate=0.12, agent_respawn_rate=0.3, grace_period=3, spawn_seed=21)
+    env = CookingVecEnv(n, ["coop_test", "switch_test"], "example", A, 35, ["TomatoSalad", "TomatoSalad"], env_id_base=500, **kw)
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    orc.reset()
+    d_act, rows = env.alloc((n, A), np.int32), GuardedRows(env)
+    d_rew, d_t, d_u = env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
+    rng = np.random.default_rng(8)
+    gone_seen = 0
+    for t in range(80):
+        acts = rng.integers(0, env.n_actions, size=(n, A), dtype=np.int32)
+        d_act.from_host(acts)
+        env.step_device_f32(d_act, rows, d_rew, d_t, d_u)
+        env.sync()
+        oo, ro, to, uo = orc.step(acts)
+        assert np.array_equal(rows.rows(), want32(oo)), t
+        assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
+        gone_seen += int((((orc.records[:, soa.W_STATUS] >> 8) & 0xF) != 0).sum())
+    assert np.array_equal(strip(env.get_state()), orc.records) and gone_seen > 100
+    env.close()
+
+
+def test_wide_user_book():
+    """graphs of more than 8 nodes (custom_wide_* recipes: wide tables, marks in record words 1 and 7)"""
+    from cooking_zoo_amd.cooking_book import recipe_drawer as rd
+    from oracle_binding import VecOracle
+    from test_custom_recipes import register_fixture_recipes
+    assert not rd.RECIPE_STORE
+    register_fixture_recipes()
+    try:
+        n, A = 64, 2
+        env = make(n, "coop_test", "example", A, ["FruitFeast", "PickyBanana"], "scheme3")
+        assert env.recipe_nodes == 16
+        orc = VecOracle.from_vec_env(env)
+        env.reset(return_obs=False)
+        orc.reset()
+        d_act, rows = env.alloc((n, A), np.int32), GuardedRows(env)
+        d_rew, d_t, d_u = env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
+        rng = np.random.default_rng(4)
+        for t in range(70):
+            acts = rng.integers(0, env.n_actions, size=(n, A), dtype=np.int32)
+            d_act.from_host(acts)
+            env.step_device_f32(d_act, rows, d_rew, d_t, d_u)
+            env.sync()
+            oo, ro, to, uo = orc.step(acts)
+            assert np.array_equal(rows.rows(), want32(oo)), t
+            assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
+        assert np.array_equal(strip(env.get_state()), orc.records)
+        env.close()
+    finally:
+        rd.RECIPE_STORE.clear()
+
+
+@pytest.mark.parametrize("K,graph", [(60, True), (20, False)])
+def test_ring_runs_with_the_float32_output_set_on_the_handle(K, graph):
+    """cz_set_f32_output: ring runs - K >= 48: graph replay, K < 48: direct launches - write the float32 rows; switching it off
+    restores the float64 kernels, and the graphs captured before a switch are not replayed with a stale pointer"""
+    from oracle_binding import VecOracle
+    n, A, period = 192, 2, 64
+    env = make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=25)
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    orc.reset()
+    ring_host = np.random.default_rng(9).integers(0, 5, size=(period, n, A), dtype=np.int32)
+    d_ring = env.alloc((period, n, A), np.int32)
+    d_ring.from_host(ring_host)
+    d_obs, rows, other = env.alloc((n, A, env.F), np.float64), GuardedRows(env), GuardedRows(env)
+    outs = [env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)]
+    L, h = _native.lib(), env._h
+    gk, dk = C.c_int64(), C.c_int64()
+    step = 0
+    for phase, (f32, obs) in enumerate([(None, d_obs), (rows, None), (other, None), (None, d_obs), (rows, None)]):
+        env.set_f32_output(f32)
+        rows.fill()
+        other.fill()
+        _native.check(h, L.cz_launch_counts(h, None, None, 1))
+        env.step_device_ring(K, d_ring, n * A, period, 0, obs, *outs)
+        env.sync()
+        _native.check(h, L.cz_launch_counts(h, C.byref(gk), C.byref(dk), 0))
+        assert (gk.value > 0) == graph and gk.value + dk.value == K, (gk.value, dk.value)
+        for k in range(K):
+            oo, ro, to, uo = orc.step(ring_host[k % period], k == K - 1)
+        step += K
+        if obs is not None:
+            assert np.array_equal(bits64(d_obs.to_host()), bits64(oo)), phase
+            assert (rows.rows() == SENTINEL).all() and (other.rows() == SENTINEL).all(), phase
+        else:
+            assert np.array_equal(f32.rows(), want32(oo)), phase
+            assert ((other if f32 is rows else rows).rows() == SENTINEL).all(), phase
+        assert np.array_equal(bits64(outs[0].to_host()), bits64(ro)) and np.array_equal(outs[2].to_host(), uo), phase
+        assert np.array_equal(strip(env.get_state()), orc.records), phase
+    env.close()
+
+
+def test_fused_ring_runs_fall_back_to_one_step_launches():
+    """cz_set_ring_fused with the float32 output set: the run goes out as one-step launches - identical results, no fused steps"""
+    n, A, period, K = 160, 2, 16, 16
+    a, b = (make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=25) for _ in range(2))
+    ring_host = np.random.default_rng(3).integers(0, 5, size=(period, n, A), dtype=np.int32)
+    res = []
+    for env, fused in ((a, True), (b, False)):
+        env.reset(return_obs=False)
+        d_ring = env.alloc((period, n, A), np.int32)
+        d_ring.from_host(ring_host)
+        rows = GuardedRows(env)
+        outs = [env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)]
+        env.set_ring_fused(fused)
+        env.set_f32_output(rows)
+        for _ in range(3):
+            env.step_device_ring(K, d_ring, n * A, period, 0, None, *outs)
+        env.sync()
+        assert env.ring_fused_steps() == 0
+        res.append((rows.rows(), [o.to_host() for o in outs], strip(env.get_state())))
+        # ... and with the setting off the same call is fused again
+        env.set_f32_output(None)
+        env.step_device_ring(K, d_ring, n * A, period, 0, None, *outs)
+        env.sync()
+        assert env.ring_fused_steps() == (K if fused else 0)
+    assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][2], res[1][2])
+    assert all(np.array_equal(x.view(np.uint8), y.view(np.uint8)) for x, y in zip(res[0][1], res[1][1]))
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("scheme,level,agents,recipes,meta", [CASES[0], CASES[1], CASES[4], CASES[6], CASES[-1]])
+def test_first_observation_as_float32_after_reset_and_set_state(scheme, level, agents, recipes, meta):
+    from oracle_binding import VecOracle
+    n = 96
+    env = make(n, level, meta, agents, recipes, scheme)
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    first = orc.reset()
+    rows = GuardedRows(env)
+    env.observe_device(d_obs32=rows)
+    env.sync()
+    assert np.array_equal(rows.rows(), want32(first))
+    rng = np.random.default_rng(1)
+    for _ in range(12):
+        acts = rng.integers(0, env.n_actions, size=(n, agents), dtype=np.int32)
+        oo, *_ = orc.step(acts)
+    env.set_state(orc.records)
+    part = GuardedRows(env, 40)
+    d_obs = env.alloc((40, agents, env.F), np.float64)
+    env.observe_device(d_obs, None, env_begin=17, env_count=40, d_obs32=part)       # both forms in one call
+    env.sync()
+    assert np.array_equal(part.rows(), want32(oo[17:57])) and np.array_equal(bits64(d_obs.to_host()), bits64(oo[17:57]))
+    env.close()
+
+
+def test_argument_errors():
+    env = make(8, "coop_test", "example", 2, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3")
+    env.reset(return_obs=False)
+    L, h = _native.lib(), env._h
+    d_act, d_obs = env.alloc((8, 2), np.int32), env.alloc((8, 2, env.F), np.float64)
+    rows, d_codes = GuardedRows(env), env.alloc((8, 2, env.codes_pitch), np.uint8)
+    assert L.cz_step_device_f32(h, d_act.ptr, None, None, None, None) != 0 and b"float32" in L.cz_last_error(h)
+    assert L.cz_observe_device_f32(h, 0, 8, None) != 0 and b"null" in L.cz_last_error(h)
+    assert L.cz_obs_table_f32(h, None) != 0
+    # both outputs set, in either order, and per call
+    env.set_f32_output(rows)
+    with pytest.raises(_native.NativeError, match="float32 output is set"):
+        env.set_compact_output(d_codes)
+    with pytest.raises(_native.NativeError, match="both set"):
+        env.step_device_compact(d_act, d_codes, None, None, None)
+    # a float64 buffer with the setting on
+    with pytest.raises(_native.NativeError, match="d_obs = NULL"):
+        env.step_device(d_act, d_obs, None, None, None)
+    with pytest.raises(_native.NativeError, match="d_obs = NULL"):
+        env.step(np.zeros((8, 2), np.int32))
+    env.set_f32_output(None)
+    env.set_compact_output(d_codes)
+    with pytest.raises(_native.NativeError, match="compact output is set"):
+        env.set_f32_output(rows)
+    with pytest.raises(_native.NativeError, match="both set"):
+        env.step_device_f32(d_act, rows, None, None, None)
+    env.set_compact_output(None)
+    # nothing of the above stepped the batch or wrote a row, and everything works afterwards
+    assert (env.get_state()[:, soa.W_T] == 0).all() and (rows.rows() == SENTINEL).all()
+    env.step_device_f32(d_act, rows, None, None, None)
+    env.step_device(d_act, d_obs, None, None, None)
+    env.sync()
+    assert (env.get_state()[:, soa.W_T] == 2).all()
+    env.close()
+
+
+def test_host_step_with_the_float32_output_set():
+    """cz_step with return_obs=False and the setting on: the launch it issues writes the float32 rows"""
+    from oracle_binding import VecOracle
+    n, A = 64, 2
+    env = make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3")
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    orc.reset()
+    rows = GuardedRows(env)
+    env.set_f32_output(rows)
+    rng = np.random.default_rng(2)
+    for t in range(10):
+        acts = rng.integers(0, 5, size=(n, A), dtype=np.int32)
+        _, rg, tg, ug = env.step(acts, return_obs=False)
+        oo, ro, to, uo = orc.step(acts)
+        assert np.array_equal(rows.rows(), want32(oo)) and np.array_equal(bits64(rg), bits64(ro)) and np.array_equal(ug, uo), t
+    env.close()
+
+
+def test_two_shards_on_one_device_equal_one_handle():
+    from cooking_zoo_amd.sharded import ShardedVecEnv
+    n, A, T = 128, 2, 40
+    args = ("coop_test", "example", A, 25, ["TomatoLettuceSalad", "CarrotBanana"])
+    kw = dict(action_scheme="scheme3", num_layouts=8, auto_reset=True)
+    one = make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=25)
+    two = ShardedVecEnv(n, *args, device_ids=[0, 0], **kw)
+    one.reset(return_obs=False)
+    two.reset(return_obs=False)
+    assert np.array_equal(two.obs_table_f32().view(np.uint32), one.obs_table_f32().view(np.uint32))
+    F = one.F
+    o_act, o_rows = one.alloc((n, A), np.int32), one.alloc((n, A, F), np.float32)
+    o_out = [one.alloc((n, A), np.float64), one.alloc((n, A), np.uint8), one.alloc((n, A), np.uint8)]
+    s_act, s_rows = two.alloc((A,), np.int32), two.alloc((A, F), np.float32)
+    s_out = [two.alloc((A,), np.float64), two.alloc((A,), np.uint8), two.alloc((A,), np.uint8)]
+    one.observe_device(d_obs32=o_rows)
+    two.observe_device(d_obs32=s_rows)
+    one.sync()
+    two.sync()
+    assert np.array_equal(s_rows.to_host().view(np.uint32), o_rows.to_host().view(np.uint32))
+    rng = np.random.default_rng(6)
+    for t in range(T):
+        acts = rng.integers(0, 5, size=(n, A), dtype=np.int32)
+        o_act.from_host(acts)
+        s_act.from_host(acts)
+        if t < T // 2:
+            one.step_device_f32(o_act, o_rows, *o_out)
+            two.step_device_f32(s_act, s_rows, *s_out)
+        else:                                            # the second half through the handle setting
+            if t == T // 2:
+                one.set_f32_output(o_rows)
+                two.set_f32_output(s_rows)
+            one.step_device(o_act, None, *o_out)
+            two.step_device(s_act, None, *s_out)
+        one.sync()
+        two.sync()
+        assert np.array_equal(s_rows.to_host().view(np.uint32), o_rows.to_host().view(np.uint32)), t
+        for a, b in zip(s_out, o_out):
+            assert np.array_equal(a.to_host().view(np.uint8), b.to_host().view(np.uint8)), t
+    assert np.array_equal(strip(two.get_state()), strip(one.get_state()))
+    one.close()
+    two.close()
+
+
+def test_step_device_f32_captured_into_a_callers_graph_replays_bit_exact():
+    """[a host-prepared action ring -> cz_step_device_f32] x K captured with hipStreamBeginCapture on the caller's stream: replays do
+    what the same launches do eagerly on the twin, and capturing steps nothing"""
+    from test_gpu_capture import Hip
+    hip = Hip()
+    n, A, K, R = 512, 2, 8, 25
+    env, ref = (make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=25) for _ in range(2))
+    ring_host = np.random.default_rng(12).integers(0, 5, size=(K, n, A), dtype=np.int32)
+    bufs = []
+    for e in (env, ref):
+        e.reset(return_obs=False)
+        ring = e.alloc((K, n, A), np.int32)
+        ring.from_host(ring_host)
+        bufs.append(dict(ring=ring, rows=GuardedRows(e), rew=e.alloc((n, A), np.float64), term=e.alloc((n, A), np.uint8),
+                         trunc=e.alloc((n, A), np.uint8)))
+    be, br = bufs
+    stream = C.c_void_p()
+    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
+    env.set_stream(stream)
+    slot = lambda b, k: b["ring"].ptr + k * n * A * 4
+    graph, gexec = C.c_void_p(), C.c_void_p()
+    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
+    for k in range(K):
+        env.step_device_f32(slot(be, k), be["rows"], be["rew"], be["term"], be["trunc"])
+    env.observe_device(d_obs32=be["rows"])                         # (a pure launch as well; rewrites the rows it finds)
+    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
+    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    assert env._steps == 0 and env.captured_steps == K
+    assert (env.get_state()[:, soa.W_T] == 0).all(), "capturing must not have stepped anything"
+    for _ in range(R):
+        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
+    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    for _ in range(R):
+        for k in range(K):
+            ref.step_device_f32(slot(br, k), br["rows"], br["rew"], br["term"], br["trunc"])
+    ref.sync()
+    assert np.array_equal(env.get_state(), ref.get_state())
+    assert np.array_equal(be["rows"].rows(), br["rows"].rows()) and not (be["rows"].rows() == SENTINEL).any()
+    for k in ("rew", "term", "trunc"):
+        assert np.array_equal(be[k].to_host().view(np.uint8), br[k].to_host().view(np.uint8)), k
+    assert env.stats() == ref.stats() and env.stats()["episodes"] > n
+    hip.lib.hipGraphExecDestroy(gexec)
+    hip.lib.hipGraphDestroy(graph)
+    env.set_stream(None)
+    hip.lib.hipStreamDestroy(stream)
+    env.close()
+    ref.close()

@@ -56,7 +56,7 @@ def main():
     extra = sys.argv[1:]
     print("Register / LDS / scratch metadata of every kernel in the shipped library (hipcc " + " ".join(FLAGS[:2]) +
           ", ROCm 7.2;\nfields from the .amdgpu_metadata notes; `instr` = static instructions up to the first s_endpgm).  "
-          "k_step<OPL,CPL,NA,SCHEME,MODE>\n(MODE: the StepMode of cz_kernels.h, 0..5); k_step_lean<OPL,CPL,NA,SCHEME> is mode 0 with the handle's uniform "
+          "k_step<OPL,CPL,NA,SCHEME,MODE>\n(MODE: the StepMode of cz_kernels.h, 0..6); k_step_lean<OPL,CPL,NA,SCHEME> is mode 0 with the handle's uniform "
           "settings fixed at compile time and exists for the small instance only.\n")
     with tempfile.TemporaryDirectory() as tmp:
         for unit in UNITS:
