@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from test_gpu_f32_obs import GuardedRows, want32
 from test_gpu_rollout import bits, make, oracle_for, strip
 
 pytestmark = pytest.mark.gpu
@@ -178,6 +179,21 @@ def run_case(i, kw, seed, extra):
     assert np.array_equal(d_term.to_host()[0], to) and np.array_equal(d_trunc.to_host()[0], uo), ctx
     st = env.stats()
     assert st["episodes"] == int(orc.records[:, soa.W_EPISODE].sum()) + int((orc.records[:, soa.W_STATUS] & 1).sum()), ctx
+    # ... and one-step launches that write float32 rows (cz_step_device_f32: kernel mode 6), actions from a generator of their own
+    rng32 = np.random.default_rng(seed ^ 0xF32)
+    d_act32, rows = env.alloc((n, A), np.int32), GuardedRows(env)
+    o_rew, o_term, o_trunc = env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
+    for t in range(12):
+        acts = rng32.integers(0, n_act, size=(n, A), dtype=np.int32)
+        d_act32.from_host(acts)
+        rows.fill()
+        env.step_device_f32(d_act32, rows, o_rew, o_term, o_trunc)
+        env.sync()
+        oo, ro, to, uo = orc.step(acts)
+        assert np.array_equal(rows.rows(), want32(oo)), (ctx, "float32 rows", t)
+        assert np.array_equal(bits(o_rew.to_host()), bits(ro)), (ctx, "float32 step rewards", t)
+        assert np.array_equal(o_term.to_host(), to) and np.array_equal(o_trunc.to_host(), uo), (ctx, "float32 step flags", t)
+    assert np.array_equal(strip(env.get_state()), orc.records), (ctx, "records after the float32 steps")
     env.close()
 
 
@@ -276,6 +292,18 @@ def run_biased_case(i, kw, seed):
         assert np.array_equal(bits(o), bits(oo)) and np.array_equal(bits(r), bits(ro[0])), (ctx, "single step", t)
         assert np.array_equal(te, to[0]) and np.array_equal(tr, uo[0]), (ctx, "single step flags", t)
     assert np.array_equal(strip(env.get_state()), orc.records), ctx
+    d_act32, rows = env.alloc((n, A), np.int32), GuardedRows(env)          # one launch per step that writes float32 rows (mode 6)
+    o_rew, o_term, o_trunc = env.alloc((n, A), np.float64), env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
+    for t in range(12):
+        acts, oo, ro, to, uo = oracle_steps(1)
+        d_act32.from_host(acts[0])
+        rows.fill()
+        env.step_device_f32(d_act32, rows, o_rew, o_term, o_trunc)
+        env.sync()
+        assert np.array_equal(rows.rows(), want32(oo)), (ctx, "float32 rows", t)
+        assert np.array_equal(bits(o_rew.to_host()), bits(ro[0])), (ctx, "float32 step rewards", t)
+        assert np.array_equal(o_term.to_host(), to[0]) and np.array_equal(o_trunc.to_host(), uo[0]), (ctx, "float32 step flags", t)
+    assert np.array_equal(strip(env.get_state()), orc.records), (ctx, "records after the float32 steps")
     inst = instance_of(env.dims)
     for k in EVENTS:
         EVENT_TOTALS[k] += ev.counts[k]

@@ -167,13 +167,13 @@ def run_compact(env, acts, want, dn):
     return env.stats()
 
 
-@pytest.mark.parametrize("scheme", ["scheme3", "scheme1"])
-def test_one_world_on_every_instance(scheme):
-    n, T = 32, 200
+def one_world_trajectory(scheme, n, T):
+    """the coop_test world at its natural D = 12 under the state-aware policy, auto-resets included (max_steps 40): the dims, the
+    reset observation and records, the actions [T][n][A], per step (observation, rewards, terminations, truncations, records),
+    and the fewest episodes an env has finished"""
     base = make(n, scheme=scheme)
     dn = base.dims
     assert dn.D == 12
-    # the trajectory: the state-aware policy over the natural-D oracle, auto-resets included (max_steps 40)
     orc = VecOracle.from_vec_env(base)
     obs0 = orc.reset()
     rec0 = strip(orc.records)
@@ -183,9 +183,16 @@ def test_one_world_on_every_instance(scheme):
         acts.append(pol.act(orc.records))
         want.append(tuple(x.copy() for x in orc.step(acts[-1])) + (strip(orc.records),))
         pol.observe_result(orc.records)
-    acts = np.stack(acts)
-    assert int(orc.records[:, soa.W_EPISODE].min()) >= 3
     base.close()
+    return dn, obs0, rec0, np.stack(acts), want, int(orc.records[:, soa.W_EPISODE].min())
+
+
+@pytest.mark.parametrize("scheme", ["scheme3", "scheme1"])
+def test_one_world_on_every_instance(scheme):
+    n, T = 32, 200
+    # the trajectory: the state-aware policy over the natural-D oracle
+    dn, obs0, rec0, acts, want, episodes = one_world_trajectory(scheme, n, T)
+    assert episodes >= 3
     first = {}
     for D, inst in PADDED:
         for path, run in (("step_device", run_step_device), ("rollout_actions", run_rollout_actions), ("compact", run_compact)):

@@ -269,12 +269,14 @@ def dense_8x8():
 
 
 def example_capacity_metas():
-    """example.json with extra Tomato / Plate slots: F = 384, the last feature count of the lean one-step kernel, and F = 385,
-    the first one past it"""
+    """example.json with extra Tomato / Plate slots (F = 278 + 5 Tomato + 3 Plate): F = 384, the last feature count of the lean
+    one-step kernel, and F = 385, the first one past it; F = 512, a row that ends exactly on the second round of 256 features of
+    the four-features-per-lane forms (codes, float32 rows), and F = 513 | 515, whose third round holds one | three features"""
     with open(os.path.join(META_DIR, "example.json")) as f:
         base = json.load(f)
     out = {}
-    for name, tomato, plate in (("example_f384", 20, 2), ("example_f385", 19, 4)):
+    for name, tomato, plate in (("example_f384", 20, 2), ("example_f385", 19, 4),
+                                ("example_f512", 45, 3), ("example_f513", 47, 0), ("example_f515", 45, 4)):
         meta = [dict(e) for e in base]
         for e in meta:
             if "Tomato" in e:
