@@ -196,7 +196,8 @@ struct cz_handle_s {
     double *d_lut = nullptr;
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
-    float *obs32 = nullptr;            // cz_set_f32_output (or the one call of cz_step_device_f32): one-step launches write float32 rows here
+    uint8_t *codes = nullptr;          // cz_set_compact_output: one-step launches also write the compact observation here
+    float *obs32 = nullptr;            // cz_set_f32_output: one-step launches called with d_obs = NULL write float32 rows here
     void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
     void *d_dump = nullptr;            // [N][4] doubles: where a one-step launch writes an output array the caller passed as NULL
     // staging for the host-pointer API
@@ -204,7 +205,6 @@ struct cz_handle_s {
     double *d_obs = nullptr;
     char *d_small = nullptr, *h_small = nullptr;   // rewards | terminations | truncations | marks: one device block, one pinned block
     uint32_t *h_marks = nullptr, *d_marks_mapped = nullptr;   // pinned, device-mapped marks buffer of the direct path
-    uint32_t *marks_out_next = nullptr;            // (cz_step hands the kernel a marks buffer for one launch)
     std::vector<uint32_t> last_marks;          // recipe marks after the most recent cz_step (cz_last_marks)
     char *h_stage = nullptr, *d_stage = nullptr;   // small batches: pinned, device-mapped staging block of cz_step
     // cz_step_device_ring: which ring / output buffers / tables the cached graphs were captured for
@@ -1053,39 +1053,68 @@ static int ready(cz_handle h) {
     return 0;
 }
 
-// Which kernel a launch gets (the same table is in DESIGN.md section 4).  P.wt is decided by then.
+// What one call asks of a launch: its five buffers, the outputs it names beyond them and, for a fused launch, its span.  Nothing
+// call-specific travels through the handle: resolve_step below merges this with the handle's durable settings.
+struct StepCall {
+    const int32_t *actions; double *obs, *rewards; uint8_t *term, *trunc;
+    uint8_t *codes = nullptr;      // the compact observation (cz_step_device_compact, cz_step_compact, cz_rollout_compact)
+    float *obs32 = nullptr;        // float32 rows (cz_step_device_f32)
+    uint32_t *marks = nullptr;     // every env's recipe marks (the host step)
+    bool fused = false;            // T steps in one launch (the rollouts, fused ring runs); seed and step0 are theirs as well
+    int32_t T = 1; uint64_t seed = 0; uint32_t step0 = 0;
+};
+enum ObsForm { OBS_F64, OBS_CODES, OBS_F32 };      // what a launch writes its observation as (OBS_CODES: float64 rows beside the codes if P.obs)
+
+// The outputs of one launch, in the Params its kernel gets: what the call named, and - one-step launches only - the handle's durable
+// setting (cz_set_compact_output, cz_set_f32_output) where the call names no output of that kind.  The one place that refuses mixed
+// outputs (returns the message; nullptr = fine), and the one place that knows the float32 pointer travels in the slot Params::codes shares.
+static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsForm &form) {
+    uint8_t *const codes = c.fused || c.codes ? c.codes : h->codes;
+    float *const obs32 = c.fused ? nullptr : c.obs32 ? c.obs32 : h->obs32;
+    if (obs32) {        // the float32 rows stand in for the float64 ones and exclude the compact form (k_step<..., STEP_F32> writes nothing else)
+        if (codes) return "a float32 output (cz_set_f32_output / cz_step_device_f32) and a compact output (cz_set_compact_output / "
+                          "cz_step_device_compact) are both set: switch one of them off";
+        if (c.obs) return "float32 observation rows are switched on (cz_set_f32_output): pass d_obs = NULL, or switch them off "
+                          "with cz_set_f32_output(h, NULL) to get float64 rows";
+    }
+    form = obs32 ? OBS_F32 : codes ? OBS_CODES : OBS_F64;
+    P = h->P;
+    P.actions = c.actions; P.obs = c.obs; P.rewards = c.rewards; P.term = c.term; P.trunc = c.trunc; P.marks_out = c.marks;
+    P.T = c.T; P.seed = c.seed; P.step0 = c.step0;
+    if (obs32) P.obs32 = obs32; else P.codes = codes;
+    return nullptr;
+}
+
+// Which kernel a launch gets (the same table is in DESIGN.md section 4).  `form` is resolve_step's; P.wt is decided by then.
 //   fused, P.actions                  -> ROLLOUT_ACTIONS      (cz_rollout_actions, fused rings)
-//   fused, P.codes without P.obs      -> ROLLOUT_CODES_ONLY   (cz_rollout_compact)
-//   fused, P.codes and P.obs          -> ROLLOUT_CODES        (cz_rollout_compact)
+//   fused, OBS_CODES without P.obs    -> ROLLOUT_CODES_ONLY   (cz_rollout_compact)
+//   fused, OBS_CODES and P.obs        -> ROLLOUT_CODES        (cz_rollout_compact)
 //   fused, neither                    -> ROLLOUT              (cz_rollout)
-//   one step, f32 (the handle's       -> STEP_F32             (cz_step_device_f32, cz_set_f32_output; launch_step has refused P.obs or
-//     float32 buffer is set)                                  P.codes beside it and puts the buffer into the slot P.codes shares)
-//   one step, P.codes                 -> STEP_CODES           (cz_step_device_compact, cz_set_compact_output)
+//   one step, OBS_F32                 -> STEP_F32             (cz_step_device_f32, cz_set_f32_output; resolve_step has refused P.obs or codes beside it)
+//   one step, OBS_CODES               -> STEP_CODES           (cz_step_device_compact, cz_set_compact_output)
 //   one step otherwise                -> STEP, and of that the lean kernel when the handle allows it (CZ_LEAN), the instance has one and
 //                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
 //                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
 //   one step without P.actions        -> hipErrorInvalidValue
-static hipError_t choose_step(cz_handle h, const Params &P, bool fused, bool f32, StepChoice &c) {
+static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c) {
     c.lean = false;
-    if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : !P.codes ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
-    else c.mode = f32 ? STEP_F32 : P.codes ? STEP_CODES : STEP;
+    if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : form != OBS_CODES ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
+    else c.mode = form == OBS_F32 ? STEP_F32 : form == OBS_CODES ? STEP_CODES : STEP;
     if (c.mode == STEP)
         c.lean = h->lean_enabled && h->kl.has_lean && P.obs && !P.marks_out && !P.wide && !(P.auto_reset & 2) && P.F <= 128 * OBS_PAIRS && P.wt == 1;
     return !fused && !P.actions ? hipErrorInvalidValue : hipSuccess;
 }
 
-static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, bool fused = false) {
-    if ((P.auto_reset & 2) && h->spawn_layouts != h->n_layouts)
+static int launch_step(cz_handle h, const StepCall &call) {
+    if ((h->P.auto_reset & 2) && h->spawn_layouts != h->n_layouts)
         return fail(h, "despawn / respawn is on, but the layout pool was reloaded since cz_set_spawn (now %d layouts): call cz_set_spawn "
                        "again (it maps every layout to the level whose spawn areas it uses)", h->n_layouts);
-    if (!stream) stream = h->stream;
-    const bool f32 = !fused && h->obs32;
-    if (f32) {          // the float32 rows stand in for the float64 ones and exclude the compact form (k_step<..., STEP_F32> writes nothing else)
-        if (P.codes) return fail(h, "a float32 output (cz_set_f32_output / cz_step_device_f32) and a compact output (cz_set_compact_output / "
-                                    "cz_step_device_compact) are both set: switch one of them off");
-        if (P.obs) return fail(h, "float32 observation rows are switched on (cz_set_f32_output): pass d_obs = NULL, or switch them off "
-                                  "with cz_set_f32_output(h, NULL) to get float64 rows");
-    }
+    const hipStream_t stream = h->stream;
+    const bool fused = call.fused;
+    Params P;                 // built here, once, from the call and the handle: nothing of an earlier launch can be left in it
+    ObsForm form;
+    if (const char *refused = resolve_step(h, call, P, form)) return fail(h, "%s", refused);
+    const bool f32 = form == OBS_F32;
     // write-through observation stores pay when the launch is short enough for the end-of-kernel L2 write-back to be
     // exposed: one step of a batch of up to ~10 000 envs, whatever its rows weigh (round 6, profiles/r06/wt_sizes.txt: the 2.2 KB
     // rows of the 7x7 levels cross over between 10 240 and 12 288 envs - 43 / 52 MiB -, the 6.7 KB rows of large_16x16 are still
@@ -1121,18 +1150,10 @@ static int launch_step(cz_handle h, Params &P, hipStream_t stream = nullptr, boo
         HIPCHK(h, hipEventRecord(e0, stream));
     }
     StepChoice choice;
-    const hipError_t chosen = choose_step(h, P, fused, f32, choice);
+    const hipError_t chosen = choose_step(h, P, fused, form, choice);
     h->last_step_lean = choice.lean ? 1 : 0;
     HIPCHK(h, chosen);
-    if (f32) {
-        // the buffer goes into the slot P.codes shares, in a copy: callers launch the same P again and again (ring runs, _many), and a
-        // pointer left in their P would be taken for a compact output by the next launch's test above
-        Params Q = P;
-        Q.obs32 = h->obs32;
-        HIPCHK(h, h->kl.step(Q, stream, choice));
-    } else {
-        HIPCHK(h, h->kl.step(P, stream, choice));
-    }
+    HIPCHK(h, h->kl.step(P, stream, choice));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -1242,35 +1263,27 @@ static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, co
     if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
     return 0;
 }
-// the Params of one call: the handle's with the call's five buffers (one step; a rollout sets T, seed and step0 itself)
-static Params call_params(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
-    Params P = h->P;
-    P.actions = d_actions; P.obs = d_obs; P.rewards = d_rewards; P.term = d_term; P.trunc = d_trunc; P.T = 1;
-    return P;
-}
 
 extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term,
                               uint8_t *d_trunc) {
     if (begin_device_call(h, d_actions, "cz_step_device: actions pointer is null")) return 1;
-    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
-    P.marks_out = h->marks_out_next; h->marks_out_next = nullptr;
-    return launch_step(h, P);
+    return launch_step(h, StepCall{d_actions, d_obs, d_rewards, d_term, d_trunc});
 }
 
 // The step with the observation as one byte per feature (and, optionally, the float64 one beside it): see observe() in cz_kernels.h.
 extern "C" int cz_step_device_compact(cz_handle h, const int32_t *d_actions, uint8_t *d_codes, double *d_obs, double *d_rewards,
                                       uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, d_actions && d_codes, "cz_step_device_compact: actions and codes pointers must not be null")) return 1;
-    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
-    P.codes = d_codes;
-    return launch_step(h, P);
+    StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
+    c.codes = d_codes;
+    return launch_step(h, c);
 }
 // From now on EVERY one-step launch of the handle (cz_step_device, _many, _ring, cz_step) also writes the compact observation
 // to d_codes (uint8 [N][A][pitch]); NULL switches it off.  With d_obs = NULL in those calls the launches write codes only.
 extern "C" int cz_set_compact_output(cz_handle h, uint8_t *d_codes) {
     if (!h) return fail(nullptr, "null handle");
     if (d_codes && h->obs32) return fail(h, "cz_set_compact_output: a float32 output is set (cz_set_f32_output): switch it off first");
-    h->P.codes = d_codes;
+    h->codes = d_codes;
     h->tables_version++;                  // (graphs captured for the ring carry the pointer)
     return 0;
 }
@@ -1282,18 +1295,15 @@ extern "C" int32_t cz_codes_pitch(cz_handle h) { return h ? codes_pitch(h->P.F) 
 extern "C" int cz_step_device_f32(cz_handle h, const int32_t *d_actions, float *d_obs32, double *d_rewards, uint8_t *d_term,
                                   uint8_t *d_trunc) {
     if (begin_device_call(h, d_actions && d_obs32, "cz_step_device_f32: actions and float32 observation pointers must not be null")) return 1;
-    Params P = call_params(h, d_actions, nullptr, d_rewards, d_term, d_trunc);
-    float *const saved = h->obs32;
-    h->obs32 = d_obs32;               // for this one launch (cz_step_compact does the same with the codes)
-    const int rc = launch_step(h, P);
-    h->obs32 = saved;
-    return rc;
+    StepCall c{d_actions, nullptr, d_rewards, d_term, d_trunc};
+    c.obs32 = d_obs32;
+    return launch_step(h, c);
 }
 // From now on EVERY one-step launch of the handle (cz_step_device, _many, _ring, cz_step) called with d_obs = NULL writes the
-// float32 rows to d_obs32; NULL switches it off.  Excludes a compact output and a float64 buffer in those calls (launch_step says so).
+// float32 rows to d_obs32; NULL switches it off.  Excludes a compact output and a float64 buffer in those calls (resolve_step says so).
 extern "C" int cz_set_f32_output(cz_handle h, float *d_obs32) {
     if (!h) return fail(nullptr, "null handle");
-    if (d_obs32 && h->P.codes) return fail(h, "cz_set_f32_output: a compact output is set (cz_set_compact_output): switch it off first");
+    if (d_obs32 && h->codes) return fail(h, "cz_set_f32_output: a compact output is set (cz_set_compact_output): switch it off first");
     h->obs32 = d_obs32;
     h->tables_version++;                  // (graphs captured for the ring carry the pointer)
     return 0;
@@ -1330,19 +1340,19 @@ extern "C" int cz_obs_table(cz_handle h, double *table) {
 }
 extern "C" const void *cz_obs_table_device(cz_handle h) { return h ? (const void *)h->d_lut : nullptr; }
 
-static bool ring_fusable(cz_handle h, const Params &P, int32_t K, int64_t stride);
-static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot);
+static bool ring_fusable(cz_handle h, const StepCall &c, int32_t K, int64_t stride);
+static int launch_ring_fused(cz_handle h, const StepCall &c, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot);
 // K consecutive steps, one launch each, issued from C: step k reads actions d_actions + k * action_stride (int32 units,
 // wrapping every `action_period` steps) and overwrites the same output buffers.  Same work as K cz_step_device calls
 // without K trips through the host language.
 extern "C" int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_actions, int64_t action_stride, int32_t action_period,
                                    double *d_obs, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, d_actions && K >= 1 && action_period >= 1, "cz_step_device_many: bad arguments")) return 1;
-    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
-    if (ring_fusable(h, P, K, action_stride)) return launch_ring_fused(h, P, K, d_actions, action_stride, action_period, 0);   // cz_set_ring_fused
+    StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
+    if (ring_fusable(h, c, K, action_stride)) return launch_ring_fused(h, c, K, d_actions, action_stride, action_period, 0);   // cz_set_ring_fused
     for (int32_t k = 0; k < K; ++k) {
-        P.actions = d_actions + (int64_t)(k % action_period) * action_stride;
-        if (launch_step(h, P)) return 1;
+        c.actions = d_actions + (int64_t)(k % action_period) * action_stride;
+        if (launch_step(h, c)) return 1;
     }
     return 0;
 }
@@ -1357,13 +1367,13 @@ extern "C" int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_acti
 // pairs pays a capture each time -- keep the runs of a loop aligned.  Results are identical to cz_step_device_many.
 constexpr int RING_MAX_GRAPH = 256, RING_CACHE = 64;   // (rocprofv3 --kernel-trace aborts on replays of ~1000 kernel nodes: malformed AQL packet)
 // captures the launches of slots [slot, slot + len) (nothing executes) and instantiates them
-static int ring_capture(cz_handle h, Params &P, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &ge) {
+static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &ge) {
     hipGraph_t g = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     int bad = 0;
     for (int s = 0; s < len && !bad; ++s) {
-        P.actions = d_ring + (int64_t)(slot + s) * stride;
-        bad = launch_step(h, P);
+        c.actions = d_ring + (int64_t)(slot + s) * stride;
+        bad = launch_step(h, c);
     }
     const hipError_t ec = hipStreamEndCapture(h->stream, &g);
     if (bad) { if (g) (void)hipGraphDestroy(g); return 1; }
@@ -1389,7 +1399,7 @@ static bool ring_select(cz_handle h, const int32_t *d_ring, int64_t stride, int3
     return true;
 }
 // the graph of run [slot, slot + len), captured on first use
-static int ring_graph(cz_handle h, Params &P, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &out) {
+static int ring_graph(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &out) {
     h->ring_clock++;
     for (auto &r : h->ring_graphs)
         if (r.slot == slot && r.len == len) { r.used = h->ring_clock; out = r.ge; return 0; }
@@ -1402,18 +1412,22 @@ static int ring_graph(cz_handle h, Params &P, const int32_t *d_ring, int64_t str
         h->ring_graphs.erase(h->ring_graphs.begin() + (long)victim);
     }
     hipGraphExec_t ge = nullptr;
-    if (ring_capture(h, P, d_ring, stride, slot, len, ge)) return 1;
+    if (ring_capture(h, c, d_ring, stride, slot, len, ge)) return 1;
     h->ring_graphs.push_back({slot, len, ge, h->ring_clock});
     out = ge;
     return 0;
 }
 // cz_set_ring_fused: the run as fused launches over the ring's own action rows (cz_rollout_actions' kernel, every step's outputs
 // written in place), one launch per stretch of consecutive slots.  Needs densely packed slots (stride = num_envs * num_agents).
-static bool ring_fusable(cz_handle h, const Params &P, int32_t K, int64_t stride) {
-    return h->ring_fused && K >= 2 && !h->ktime && !P.codes && !h->obs32 && stride == (int64_t)P.N * P.A;
+// (and a run whose one-step launches would write float64 rows or none: the fused kernel has neither codes nor float32 rows in place)
+static bool ring_fusable(cz_handle h, const StepCall &c, int32_t K, int64_t stride) {
+    Params P;
+    ObsForm form;
+    return h->ring_fused && K >= 2 && !h->ktime && !resolve_step(h, c, P, form) && form == OBS_F64 && stride == (int64_t)h->P.N * h->P.A;
 }
-static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot) {
+static int launch_ring_fused(cz_handle h, const StepCall &c, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot) {
     // (the kernel addresses the action rows with 32-bit byte offsets from the first row of the launch)
+    const Params &P = h->P;
     const int64_t max_T = (int64_t)(0xFFFFFFFFull / ((uint64_t)P.N * (uint64_t)P.A * 4ull));
     if (max_T < 1) return fail(h, "fused ring run: one action row of %d envs x %d agents exceeds the 4 GiB the kernel addresses", P.N, P.A);
     int32_t k = 0;
@@ -1422,10 +1436,10 @@ static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d
         int64_t run = K - k;
         if (run > period - slot) run = period - slot;
         if (run > max_T) run = max_T;
-        Params Q = P;
-        Q.actions = d_ring + (int64_t)slot * stride;
-        Q.T = (int32_t)run; Q.seed = 0; Q.step0 = 1u;          // bit 0: outputs in place
-        if (launch_step(h, Q, nullptr, true)) return 1;
+        StepCall q = c;
+        q.actions = d_ring + (int64_t)slot * stride;
+        q.fused = true; q.T = (int32_t)run; q.seed = 0; q.step0 = 1u;          // bit 0: outputs in place
+        if (launch_step(h, q)) return 1;
         k += (int32_t)run;
     }
     h->n_ring_fused_steps += K;
@@ -1434,8 +1448,8 @@ static int launch_ring_fused(cz_handle h, Params &P, int32_t K, const int32_t *d
 // walks the run [first_slot, first_slot + K) piece by piece; launch = false only builds the graphs
 static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot, double *d_obs,
                      double *d_rewards, uint8_t *d_term, uint8_t *d_trunc, bool launch) {
-    Params P = call_params(h, d_ring, d_obs, d_rewards, d_term, d_trunc);
-    if (ring_fusable(h, P, K, stride)) return launch ? launch_ring_fused(h, P, K, d_ring, stride, period, first_slot) : 0;
+    StepCall c{d_ring, d_obs, d_rewards, d_term, d_trunc};
+    if (ring_fusable(h, c, K, stride)) return launch ? launch_ring_fused(h, c, K, d_ring, stride, period, first_slot) : 0;
     // (inside a capture of the caller: plain launches - a capture of the library's own cannot nest in it)
     const bool graphs = !caller_capturing(h) && ring_select(h, d_ring, stride, period, d_obs, d_rewards, d_term, d_trunc);
     int32_t k = 0;
@@ -1453,11 +1467,11 @@ static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stri
         const int32_t pre = k == 0 ? h->ring_prefix : 0;
         if (graphs && run >= h->graph_min_run + pre) {
             hipGraphExec_t ge = nullptr;
-            if (ring_graph(h, P, d_ring, stride, slot + pre, run - pre, ge)) return 1;
+            if (ring_graph(h, c, d_ring, stride, slot + pre, run - pre, ge)) return 1;
             if (launch) {
                 for (int32_t j = 0; j < pre; ++j) {
-                    P.actions = d_ring + (int64_t)(slot + j) * stride;
-                    if (launch_step(h, P)) return 1;
+                    c.actions = d_ring + (int64_t)(slot + j) * stride;
+                    if (launch_step(h, c)) return 1;
                 }
                 HIPCHK(h, hipGraphLaunch(ge, h->stream));
                 h->n_graph_kernels += run - pre;
@@ -1465,8 +1479,8 @@ static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stri
             }
         } else if (launch) {
             for (int32_t j = 0; j < run; ++j) {
-                P.actions = d_ring + (int64_t)(slot + j) * stride;
-                if (launch_step(h, P)) return 1;
+                c.actions = d_ring + (int64_t)(slot + j) * stride;
+                if (launch_step(h, c)) return 1;
             }
             h->n_direct_kernels += run;
         }
@@ -1517,9 +1531,9 @@ extern "C" int cz_launch_counts(cz_handle h, int64_t *graph_kernels, int64_t *di
 extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, double *d_obs, double *d_rewards,
                           uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1, "cz_rollout: T must be >= 1", "cz_rollout", T)) return 1;
-    Params P = call_params(h, nullptr, d_obs, d_rewards, d_term, d_trunc);
-    P.codes = nullptr; P.T = T; P.seed = seed; P.step0 = step0;
-    return launch_step(h, P, nullptr, true);
+    StepCall c{nullptr, d_obs, d_rewards, d_term, d_trunc};
+    c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    return launch_step(h, c);
 }
 
 // ... with a COMPACT trajectory: d_codes uint8 [T][N][A][cz_codes_pitch] (one byte per feature, see cz_step_device_compact) instead
@@ -1527,9 +1541,9 @@ extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0,
 extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, uint8_t *d_codes, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_codes, "cz_rollout_compact: T must be >= 1 and the codes pointer non-null", "cz_rollout_compact", T)) return 1;
-    Params P = call_params(h, nullptr, d_obs, d_rewards, d_term, d_trunc);
-    P.codes = d_codes; P.T = T; P.seed = seed; P.step0 = step0;
-    return launch_step(h, P, nullptr, true);
+    StepCall c{nullptr, d_obs, d_rewards, d_term, d_trunc};
+    c.codes = d_codes; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    return launch_step(h, c);
 }
 
 // The same fused launch over actions of the caller: d_actions int32 [T][N][A], step t of env e reads row t.  What replay and
@@ -1538,9 +1552,9 @@ extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_
 extern "C" int cz_rollout_actions(cz_handle h, int32_t T, const int32_t *d_actions, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_actions, "cz_rollout_actions: T must be >= 1 and the actions pointer non-null", "cz_rollout_actions", T)) return 1;
-    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
-    P.codes = nullptr; P.T = T; P.seed = 0; P.step0 = 0;
-    return launch_step(h, P, nullptr, true);
+    StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
+    c.fused = true; c.T = T;
+    return launch_step(h, c);
 }
 
 // the device address of pinned, device-mapped host memory (cz_host_alloc, hipHostMalloc, hipHostRegister); nullptr for
@@ -1554,20 +1568,12 @@ static void *mapped_device_pointer(const void *host) {
     return attr.type == hipMemoryTypeHost ? attr.devicePointer : nullptr;
 }
 
-// cz_step_device with the recipe marks of every env written to d_marks as well: armed for this one launch, whatever becomes of it
-static int step_device_with_marks(cz_handle h, uint32_t *d_marks, const int32_t *d_actions, double *d_obs, double *d_rewards,
-                                  uint8_t *d_term, uint8_t *d_trunc) {
-    h->marks_out_next = d_marks;
-    const int rc = cz_step_device(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
-    h->marks_out_next = nullptr;
-    return rc;
-}
-
-extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double *rewards, uint8_t *term, uint8_t *trunc) {
+// The host-pointer step: cz_step, and cz_step_compact with d_codes, the device's view of where the codes go.
+static int host_step(cz_handle h, const int32_t *actions, double *obs, uint8_t *d_codes, double *rewards, uint8_t *term, uint8_t *trunc) {
     if (ready(h)) return 1;
     if (!actions || !rewards || !term || !trunc) return fail(h, "cz_step: null buffer");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    const size_t NA = (size_t)h->P.N * h->P.A;
+    const size_t NA = (size_t)h->P.N * h->P.A, marks_words = 2 * (size_t)h->P.N;
     {   // host actions are checked here (the device-pointer entry points cannot look: their kernel reads action & 7)
         const int32_t n_actions = h->P.scheme == 3 ? 5 : 8;              // actions.py:17,50
         for (size_t i = 0; i < NA; ++i)
@@ -1576,6 +1582,26 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
                             i / (size_t)h->P.A, i % (size_t)h->P.A, n_actions);
     }
     const size_t ob = NA * h->P.F * 8;
+    // What the three transports below share.  Each says where its five buffers and its marks live; then: the launch (as cz_step_device
+    // begins and issues it, with the marks buffer), the staged transport's copies back (`staged` bytes of its device block), one
+    // synchronisation, the small outputs out of `small` - the CPU's view of the block they landed in, nullptr where the kernel wrote the
+    // caller's arrays - and the marks.
+    const auto run = [&](StepCall c, size_t staged, const char *small, size_t o_rew, size_t o_term, size_t o_trunc, const void *marks) -> int {
+        c.codes = d_codes;
+        if (begin_device_call(h, true, "") || launch_step(h, c)) return 1;
+        if (staged) {
+            HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, staged, hipMemcpyDeviceToHost, h->stream));
+            if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->d_obs, ob, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (small) {
+            memcpy(rewards, small + o_rew, NA * 8);
+            memcpy(term, small + o_term, NA);
+            memcpy(trunc, small + o_trunc, NA);
+        }
+        h->last_marks.assign((const uint32_t *)marks, (const uint32_t *)marks + marks_words);
+        return 0;
+    };
     // Small batches (the single-env facade): the step is pure latency, so the kernel reads the actions from and writes
     // its outputs to one pinned, device-mapped host block -- one launch and one synchronisation, no copy commands.
     const size_t o_act = 0, o_rew = (NA * 4 + 15) & ~(size_t)15, o_term = o_rew + NA * 8, o_trunc = o_term + ((NA + 15) & ~(size_t)15),
@@ -1587,16 +1613,11 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
             HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_stage, h->h_stage, 0));
         }
         memcpy(h->h_stage + o_act, actions, NA * 4);
-        if (step_device_with_marks(h, (uint32_t *)(h->d_stage + o_marks), (const int32_t *)(h->d_stage + o_act),
-                                   obs ? (double *)(h->d_stage + o_obs) : nullptr, (double *)(h->d_stage + o_rew),
-                                   (uint8_t *)(h->d_stage + o_term), (uint8_t *)(h->d_stage + o_trunc)))
-            return 1;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        StepCall c{(const int32_t *)(h->d_stage + o_act), obs ? (double *)(h->d_stage + o_obs) : nullptr, (double *)(h->d_stage + o_rew),
+                   (uint8_t *)(h->d_stage + o_term), (uint8_t *)(h->d_stage + o_trunc)};
+        c.marks = (uint32_t *)(h->d_stage + o_marks);
+        if (run(c, 0, h->h_stage, o_rew, o_term, o_trunc, h->h_stage + o_marks)) return 1;
         if (obs) memcpy(obs, h->h_stage + o_obs, ob);
-        memcpy(rewards, h->h_stage + o_rew, NA * 8);
-        memcpy(term, h->h_stage + o_term, NA);
-        memcpy(trunc, h->h_stage + o_trunc, NA);
-        h->last_marks.assign((const uint32_t *)(h->h_stage + o_marks), (const uint32_t *)(h->h_stage + o_marks) + 2 * (size_t)h->P.N);
         return 0;
     }
     // Buffers from cz_host_alloc (or any pinned, device-mapped host memory): the kernel reads the actions from and writes
@@ -1610,12 +1631,9 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
                 HIPCHK(h, hipHostMalloc((void **)&h->h_marks, (size_t)h->P.N * 8, hipHostMallocMapped));
                 HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_marks_mapped, h->h_marks, 0));
             }
-            if (step_device_with_marks(h, h->d_marks_mapped, (const int32_t *)d_act, (double *)d_obs, (double *)d_rew, (uint8_t *)d_term,
-                                       (uint8_t *)d_trunc))
-                return 1;
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            h->last_marks.assign(h->h_marks, h->h_marks + 2 * (size_t)h->P.N);
-            return 0;
+            StepCall c{(const int32_t *)d_act, (double *)d_obs, (double *)d_rew, (uint8_t *)d_term, (uint8_t *)d_trunc};
+            c.marks = h->d_marks_mapped;
+            return run(c, 0, nullptr, 0, 0, 0, h->h_marks);
         }
     }
     // Pageable buffers: staged copies.  The small outputs (rewards, flags, marks) live in one device block and come back
@@ -1629,17 +1647,12 @@ extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double 
     }
     if (obs && !h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, ob));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, NA * 4, hipMemcpyHostToDevice, h->stream));
-    if (step_device_with_marks(h, (uint32_t *)(h->d_small + s_marks), h->d_actions, obs ? h->d_obs : nullptr, (double *)(h->d_small + s_rew),
-                               (uint8_t *)(h->d_small + s_term), (uint8_t *)(h->d_small + s_trunc)))
-        return 1;
-    HIPCHK(h, hipMemcpyAsync(h->h_small, h->d_small, s_total, hipMemcpyDeviceToHost, h->stream));
-    if (obs) HIPCHK(h, hipMemcpyAsync(obs, h->d_obs, ob, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(rewards, h->h_small + s_rew, NA * 8);
-    memcpy(term, h->h_small + s_term, NA);
-    memcpy(trunc, h->h_small + s_trunc, NA);
-    h->last_marks.assign((const uint32_t *)(h->h_small + s_marks), (const uint32_t *)(h->h_small + s_marks) + 2 * (size_t)h->P.N);
-    return 0;
+    StepCall c{h->d_actions, obs ? h->d_obs : nullptr, (double *)(h->d_small + s_rew), (uint8_t *)(h->d_small + s_term), (uint8_t *)(h->d_small + s_trunc)};
+    c.marks = (uint32_t *)(h->d_small + s_marks);
+    return run(c, s_total, h->h_small, s_rew, s_term, s_trunc, h->h_small + s_marks);
+}
+extern "C" int cz_step(cz_handle h, const int32_t *actions, double *obs, double *rewards, uint8_t *term, uint8_t *trunc) {
+    return host_step(h, actions, obs, nullptr, rewards, term, trunc);
 }
 
 // The host-pointer step with the COMPACT observation instead of the float64 rows: codes uint8 [N][A][cz_codes_pitch] (see
@@ -1650,13 +1663,9 @@ extern "C" int cz_step_compact(cz_handle h, const int32_t *actions, uint8_t *cod
     if (!codes) return fail(h, "cz_step_compact: null codes buffer");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t bytes = (size_t)h->P.N * h->P.A * (size_t)codes_pitch(h->P.F);
-    uint8_t *const saved = h->P.codes;
     void *direct = mapped_device_pointer(codes);
     if (!direct && !h->d_codes_stage) HIPCHK(h, hipMalloc(&h->d_codes_stage, bytes));
-    h->P.codes = direct ? (uint8_t *)direct : (uint8_t *)h->d_codes_stage;
-    const int rc = cz_step(h, actions, nullptr, rewards, term, trunc);
-    h->P.codes = saved;
-    if (rc) return rc;
+    if (host_step(h, actions, nullptr, direct ? (uint8_t *)direct : (uint8_t *)h->d_codes_stage, rewards, term, trunc)) return 1;
     if (!direct) {
         HIPCHK(h, hipMemcpyAsync(codes, h->d_codes_stage, bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1693,7 +1702,7 @@ extern "C" int cz_probe_output_only(cz_handle h, void *d_dst, size_t bytes, int3
 // the closed loop of the two probes below: K x [one step, the policy's launch] captured into one HIP graph, which is replayed `reps` times
 // behind a warm-up replay; the average time per step (step + policy)
 template <class Policy>
-static int probe_closed_loop(cz_handle h, Params &P, int32_t K, int32_t reps, float *us_per_step, Policy &&policy) {
+static int probe_closed_loop(cz_handle h, const StepCall &c, int32_t K, int32_t reps, float *us_per_step, Policy &&policy) {
     const bool was_timing = h->ktime;
     h->ktime = false;
     hipGraph_t g = nullptr;
@@ -1701,7 +1710,7 @@ static int probe_closed_loop(cz_handle h, Params &P, int32_t K, int32_t reps, fl
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     int bad = 0;
     for (int k = 0; k < K && !bad; ++k) {
-        bad = launch_step(h, P);
+        bad = launch_step(h, c);
         if (!bad && !getenv("CZ_PROBE_NO_POLICY")) policy();
     }
     const hipError_t ec = hipStreamEndCapture(h->stream, &g);
@@ -1732,10 +1741,10 @@ extern "C" int cz_probe_closed_loop(cz_handle h, int32_t K, int32_t reps, int32_
     if (ready(h)) return 1;
     if (K < 1 || K > 1024 || reps < 1 || !d_actions || !d_obs || !us_per_step) return fail(h, "cz_probe_closed_loop: bad arguments");
     if (set_device(h)) return 1;
-    Params P = call_params(h, d_actions, d_obs, d_rewards, d_term, d_trunc);
+    const StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
     const int rows = h->P.N * h->P.A;
     const uint32_t n_actions = h->P.scheme == 3 ? 5u : 8u;
-    return probe_closed_loop(h, P, K, reps, us_per_step, [&] {
+    return probe_closed_loop(h, c, K, reps, us_per_step, [&] {
         hipLaunchKernelGGL(k_probe_policy, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_obs, d_actions, rows, h->P.F, n_actions);
     });
 }
@@ -1763,11 +1772,11 @@ extern "C" int cz_probe_closed_loop_compact(cz_handle h, int32_t K, int32_t reps
     if (ready(h)) return 1;
     if (K < 1 || K > 1024 || reps < 1 || !d_actions || !d_codes || !us_per_step) return fail(h, "cz_probe_closed_loop_compact: bad arguments");
     if (set_device(h)) return 1;
-    Params P = call_params(h, d_actions, nullptr, d_rewards, d_term, d_trunc);
-    P.codes = d_codes;
+    StepCall c{d_actions, nullptr, d_rewards, d_term, d_trunc};
+    c.codes = d_codes;
     const int rows = h->P.N * h->P.A;
     const uint32_t n_actions = h->P.scheme == 3 ? 5u : 8u;
-    return probe_closed_loop(h, P, K, reps, us_per_step, [&] {
+    return probe_closed_loop(h, c, K, reps, us_per_step, [&] {
         hipLaunchKernelGGL(k_probe_policy_codes, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, d_codes, h->d_lut, d_actions, rows,
                            h->P.F, codes_pitch(h->P.F), n_actions);
     });

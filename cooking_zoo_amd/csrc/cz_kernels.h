@@ -327,17 +327,11 @@ typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {                       // v_pk_sub_u16: two 16-bit lanes, no borrow across
     return __builtin_bit_cast(uint32_t, (ushort2_t)(__builtin_bit_cast(ushort2_t, a) - __builtin_bit_cast(ushort2_t, b)));
 }
-// LEAN (k_step_lean, see StepTraits): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
-// time - one chunk, no store-flavour switch, no descriptor reload.  F64 = false: the codes-only variant, which carries no float64 path.
-// F32 (STEP_F32, k_observe_f32): `out` is float[A][F] of this env - dense rows, no pitch - and `lut` the FLOAT32 table (256 floats: every
-// entry the float64 one rounded to nearest even), neither float64 rows nor codes.  Shaped like the codes path: a lane takes four adjacent
-// features per round of 256, one descriptor b128 load (`pre` holds the first rounds'), and one 16-byte store per observer whose range,
-// F * 4 bytes from the row's base, drops what lies past the row - nothing is written behind a row, there is no padding.
-template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false, bool F32 = false>
-__device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
-                                        const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
-                                        bool objs_changed = true, bool cells_changed = true, uint8_t *__restrict__ codes = nullptr /* [A][Fp] */,
-                                        CodesPrefetch *pre = nullptr) {
+// The LDS image of one env, which every form of the observation is gathered from: objects, cells, agents and the per-observer
+// subtrahend table, up to the wave barrier behind them.
+template <int OPL, int CPL, int NA>
+__device__ __forceinline__ void build_image(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s, uint32_t submask,
+                                            bool objs_changed, bool cells_changed) {
     uint32_t *img32 = reinterpret_cast<uint32_t *>(s.img);
     const uint32_t dead = (uint32_t)(LUT_ABSENT * 8) * 0x10001u;
     const uint32_t c01 = (uint32_t)((P.W - 1) * 8) | ((uint32_t)((LUT_Y0 + P.H - 1) * 8) << 16);
@@ -387,6 +381,70 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
         (&s.sub[0][0])[cx.lane] = (int)((q & 0xFFFFu) + (q >> 16));         // (rows of observers >= NA: never read)
     }
     __builtin_amdgcn_wave_barrier();             // one wave owns this LDS region: DS ops of a wave execute in order
+}
+
+// The float32 rows (STEP_F32, k_observe_f32) from the image build_image has made: `out32` is float[A][F] of this env - dense rows, no
+// pitch - and `lut` the FLOAT32 table (256 floats: every entry the float64 one rounded to nearest even).  Shaped like observe's codes
+// path: a lane takes four adjacent features per round of 256, one descriptor b128 load (`pre` holds the first rounds'), and one 16-byte
+// store per observer whose range, F * 4 bytes from the row's base, drops what lies past the row - nothing is written behind a row, there
+// is no padding.  P.wt selects the stores' cache policy as in observe.
+// (The descriptor / image / subtrahend gather is spelled out here and in observe's codes loop: moved into one helper of both, 32 of the
+// small instance's 76 instruction streams change and k_observe grows by 46 to 78 instructions.)
+template <int OPL, int CPL, int NA>
+__device__ __forceinline__ void write_rows_f32(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s, const float *lut,
+                                               float *__restrict__ out32 /* [A][F] of this env */, CodesPrefetch *pre) {
+    const char *lutb = reinterpret_cast<const char *>(lut);
+    const char *imgb = reinterpret_cast<const char *>(s.img);
+    const char *subb = reinterpret_cast<const char *>(s.sub);
+    decltype(__builtin_amdgcn_make_buffer_rsrc(out32, 0, 0, 0)) r32[NA];
+    // (a row starts wherever the rows before it end: 4-byte aligned when F is odd.  Buffer stores of several dwords need dword
+    // alignment only, and the range check works dword by dword - what the float64 rows of an odd F, 8-byte aligned, rely on too)
+#pragma unroll
+    for (int a = 0; a < NA; ++a) r32[a] = __builtin_amdgcn_make_buffer_rsrc(out32 + (size_t)a * (uint32_t)P.F, 0, P.F * 4, 0x00020000);
+    const uint32_t wt = (uint32_t)P.wt;                                              // wave-uniform
+    for (int f0 = 0; f0 < P.F; f0 += 256) {
+        const uint32_t f = (uint32_t)f0 + 4u * (uint32_t)cx.lane;                       // this lane's first feature
+        uint4_t d;
+        if (pre && f0 < 256 * CODES_PREFETCH) d = f0 == 0 ? pre->d[0] : pre->d[1];
+        else d = load_desc4(P, e.layout, f);
+        const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
+        uint32_t b[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const uint16_t *>(imgb + (dw[k] & 0xFFFFu));
+        int sb[NA][4];
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sb[a][k] = *reinterpret_cast<const int32_t *>(subb + 64 * a + (dw[k] >> 16));
+        // image halfword - subtrahend: the byte offset into the float64 table (a multiple of 8); halved, into the float32 one
+        uint4_t v[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            uint32_t w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const uint32_t *>(lutb + (((int)b[k] - sb[a][k]) >> 1));
+            v[a].x = w[0]; v[a].y = w[1]; v[a].z = w[2]; v[a].w = w[3];
+        }
+#define CZ_OBS_WRITE_ROWS32(AUX)                                                                                             \
+    _Pragma("unroll") for (int a = 0; a < NA; ++a) __builtin_amdgcn_raw_buffer_store_b128(v[a], r32[a], f * 4u, 0, AUX)
+        if (wt == 1u) { CZ_OBS_WRITE_ROWS32(16); }          // sc1: write-through
+        else if (wt == 2u) { CZ_OBS_WRITE_ROWS32(2); }      // nt: streaming
+        else { CZ_OBS_WRITE_ROWS32(0); }
+#undef CZ_OBS_WRITE_ROWS32
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// LEAN (k_step_lean, see StepTraits): float64 rows present, write-through stores and F <= 128 * OBS_PAIRS, all known at compile
+// time - one chunk, no store-flavour switch, no descriptor reload.  F64 = false: the codes-only variant, which carries no float64 path.
+// (The codes loop and the float64 loop stay in this function: moved into functions of their own, 20 of the small instance's 76
+// instruction streams change by an instruction - k_reset, k_observe and some k_step<..., 3 / 5> among them.)
+template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false>
+__device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
+                                        const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
+                                        bool objs_changed = true, bool cells_changed = true, uint8_t *__restrict__ codes = nullptr /* [A][Fp] */,
+                                        CodesPrefetch *pre = nullptr) {
+    build_image<OPL, CPL, NA>(P, e, cx, s, submask, objs_changed, cells_changed);
     // One buffer resource per observer whose range is exactly that observer's row (F * 8 bytes): the per-lane offset
     // (feature index * 8) is range-checked by the hardware, dword by dword (the scalar offset would be part of that check,
     // so the row's base goes into the resource).  Features past F - whole pairs, or the second half of the last pair when
@@ -394,47 +452,6 @@ __device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA>
     const char *lutb = reinterpret_cast<const char *>(lut);
     const char *imgb = reinterpret_cast<const char *>(s.img);
     const char *subb = reinterpret_cast<const char *>(s.sub);
-    if constexpr (F32) {
-        float *const out32 = reinterpret_cast<float *>(out);
-        decltype(__builtin_amdgcn_make_buffer_rsrc(out32, 0, 0, 0)) r32[NA];
-        // (a row starts wherever the rows before it end: 4-byte aligned when F is odd.  Buffer stores of several dwords need dword
-        // alignment only, and the range check works dword by dword - what the float64 rows of an odd F, 8-byte aligned, rely on too)
-#pragma unroll
-        for (int a = 0; a < NA; ++a) r32[a] = __builtin_amdgcn_make_buffer_rsrc(out32 + (size_t)a * (uint32_t)P.F, 0, P.F * 4, 0x00020000);
-        const uint32_t wt = (uint32_t)P.wt;                                              // wave-uniform
-        for (int f0 = 0; f0 < P.F; f0 += 256) {
-            const uint32_t f = (uint32_t)f0 + 4u * (uint32_t)cx.lane;                       // this lane's first feature
-            uint4_t d;
-            if (pre && f0 < 256 * CODES_PREFETCH) d = f0 == 0 ? pre->d[0] : pre->d[1];
-            else d = load_desc4(P, e.layout, f);
-            const uint32_t dw[4] = {d.x, d.y, d.z, d.w};
-            uint32_t b[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const uint16_t *>(imgb + (dw[k] & 0xFFFFu));
-            int sb[NA][4];
-#pragma unroll
-            for (int a = 0; a < NA; ++a)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sb[a][k] = *reinterpret_cast<const int32_t *>(subb + 64 * a + (dw[k] >> 16));
-            // image halfword - subtrahend: the byte offset into the float64 table (a multiple of 8); halved, into the float32 one
-            uint4_t v[NA];
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                uint32_t w[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const uint32_t *>(lutb + (((int)b[k] - sb[a][k]) >> 1));
-                v[a].x = w[0]; v[a].y = w[1]; v[a].z = w[2]; v[a].w = w[3];
-            }
-#define CZ_OBS_WRITE_ROWS32(AUX)                                                                                             \
-    _Pragma("unroll") for (int a = 0; a < NA; ++a) __builtin_amdgcn_raw_buffer_store_b128(v[a], r32[a], f * 4u, 0, AUX)
-            if (wt == 1u) { CZ_OBS_WRITE_ROWS32(16); }          // sc1: write-through
-            else if (wt == 2u) { CZ_OBS_WRITE_ROWS32(2); }      // nt: streaming
-            else { CZ_OBS_WRITE_ROWS32(0); }
-#undef CZ_OBS_WRITE_ROWS32
-        }
-        __builtin_amdgcn_wave_barrier();
-        return;
-    }
     if (codes) {
         const int Fp = codes_pitch(P.F);
         decltype(__builtin_amdgcn_make_buffer_rsrc(codes, 0, 0, 0)) rc[NA];
@@ -802,7 +819,8 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     bool img_objs = true, img_cells = true;                 // which parts of the LDS image the next encode must rebuild
     // (STEP_F32: the same array holds the float32 table - every entry rounded to nearest even, v_cvt_f32_f64 in the default rounding
     // mode, which is what cz_obs_table_f32 hands the host - so the float32 form adds no load to the prologue)
-    if (V::f32) { if (threadIdx.x < (unsigned)LUT_SIZE) reinterpret_cast<float *>(lut)[threadIdx.x] = (float)lutv; }
+    float *const lutf = reinterpret_cast<float *>(lut);
+    if (V::f32) { if (threadIdx.x < (unsigned)LUT_SIZE) lutf[threadIdx.x] = (float)lutv; }
     else if (threadIdx.x < (unsigned)LUT_SIZE) lut[threadIdx.x] = lutv;
     __syncthreads();
     if (env_raw >= P.N) return;
@@ -927,7 +945,8 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         if constexpr (V::f32) {
             // (choose_step takes this variant only with a float32 buffer: the rows are written unconditionally)
             float *const obs_row = Pt.obs32 + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F);
-            observe<OPL, CPL, NA, false, false, true>(Pt, e, cx, lds, lut, dsc, submask, reinterpret_cast<double *>(obs_row), img_objs, img_cells, nullptr, &cpre);
+            build_image<OPL, CPL, NA>(Pt, e, cx, lds, submask, img_objs, img_cells);
+            write_rows_f32<OPL, CPL, NA>(Pt, e, cx, lds, lutf, obs_row, &cpre);
         } else if (V::lean || Pt.obs || V::codes) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
             uint8_t *const codes = V::codes ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
@@ -1053,9 +1072,8 @@ __global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_
     init_lds<CPL>(P, cx, lds);
     Env<OPL, CPL, NA> e;
     load_env(P, e, cx, P.state + (size_t)(env_begin + i) * P.RW);
-    uint32_t dsc[OBS_CHUNK] = {};
-    observe<OPL, CPL, NA, false, false, true>(P, e, cx, lds, reinterpret_cast<const double *>(lutf), dsc, load_submask(P, lane),
-                                              reinterpret_cast<double *>(obs_out + (size_t)i * NA * P.F));
+    build_image<OPL, CPL, NA>(P, e, cx, lds, load_submask(P, lane), true, true);
+    write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs_out + (size_t)i * NA * P.F, nullptr);
 }
 
 // launchers exported by each instantiation unit

@@ -393,3 +393,157 @@ def test_step_device_f32_captured_into_a_callers_graph_replays_bit_exact():
     hip.lib.hipStreamDestroy(stream)
     env.close()
     ref.close()
+
+
+BOTH_SET = ("a float32 output (cz_set_f32_output / cz_step_device_f32) and a compact output (cz_set_compact_output / "
+            "cz_step_device_compact) are both set: switch one of them off")
+PASS_NULL = ("float32 observation rows are switched on (cz_set_f32_output): pass d_obs = NULL, or switch them off "
+             "with cz_set_f32_output(h, NULL) to get float64 rows")
+
+
+class Guarded:
+    """a device array of `shape` with a sentinel in every element and GUARD more elements of it behind the last one"""
+    SENTINELS = {1: 0xA5, 4: SENTINEL, 8: 0x7FF8BEEF0BADF00D}
+
+    def __init__(self, env, shape, itemsize):
+        self.shape, self.words = shape, int(np.prod(shape))
+        self.dtype = {1: np.uint8, 4: np.uint32, 8: np.uint64}[itemsize]
+        self.sentinel = self.SENTINELS[itemsize]
+        self.buf = env.alloc((self.words + GUARD,), self.dtype)
+        self.ptr = self.buf.ptr
+        self.fill()
+
+    def fill(self):
+        self.buf.from_host(np.full(self.words + GUARD, self.sentinel, dtype=self.dtype))
+
+    def get(self):
+        got = self.buf.to_host()
+        assert (got[self.words:] == self.sentinel).all(), "a store went past the array's end"
+        return got[:self.words].reshape(self.shape)
+
+    def untouched(self):
+        return bool((self.buf.to_host() == self.sentinel).all())
+
+
+def test_every_call_writes_the_outputs_it_names_and_no_others():
+    """One handle, 9 envs (one full workgroup of 8 waves and a partial one) of the 7x7 two-agent level.  Every call form in turn -
+    cz_step_device_f32, cz_step_device_compact, cz_step + cz_last_marks, cz_step_compact, cz_step_device, a 3-step
+    cz_step_device_ring - first with no output set on the handle, then with cz_set_compact_output, then with cz_set_f32_output:
+    what a call names (its own buffers, and the handle's buffer where the form includes it) equals the oracle bit for bit, every
+    other buffer - the handle's one under a one-call form that excludes it, the one-call buffers under every later call - keeps its
+    sentinel, and the refused combinations fail with their messages, step nothing and leave the next call working."""
+    from oracle_binding import VecOracle
+    n, A, K = 9, 2, 3
+    env = make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=20)
+    assert (env.dims.W, env.dims.H) == (7, 7)
+    orc = VecOracle.from_vec_env(env)
+    env.reset(return_obs=False)
+    orc.reset()
+    F, Fp, table = env.F, env.codes_pitch, env.obs_table()
+    B = dict(call32=Guarded(env, (n, A, F), 4), set32=Guarded(env, (n, A, F), 4), call_codes=Guarded(env, (n, A, Fp), 1),
+             set_codes=Guarded(env, (n, A, Fp), 1), obs=Guarded(env, (n, A, F), 8), rew=Guarded(env, (n, A), 8),
+             term=Guarded(env, (n, A), 1), trunc=Guarded(env, (n, A), 1))
+    outs = (B["rew"], B["term"], B["trunc"])
+    d_act, d_ring = env.alloc((n, A), np.int32), env.alloc((K, n, A), np.int32)
+    rng = np.random.default_rng(31)
+    state = {"steps": 0}
+
+    def codes_ok(codes, oo):
+        return np.array_equal(bits64(table[codes[..., :F]]), bits64(oo)) and (codes[..., F:] == 255).all()
+
+    def expect(what, oracle, named, host=None):
+        """`named`: the device buffers the call wrote (all of rew / term / trunc with "outs"); `host`: what a host step returned"""
+        oo, ro, to, uo = oracle
+        for key in named:
+            if key in ("call32", "set32"):
+                assert np.array_equal(B[key].get(), want32(oo)), (what, key)
+            elif key in ("call_codes", "set_codes"):
+                assert codes_ok(B[key].get(), oo), (what, key)
+            elif key == "obs":
+                assert np.array_equal(B[key].get(), bits64(oo)), (what, key)
+            else:
+                assert key == "outs"
+                assert np.array_equal(B["rew"].get(), bits64(ro)) and np.array_equal(B["term"].get(), to) and np.array_equal(B["trunc"].get(), uo), what
+        written = set(named) - {"outs"} | ({"rew", "term", "trunc"} if "outs" in named else set())
+        for key, buf in B.items():
+            if key not in written:
+                assert buf.untouched(), (what, "wrote", key)
+            buf.fill()
+        if host is not None:
+            og, cg, rg, tg, ug = host
+            assert og is None or np.array_equal(bits64(og), bits64(oo)), what
+            assert cg is None or codes_ok(cg, oo), what
+            assert np.array_equal(bits64(rg), bits64(ro)) and np.array_equal(tg, to) and np.array_equal(ug, uo), what
+        state["steps"] += 1
+        assert np.array_equal(strip(env.get_state()), orc.records), what
+
+    def refused(what, message, call):
+        with pytest.raises(_native.NativeError) as err:
+            call()
+        assert message in str(err.value), what
+        env.sync()
+        assert all(buf.untouched() for buf in B.values()), what
+        assert np.array_equal(strip(env.get_state()), orc.records), what
+
+    def fresh():
+        acts = rng.integers(0, 5, size=(n, A), dtype=np.int32)
+        d_act.from_host(acts)
+        return acts
+
+    for setting in (None, "codes", "f32"):
+        env.set_compact_output(B["set_codes"] if setting == "codes" else None)
+        env.set_f32_output(B["set32"] if setting == "f32" else None)
+        durable = [] if setting is None else ["set_codes" if setting == "codes" else "set32"]
+        rows = None if setting == "f32" else B["obs"]           # the float64 buffer of the device calls: NULL under cz_set_f32_output
+        named_rows = [] if setting == "f32" else ["obs"]
+        for cycle in range(3):
+            what = (setting, cycle)
+            # cz_step_device_f32: its own rows and nothing else; refused beside a compact output of the handle
+            acts = fresh()
+            if setting == "codes":
+                refused(what, BOTH_SET, lambda: env.step_device_f32(d_act, B["call32"], *outs))
+            else:
+                env.step_device_f32(d_act, B["call32"], *outs)
+                env.sync()
+                expect((what, "f32"), orc.step(acts), ["call32", "outs"])
+            # cz_step_device_compact: its own codes (every other cycle with float64 rows beside them), not the handle's
+            acts = fresh()
+            beside = B["obs"] if cycle % 2 else None
+            if setting == "f32":
+                refused(what, BOTH_SET, lambda: env.step_device_compact(d_act, B["call_codes"], *outs, d_obs=beside))
+            else:
+                env.step_device_compact(d_act, B["call_codes"], *outs, d_obs=beside)
+                env.sync()
+                expect((what, "compact"), orc.step(acts), ["call_codes", "outs"] + (["obs"] if beside is not None else []))
+            # cz_step: host arrays, cz_last_marks, and the handle's output
+            acts = fresh()
+            if setting == "f32":
+                refused(what, PASS_NULL, lambda: env.step(acts))
+            og, rg, tg, ug = env.step(acts, return_obs=setting != "f32")
+            expect((what, "host"), orc.step(acts), durable, host=(og, None, rg, tg, ug))
+            marks = orc.records[:, soa.W_MARKS].astype(np.uint64) | (orc.records[:, soa.W_MARKS_HI].astype(np.uint64) << np.uint64(32))
+            assert np.array_equal(env.last_marks(), marks), what
+            # cz_step_compact: host codes, not the handle's
+            acts = fresh()
+            if setting == "f32":
+                refused(what, BOTH_SET, lambda: env.step_compact(acts))
+            else:
+                cg, rg, tg, ug = env.step_compact(acts)
+                expect((what, "host compact"), orc.step(acts), [], host=(None, cg, rg, tg, ug))
+            # cz_step_device: float64 rows (NULL, and refused otherwise, under cz_set_f32_output) and the handle's output
+            acts = fresh()
+            if setting == "f32":
+                refused(what, PASS_NULL, lambda: env.step_device(d_act, B["obs"], *outs))
+            env.step_device(d_act, rows, *outs)
+            env.sync()
+            expect((what, "device"), orc.step(acts), named_rows + durable + ["outs"])
+            # cz_step_device_ring, 3 steps: the last step's outputs
+            ring = rng.integers(0, 5, size=(K, n, A), dtype=np.int32)
+            d_ring.from_host(ring)
+            env.step_device_ring(K, d_ring, n * A, K, 0, rows, *outs)
+            env.sync()
+            for k in range(K - 1):
+                orc.step(ring[k], False)
+            expect((what, "ring"), orc.step(ring[K - 1]), named_rows + durable + ["outs"])
+    assert int(env.get_state()[:, soa.W_EPISODE].min()) >= 2 and state["steps"] >= 40         # reset passes were among the steps
+    env.close()
