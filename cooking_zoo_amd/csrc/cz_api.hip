@@ -235,6 +235,7 @@ struct cz_handle_s {
     int wt_override = -1;          // CZ_WT experiment switch, read once
     bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
     int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
+    int last_step_mode = -1;       // the StepMode of that launch (cz_diag_last_step_mode)
     bool huge = false;             // the 256-slot / 1024-cell instance (its own LDS image layout)
     int instance = 0;              // which kernel instance cz_create picked: 0 small, 1 large, 2 huge (cz_diag_instance)
     unsigned long long *tl_base = nullptr;   // timeline build: stamp buffer, its capacity in launches, launches so far
@@ -1152,6 +1153,7 @@ static int launch_step(cz_handle h, const StepCall &call) {
     StepChoice choice;
     const hipError_t chosen = choose_step(h, P, fused, form, choice);
     h->last_step_lean = choice.lean ? 1 : 0;
+    h->last_step_mode = choice.mode;
     HIPCHK(h, chosen);
     HIPCHK(h, h->kl.step(P, stream, choice));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
@@ -1330,6 +1332,8 @@ extern "C" int cz_obs_table_f32(cz_handle h, float *table) {
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_lean_step.py): 1 if the most recent step launch issued or captured by the
 // handle was the lean one-step kernel, 0 if another kernel, -1 before the first
 extern "C" int32_t cz_diag_last_step_lean(cz_handle h) { return h ? h->last_step_lean : -1; }
+// diagnostic, not part of cookingzoo.h (tests/test_gpu_kernel_matrix.py): the StepMode (cz_kernels.h) of that launch, -1 before the first
+extern "C" int32_t cz_diag_last_step_mode(cz_handle h) { return h ? h->last_step_mode : -1; }
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_instance_edges.py): the kernel instance the handle's launches use,
 // 0 small (Inst<1,1>), 1 large (Inst<2,4>), 2 huge (Inst<4,16>); -1 for a null handle
 extern "C" int32_t cz_diag_instance(cz_handle h) { return h ? h->instance : -1; }
