@@ -1059,7 +1059,7 @@ static int ready(cz_handle h) {
 struct StepCall {
     const int32_t *actions; double *obs, *rewards; uint8_t *term, *trunc;
     uint8_t *codes = nullptr;      // the compact observation (cz_step_device_compact, cz_step_compact, cz_rollout_compact)
-    float *obs32 = nullptr;        // float32 rows (cz_step_device_f32)
+    float *obs32 = nullptr;        // float32 rows (cz_step_device_f32) or, fused, the float32 trajectory (cz_rollout_f32, cz_rollout_actions_f32)
     uint32_t *marks = nullptr;     // every env's recipe marks (the host step)
     bool fused = false;            // T steps in one launch (the rollouts, fused ring runs); seed and step0 are theirs as well
     int32_t T = 1; uint64_t seed = 0; uint32_t step0 = 0;
@@ -1067,12 +1067,13 @@ struct StepCall {
 enum ObsForm { OBS_F64, OBS_CODES, OBS_F32 };      // what a launch writes its observation as (OBS_CODES: float64 rows beside the codes if P.obs)
 
 // The outputs of one launch, in the Params its kernel gets: what the call named, and - one-step launches only - the handle's durable
-// setting (cz_set_compact_output, cz_set_f32_output) where the call names no output of that kind.  The one place that refuses mixed
+// setting (cz_set_compact_output, cz_set_f32_output) where the call names no output of that kind (a fused launch writes what its call
+// names and nothing of the handle's settings).  The one place that refuses mixed
 // outputs (returns the message; nullptr = fine), and the one place that knows the float32 pointer travels in the slot Params::codes shares.
 static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsForm &form) {
     uint8_t *const codes = c.fused || c.codes ? c.codes : h->codes;
-    float *const obs32 = c.fused ? nullptr : c.obs32 ? c.obs32 : h->obs32;
-    if (obs32) {        // the float32 rows stand in for the float64 ones and exclude the compact form (k_step<..., STEP_F32> writes nothing else)
+    float *const obs32 = c.fused || c.obs32 ? c.obs32 : h->obs32;
+    if (obs32) {        // the float32 rows stand in for the float64 ones and exclude the compact form (the float32 kernels write nothing else)
         if (codes) return "a float32 output (cz_set_f32_output / cz_step_device_f32) and a compact output (cz_set_compact_output / "
                           "cz_step_device_compact) are both set: switch one of them off";
         if (c.obs) return "float32 observation rows are switched on (cz_set_f32_output): pass d_obs = NULL, or switch them off "
@@ -1087,6 +1088,8 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 }
 
 // Which kernel a launch gets (the same table is in DESIGN.md section 4).  `form` is resolve_step's; P.wt is decided by then.
+//   fused, OBS_F32 and P.actions      -> ROLLOUT_ACTIONS_F32  (cz_rollout_actions_f32)
+//   fused, OBS_F32                    -> ROLLOUT_F32          (cz_rollout_f32)
 //   fused, P.actions                  -> ROLLOUT_ACTIONS      (cz_rollout_actions, fused rings)
 //   fused, OBS_CODES without P.obs    -> ROLLOUT_CODES_ONLY   (cz_rollout_compact)
 //   fused, OBS_CODES and P.obs        -> ROLLOUT_CODES        (cz_rollout_compact)
@@ -1099,7 +1102,8 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 //   one step without P.actions        -> hipErrorInvalidValue
 static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c) {
     c.lean = false;
-    if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : form != OBS_CODES ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
+    if (fused && form == OBS_F32) c.mode = P.actions ? ROLLOUT_ACTIONS_F32 : ROLLOUT_F32;
+    else if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : form != OBS_CODES ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
     else c.mode = form == OBS_F32 ? STEP_F32 : form == OBS_CODES ? STEP_CODES : STEP;
     if (c.mode == STEP)
         c.lean = h->lean_enabled && h->kl.has_lean && P.obs && !P.marks_out && !P.wide && !(P.auto_reset & 2) && P.F <= 128 * OBS_PAIRS && P.wt == 1;
@@ -1128,7 +1132,9 @@ static int launch_step(cz_handle h, const StepCall &call) {
     if (!fused) P.wt = obs_bytes > ((size_t)224 << 20) ? 2 : P.N <= 10240 ? 1 : 0;
     // (fused: streaming stores only when an agent's row fills whole DRAM pages - 4 KiB and more, config 5: +8 %; with the
     // 2.2 KB rows of the 7x7 levels they lose 15 % against the cache's own write-back order, profiles/r03/wt_ab2.txt)
-    else P.wt = (obs_bytes > ((size_t)224 << 20) && (size_t)P.F * 8 >= 4096) ? 2 : 0;
+    // A float32 trajectory (ROLLOUT_F32, ROLLOUT_ACTIONS_F32) takes the same rule with the row's real bytes, 4 F >= 4096.  Both
+    // figures were measured for float64 rows only: for float32 rows the fused rule is UNMEASURED as well.
+    else P.wt = (obs_bytes > ((size_t)224 << 20) && (size_t)P.F * (f32 ? 4 : 8) >= 4096) ? 2 : 0;
     if (h->wt_override >= 0) P.wt = h->wt_override;
     if (!fused) {             // the one-step kernels store rewards and flags unconditionally
         if (!P.rewards) P.rewards = (double *)h->d_dump;
@@ -1558,6 +1564,30 @@ extern "C" int cz_rollout_actions(cz_handle h, int32_t T, const int32_t *d_actio
     if (begin_device_call(h, T >= 1 && d_actions, "cz_rollout_actions: T must be >= 1 and the actions pointer non-null", "cz_rollout_actions", T)) return 1;
     StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
     c.fused = true; c.T = T;
+    return launch_step(h, c);
+}
+
+// The fused launch with the trajectory as FLOAT32 rows (cooking_env.py:243-269 T times, the observation of :352-373 in the dtype a
+// policy network takes): d_obs32 float [T][N][A][F], dense, every element np.float32 of the float64 feature as in cz_step_device_f32 -
+// k_step<..., ROLLOUT_F32>, which writes no other form of the observation.  State, statistics, rewards and flags are those cz_rollout
+// leaves from the same start; the handle's cz_set_compact_output / cz_set_f32_output settings are ignored, as by every rollout.
+extern "C" int cz_rollout_f32(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, float *d_obs32, double *d_rewards,
+                              uint8_t *d_term, uint8_t *d_trunc) {
+    if (begin_device_call(h, T >= 1 && d_obs32, "cz_rollout_f32: T must be >= 1 and the float32 trajectory pointer non-null (without one: "
+                                                "cz_rollout with d_obs = NULL)", "cz_rollout_f32", T)) return 1;
+    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
+    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    return launch_step(h, c);
+}
+// ... over actions of the caller (cooking_env.py:243-269 T times, :352-373): d_actions int32 [T][N][A] as for cz_rollout_actions, every
+// step's rows in row t of the trajectory (k_step<..., ROLLOUT_ACTIONS_F32>: there is no in-place form)
+extern "C" int cz_rollout_actions_f32(cz_handle h, int32_t T, const int32_t *d_actions, float *d_obs32, double *d_rewards,
+                                      uint8_t *d_term, uint8_t *d_trunc) {
+    if (begin_device_call(h, T >= 1 && d_actions && d_obs32, "cz_rollout_actions_f32: T must be >= 1 and the actions and float32 trajectory "
+                                                             "pointers non-null (without a trajectory: cz_rollout_actions with d_obs = NULL)",
+                          "cz_rollout_actions_f32", T)) return 1;
+    StepCall c{d_actions, nullptr, d_rewards, d_term, d_trunc};
+    c.obs32 = d_obs32; c.fused = true; c.T = T;
     return launch_step(h, c);
 }
 

@@ -67,7 +67,7 @@ struct Params {
     uint32_t *marks_out;           // [N] recipe-node marks after the step (host-pointer cz_step only), or nullptr
     union {                        // (one slot: a launch writes one of the two at most, and the block must not grow - see below)
         uint8_t *codes;            // [N][A][Fp] compact observation (cz_step_device_compact): one table index per feature, or nullptr
-        float *obs32;              // k_step<..., STEP_F32> only (resolve_step in cz_api.hip puts it here): [N][A][F] dense float32 rows
+        float *obs32;              // the float32 variants only (resolve_step in cz_api.hip puts it here): dense float32 rows [N][A][F], fused [T][N][A][F]
     };
     uint32_t *stat_u;              // [N][SU_WORDS]
     double *stat_f;                // [N][SF_WORDS]

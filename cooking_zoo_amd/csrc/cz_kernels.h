@@ -54,12 +54,17 @@ enum StepMode : int {
     ROLLOUT_CODES_ONLY = 5,   // the same without a float64 trajectory beside it
     STEP_F32 = 6,             // one step that writes the observation as dense float32 rows float[N][A][F] (cz_step_device_f32 / cz_set_f32_output)
                               // and nothing else: its own instance for the reason STEP_CODES is one
+    ROLLOUT_F32 = 7,          // P.T steps over the on-device action stream with a float32 trajectory float[T][N][A][F] and no other form of
+                              // the observation (cz_rollout_f32)
+    ROLLOUT_ACTIONS_F32 = 8,  // the same over the caller's actions [t][env][agent] (cz_rollout_actions_f32): its own instance for the reason
+                              // ROLLOUT_ACTIONS is one; always writes row t (the in-place form of fused ring runs is not offered in float32)
 };
 template <int MODE, bool LEAN = false>
 struct StepTraits {
-    static_assert(MODE >= STEP && MODE <= STEP_F32 && (!LEAN || MODE == STEP), "no such variant");
-    static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // P.T steps per launch
-    static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS;                         // a fused launch that reads the caller's actions
+    static_assert(MODE >= STEP && MODE <= ROLLOUT_ACTIONS_F32 && (!LEAN || MODE == STEP), "no such variant");
+    static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY ||
+                                  MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32;   // P.T steps per launch
+    static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_ACTIONS_F32;   // a fused launch that reads the caller's actions
     static constexpr bool codes = MODE == STEP_CODES || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // writes the compact observation
     // a fused rollout that writes codes ONLY (cz_rollout_compact without a float64 trajectory).  Without the float64 path - its six
     // descriptor registers, its encode - the codes' own descriptor words fit the registers for the whole launch (ROLLOUT_CODES reloads
@@ -67,8 +72,17 @@ struct StepTraits {
     static constexpr bool codes_only = MODE == ROLLOUT_CODES_ONLY;
     // the float32 rows: np.float32 of the float64 feature (round to nearest even), gathered from a float32 copy of the table that the
     // workgroup makes while it stages the table into LDS - no arithmetic on values, no float64 path beside it
-    static constexpr bool f32 = MODE == STEP_F32;
+    static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32;
     static constexpr bool f64 = !codes_only && !f32;                                     // carries the float64 observation path
+    // The CodesPrefetch words (the b128 descriptor loads of the codes and of the float32 rows): fetched once behind the prologue and held
+    // in registers - a fused launch fetches them again only when a reset pass has moved the env to another layout - or, desc_per_step,
+    // fetched at the top of every fused step.  The float32 rollouts hold them: held, no instance loses a wave per SIMD against
+    // ROLLOUT_CODES_ONLY (profiles/r14/README.md has the register counts of both forms; CZ_ROLLOUT_F32_HOLD=0 builds the other one).
+#ifndef CZ_ROLLOUT_F32_HOLD
+#define CZ_ROLLOUT_F32_HOLD 1
+#endif
+    static constexpr bool desc_held = (codes || f32) && (!fused || codes_only || (f32 && CZ_ROLLOUT_F32_HOLD != 0));
+    static constexpr bool desc_per_step = (codes || f32) && fused && !desc_held;
     // k_step_lean: the one-step kernel with the handle's uniform settings fixed at compile time - narrow recipe tables, no despawn /
     // respawn, float64 observations of at most 128 * OBS_PAIRS features with write-through stores, no compact output and no marks
     // buffer (choose_step in cz_api.hip picks it when all of that holds).  The code is the one-step kernel with those tests folded
@@ -817,8 +831,9 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     const int64_t env_global = P.env_id_base + env;
     bool cells_dirty = false, objs_dirty = false, header_dirty = V::fused;
     bool img_objs = true, img_cells = true;                 // which parts of the LDS image the next encode must rebuild
-    // (STEP_F32: the same array holds the float32 table - every entry rounded to nearest even, v_cvt_f32_f64 in the default rounding
-    // mode, which is what cz_obs_table_f32 hands the host - so the float32 form adds no load to the prologue)
+    // (the float32 variants - STEP_F32, ROLLOUT_F32, ROLLOUT_ACTIONS_F32: the same array holds the float32 table - every entry rounded to
+    // nearest even, v_cvt_f32_f64 in the default rounding mode, which is what cz_obs_table_f32 hands the host - so the float32 form adds
+    // no load to the prologue)
     float *const lutf = reinterpret_cast<float *>(lut);
     if (V::f32) { if (threadIdx.x < (unsigned)LUT_SIZE) lutf[threadIdx.x] = (float)lutv; }
     else if (threadIdx.x < (unsigned)LUT_SIZE) lut[threadIdx.x] = lutv;
@@ -831,7 +846,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     cpre.layout = e.layout;
     // (this fetch is spelled out at its three sites: behind a shared function - tried with and without the layout word - the code
     // variants come out with a few instructions more or fewer, and the shipped streams are kept instruction for instruction)
-    if ((V::codes || V::f32) && (!V::fused || V::codes_only)) {
+    if (V::desc_held) {
 #pragma unroll
         for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(P, e.layout, 256u * r + 4u * (uint32_t)lane);
     }
@@ -861,7 +876,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         } else {
             Pt = P;
         }
-        if (V::codes && V::fused && !V::codes_only) {
+        if (V::desc_per_step) {
             // (a fused rollout fetches the code descriptors again at the top of every step - hidden by the step's dynamics - instead
             // of holding eight more registers across the loop: with them the kernel no longer fits four waves per SIMD)
             cpre.layout = e.layout;
@@ -906,8 +921,9 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         // that T * N * A * 8 fits): the `global_store v, v_off, s[base]` form, no 64-bit per-lane address arithmetic.  The
         // one-step kernels store unconditionally - the host hands them a scratch row for an array the caller does not want.
         // (ROLLOUT_ACTIONS with P.step0 & 1 - cz_set_ring_fused: the steps of an action ring fused into one launch - writes every step's
-        // outputs to row `env`, like the one-step launches it stands in for; a wave's stores to one address keep their order)
-        const bool in_place = V::ext_actions && (Pt.step0 & 1u) != 0u;
+        // outputs to row `env`, like the one-step launches it stands in for; a wave's stores to one address keep their order.
+        // ROLLOUT_ACTIONS_F32 has no such form: it always writes row t)
+        const bool in_place = V::ext_actions && !V::f32 && (Pt.step0 & 1u) != 0u;
         const size_t row = V::fused ? ((size_t)(in_place ? 0 : t) * Pt.N + env) : (size_t)env;
         // (the compact path's descriptor words were fetched long ago; waiting for them HERE costs nothing, while behind the
         // stores below the same wait would also stand for those stores' acknowledgement - one counter for loads and stores)
@@ -943,10 +959,12 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         img_objs |= (dt.touched | dt.moved) != 0;
         img_cells |= dt.cells != 0;
         if constexpr (V::f32) {
-            // (choose_step takes this variant only with a float32 buffer: the rows are written unconditionally)
+            // (choose_step takes these variants only with a float32 buffer: the rows are written unconditionally.  Fused: row t * N + env of
+            // float[T][N][A][F], a 64-bit product like the float64 trajectory's, and the image is rebuilt where the step changed it)
             float *const obs_row = Pt.obs32 + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F);
             build_image<OPL, CPL, NA>(Pt, e, cx, lds, submask, img_objs, img_cells);
             write_rows_f32<OPL, CPL, NA>(Pt, e, cx, lds, lutf, obs_row, &cpre);
+            if (V::fused) { img_objs = false; img_cells = false; }
         } else if (V::lean || Pt.obs || V::codes) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
             uint8_t *const codes = V::codes ? Pt.codes + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * codes_pitch(Pt.F)) : nullptr;
@@ -1129,6 +1147,8 @@ struct Inst {
                 case ROLLOUT_CODES: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES>, P, st);
                 case ROLLOUT_CODES_ONLY: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_CODES_ONLY>, P, st);
                 case STEP_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_F32>, P, st);
+                case ROLLOUT_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_F32>, P, st);
+                case ROLLOUT_ACTIONS_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_ACTIONS_F32>, P, st);
                 }
                 return hipErrorInvalidValue;
             });

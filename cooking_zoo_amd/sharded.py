@@ -375,6 +375,15 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.rollout_actions(P(d_actions, i), T, P(d_obs, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))
 
+    def rollout_f32(self, T, seed, step0, d_obs32, d_rewards=None, d_term=None, d_trunc=None):
+        """`CookingVecEnv.rollout_f32` on every shard (d_obs32: a ShardedBuffer of float32 with leading = (T,))"""
+        P = self._part
+        self._each(lambda i, env: env.rollout_f32(T, seed, step0, P(d_obs32, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))
+
+    def rollout_actions_f32(self, d_actions, T, d_obs32, d_rewards=None, d_term=None, d_trunc=None):
+        P = self._part
+        self._each(lambda i, env: env.rollout_actions_f32(P(d_actions, i), T, P(d_obs32, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))
+
     def sync(self):
         self._each(lambda i, env: env.sync())
 

@@ -806,6 +806,23 @@ class CookingVecEnv:
                                                                 p(d_term), p(d_trunc)))
         self._issued(T)
 
+    def rollout_f32(self, T, seed, step0, d_obs32, d_rewards=None, d_term=None, d_trunc=None):
+        """`rollout` with the trajectory as float32: d_obs32 float32 [T, N, A, F], contiguous (e.g. a torch.float32 tensor of that
+        shape), receives np.float32 of every float64 feature bit for bit - half the bytes of the float64 trajectory and no
+        conversion pass behind it.  Rewards stay float64; state and statistics afterwards are those of `rollout`."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_rollout_f32(self._h, int(T), int(seed), int(step0), p(d_obs32), p(d_rewards),
+                                                            p(d_term), p(d_trunc)))
+        self._issued(T)
+
+    def rollout_actions_f32(self, d_actions, T, d_obs32, d_rewards=None, d_term=None, d_trunc=None):
+        """`rollout_actions` with the trajectory as float32 (d_obs32 float32 [T, N, A, F]): the same rows as T `step_device_f32` calls
+        over those action rows."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_rollout_actions_f32(self._h, int(T), p(d_actions), p(d_obs32), p(d_rewards),
+                                                                    p(d_term), p(d_trunc)))
+        self._issued(T)
+
     def sync(self):
         _native.check(self._h, _native.lib().cz_sync(self._h))
 

@@ -282,7 +282,8 @@ int cz_step_device_f32(cz_handle h, const int32_t *d_actions, float *d_obs32, do
  * launch (cz_step_device, _many, _ring, cz_step) called with d_obs = NULL writes the float32 rows to d_obs32; NULL switches it
  * off.  Refused: setting it while a compact output is set (and the reverse), and a one-step call with d_obs != NULL while it is
  * set.  Ring graphs built before the call are dropped; fused ring runs (cz_set_ring_fused) are issued as one-step launches
- * while it is set.  The fused rollouts (cz_rollout*) ignore it: their float32-sized form is the compact trajectory. */
+ * while it is set.  The fused rollouts (cz_rollout*) ignore it: their float32 trajectory is a call of its own (cz_rollout_f32,
+ * cz_rollout_actions_f32). */
 int cz_set_f32_output(cz_handle h, float *d_obs32);
 /* host mirror of the table those rows are gathered from (cooking_env.py:352-373: every feature is one of these values):
  * table[i] == (float)cz_obs_table[i], and d_obs32[e][a][f] == table[codes[e][a][f]] bit for bit. */
@@ -340,6 +341,21 @@ int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, ui
  * over those rows, with every step's outputs in the trajectory buffers. */
 int cz_rollout_actions(cz_handle h, int32_t T, const int32_t *d_actions, double *d_obs, double *d_rewards,
                        uint8_t *d_terminations, uint8_t *d_truncations);
+
+/* cz_rollout with the trajectory as FLOAT32 rows (cooking_env.py:243-269 T times, each step's observation - :271,352-373 - in the
+ * dtype a policy network takes): d_obs32 float [T][N][A][F], dense, every element (float) of the reference's float64 feature as in
+ * cz_step_device_f32 - half the bytes of the float64 trajectory, written once, no conversion or gather pass behind the launch.
+ * d_obs32 must not be NULL (without a trajectory: cz_rollout with d_obs = NULL).  Rewards stay float64; d_rewards and the flags
+ * [T][N][A] may each be NULL.  State, statistics, rewards and flags afterwards are bit for bit what cz_rollout leaves from the same
+ * start.  A pure launch on the handle's stream (legal inside a capture of the caller); ignores cz_set_compact_output /
+ * cz_set_f32_output like every rollout.  Same limit on T as cz_rollout (T * num_envs * num_agents * 8 below 4 GiB). */
+int cz_rollout_f32(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, float *d_obs32, double *d_rewards,
+                   uint8_t *d_terminations, uint8_t *d_truncations);
+/* ... and cz_rollout_actions likewise (cooking_env.py:243-269 T times over the caller's actions, :352-373): d_actions int32
+ * [T][N][A], step t reads row t and writes row t of d_obs32 float [T][N][A][F].  The same rows, rewards, flags, state and statistics
+ * as T cz_step_device_f32 launches over those action rows. */
+int cz_rollout_actions_f32(cz_handle h, int32_t T, const int32_t *d_actions, float *d_obs32, double *d_rewards,
+                           uint8_t *d_terminations, uint8_t *d_truncations);
 
 /* the action the on-device stream draws (host mirror, for parity tests) */
 uint32_t cz_action(uint64_t seed, int64_t env_global, int32_t agent, uint32_t step, uint32_t n_actions);
