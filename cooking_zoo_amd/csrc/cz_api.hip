@@ -196,6 +196,7 @@ struct cz_handle_s {
     double *d_lut = nullptr;
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
+    unsigned long long *d_reset_refused = nullptr;   // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
     uint8_t *codes = nullptr;          // cz_set_compact_output: one-step launches also write the compact observation here
     float *obs32 = nullptr;            // cz_set_f32_output: one-step launches called with d_obs = NULL write float32 rows here
     void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
@@ -275,7 +276,7 @@ static int fail(cz_handle h, const char *fmt, ...) {
 extern "C" const char *cz_last_error(cz_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 // Is the stream this handle's work goes to (a stream of the caller, cz_set_stream) being captured - hipStreamBeginCapture,
-// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*) are then pure
+// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*) and cz_reset_device are then pure
 // kernel launches: nothing that queries or synchronises (a staged layout update stays staged until the first call outside the
 // capture; no graphs of the library's own inside the caller's), so the capture stays valid and replays do what the launches did.
 static bool caller_capturing(cz_handle h) {
@@ -413,6 +414,8 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     CREATE_CHK(hipMalloc(&h->d_stats_out, sizeof(cz_stats)));
     CREATE_CHK(hipMalloc(&h->d_dump, N * MAX_AGENTS * sizeof(double)));
     CREATE_CHK(hipMalloc(&h->d_reset_words, N * 3 * sizeof(int32_t)));
+    CREATE_CHK(hipMalloc(&h->d_reset_refused, sizeof(unsigned long long)));
+    CREATE_CHK(hipMemsetAsync(h->d_reset_refused, 0, sizeof(unsigned long long), h->stream));
     CREATE_CHK(hipMalloc(&h->d_stats_part, (size_t)STAT_CHAINS * 16 * sizeof(unsigned long long)));
     CREATE_CHK(hipStreamSynchronize(h->stream));
     P.state = h->d_state; P.stat_u = h->d_stat_u; P.stat_f = h->d_stat_f;
@@ -480,7 +483,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1270,6 +1273,27 @@ static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, co
     if (set_device(h)) return 1;
     if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
     return 0;
+}
+
+// reset() of cooking_env.py:178-210 for chosen envs, decided and carried out on the device: one launch of k_reset_where over the whole
+// batch on the handle's stream - no copy, no query, no wait, so it is legal inside a capture of the caller; outside one a staged layout
+// update is flushed as by every device-pointer call.  The handle's cz_set_compact_output / cz_set_f32_output settings play no part:
+// the call writes the forms it names, rows of the restarted envs only (cooking_env.py:271,352-373), with plain stores.
+extern "C" int cz_reset_device(cz_handle h, const uint8_t *d_mask, const int32_t *d_layout_ids, double *d_obs, float *d_obs32,
+                               uint8_t *d_codes) {
+    if (begin_device_call(h, true, "")) return 1;
+    Params P = h->P;
+    P.wt = 0;
+    HIPCHK(h, h->kl.reset_where(P, h->stream, d_mask, d_layout_ids, d_obs, d_obs32, d_codes, h->d_reset_refused));
+    return 0;
+}
+// envs that cz_reset_device left alone since cz_create because their explicit layout id was >= the pool size (waits for the stream); -1 on error
+extern "C" int64_t cz_reset_device_refused(cz_handle h) {
+    if (!h) return -1;
+    unsigned long long n = 0;
+    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&n, h->d_reset_refused, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_reset_device_refused: copy failed"); return -1; }
+    return (int64_t)n;
 }
 
 extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term,

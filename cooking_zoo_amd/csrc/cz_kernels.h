@@ -1094,6 +1094,70 @@ __global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_
     write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs_out + (size_t)i * NA * P.F, nullptr);
 }
 
+// reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
+// when mask[e] != 0 or, without a mask, when its status word has the done bit - what the auto-reset pass of step_env does to such an
+// env, without spending a step.  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load,
+// before anything is staged, and strands no barrier.  A chosen env: episode + 1; the layout is layout_ids[e] when that is >= 0, else
+// the keyed draw of the auto-reset pass (same control words); an explicit id >= L is refused - the env stays as it was, `refused`
+// counts it.  Then k_reset's work - recipes and pool word are the old record's - and the rows of whichever forms were asked for, in
+// buffers laid out for the whole batch: rows e of the chosen envs only.  P.wt is 0 here (plain stores).
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_reset_where(const Params P, const uint8_t *__restrict__ mask, const int32_t *__restrict__ layout_ids,
+                                                    double *obs_out, float *obs32_out, uint8_t *codes_out, unsigned long long *refused) {
+    __shared__ Lds<CPL> lds;
+    __shared__ double lut[LUT_SIZE];
+    __shared__ float lutf[LUT_SIZE];
+    const uint32_t env = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    uint32_t *rec = P.state + (size_t)env * P.RW;
+    uint32_t old_status = 0u;
+    if (mask) {
+        if (rfl((uint32_t)mask[env]) == 0u) return;
+        old_status = rfl(rec[W_STATUS]);
+    } else {
+        old_status = rfl(rec[W_STATUS]);
+        if (!(old_status & ST_DONE)) return;
+    }
+    const int32_t want = layout_ids ? (int32_t)rfl((uint32_t)layout_ids[env]) : -1;
+    if (want >= P.L) {                                               // refused: nothing of the env or of its rows is touched
+        if (lane == 0) atomicAdd(refused, 1ull);
+        return;
+    }
+    // the old record's words, read before anything overwrites them
+    const uint32_t old_t = rfl(rec[W_T]), episode = rfl(rec[W_EPISODE]) + 1u, recipes = rfl(rec[W_RECIPES]), pool = rfl(rec[W_POOL]);
+    // an episode cut short: its steps stay counted as env-steps (k_count_aborted of cz_reset); a finished one was counted when it ended
+    if (!(old_status & ST_DONE) && lane == 0) P.stat_u[(size_t)env * SU_WORDS + SU_STEPS] += old_t;
+    uint32_t lay = (uint32_t)want;
+    if (want < 0) {
+        const uint32_t *ctl = P.lay_init - LAY_CTL_WORDS;
+        lay = next_layout(P.env_id_base + (int64_t)env, episode, pool, (uint32_t)P.L, rfl(ctl[LC_GROUPS]), rfl(ctl[LC_ACTIVE]));
+    }
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    init_lds<CPL>(P, cx, lds);
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, P.lay_init + (size_t)lay * P.RW);
+    e.t = 0; e.layout = lay; e.status = 0; e.episode = episode; e.recipes = recipes; e.pool = pool;
+    if (P.auto_reset & 2)
+        e.status = spawn_initial_status(rfl(reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET)->grace_period), NA);
+    uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
+    all_marks(P, e, cx, rowv, lds);
+    store_env(P, e, cx, rec, true, true);
+    if (lane < MAX_AGENTS) reinterpret_cast<double *>(rec + RET_WORD0)[lane] = 0.0;
+    const uint32_t submask = load_submask(P, lane);
+    if (obs_out || codes_out) {
+        if (obs_out) init_lut(P, lut, lane, 64);
+        uint32_t dsc[OBS_CHUNK];
+        load_desc(P, e.layout, 0, lane, dsc);
+        observe(P, e, cx, lds, lut, dsc, submask, obs_out ? obs_out + (size_t)env * NA * P.F : nullptr, true, true,
+                codes_out ? codes_out + (size_t)env * NA * codes_pitch(P.F) : nullptr);
+    }
+    if (obs32_out) {
+        for (int i = lane; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
+        if (!(obs_out || codes_out)) build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);      // (else observe has built it)
+        write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs32_out + (size_t)env * NA * P.F, nullptr);
+    }
+}
+
 // launchers exported by each instantiation unit
 struct StepChoice { StepMode mode; bool lean; };       // which variant a launch takes (choose_step, cz_api.hip)
 struct Launchers {
@@ -1103,6 +1167,8 @@ struct Launchers {
     hipError_t (*observe)(const Params &, hipStream_t, int64_t, int, double *, uint8_t *);
     bool has_lean;             // the instance carries the k_step_lean kernels
     hipError_t (*observe_f32)(const Params &, hipStream_t, int64_t, int, float *);
+    // k_reset_where over all P.N envs: mask, layout ids, float64 rows, float32 rows, codes, refused counter
+    hipError_t (*reset_where)(const Params &, hipStream_t, const uint8_t *, const int32_t *, double *, float *, uint8_t *, unsigned long long *);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1173,7 +1239,14 @@ struct Inst {
             return hipGetLastError();
         });
     }
-    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32}; }
+    static hipError_t reset_where(const Params &P, hipStream_t st, const uint8_t *mask, const int32_t *lay, double *obs, float *obs32,
+                                  uint8_t *codes, unsigned long long *refused) {
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_reset_where<OPL, CPL, decltype(na)::value>), dim3((unsigned)P.N), dim3(64), 0, st, P, mask, lay, obs, obs32, codes, refused);
+            return hipGetLastError();
+        });
+    }
+    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where}; }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

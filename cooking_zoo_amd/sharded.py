@@ -313,6 +313,16 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.observe_device(P(d_obs, i), P(d_codes, i), d_obs32=P(d_obs32, i)))
 
+    def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
+        """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids
+        int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""
+        P = self._part
+        self._each(lambda i, env: env.reset_device(P(d_mask, i), P(d_layout_ids, i), P(d_obs, i), P(d_obs32, i), P(d_codes, i)))
+
+    def reset_device_refused(self):
+        """envs `reset_device` refused (explicit layout id past the pool), summed over the local shards"""
+        return sum(self._each(lambda i, env: env.reset_device_refused()))
+
     def step_device_ring(self, K, d_ring, action_period, first_slot, d_obs, d_rewards, d_term, d_trunc):
         """K steps; step k reads slot (first_slot + k) % action_period of `d_ring` (ShardedBuffer with leading = (action_period,))"""
         P = self._part

@@ -742,6 +742,23 @@ class CookingVecEnv:
                                                                     p(d_trunc)))
         self._issued(1)
 
+    def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
+        """`reset()` (cooking_env.py:178-210) of chosen envs, decided on the device: one launch on the env's stream, no copy and no
+        wait, legal inside a capture, and no env-step is spent (unlike the auto-reset pass).  d_mask uint8 [N]: env e restarts when
+        d_mask[e] != 0, finished or not; None: every finished env.  d_layout_ids int32 [N]: the layout of env e where >= 0, else (or
+        None) the keyed draw auto-reset makes; an id past the pool is refused - the env stays as it was, `reset_device_refused`
+        counts it.  d_obs float64 [N, A, F], d_obs32 float32 [N, A, F], d_codes uint8 [N, A, codes_pitch]: whole-batch buffers of which
+        only the rows of the restarted envs are written.  Buffers as in `step_device`.  Not a step: layout rotation does not advance."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_reset_device(self._h, p(d_mask), p(d_layout_ids), p(d_obs), p(d_obs32), p(d_codes)))
+
+    def reset_device_refused(self):
+        """envs `reset_device` left alone because their explicit layout id was past the pool, since the env was created (waits)"""
+        n = int(_native.lib().cz_reset_device_refused(self._h))
+        if n < 0:
+            _native.check(self._h, 1)
+        return n
+
     def set_compact_output(self, d_codes=None):
         """every one-step launch from now on (step_device, step_device_ring, step) also writes the compact observation to d_codes
         (uint8 [N, A, codes_pitch]); None switches it off.  Pass d_obs=None to those calls for codes only."""

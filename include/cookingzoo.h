@@ -102,7 +102,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -219,6 +219,31 @@ int cz_get_state(cz_handle h, int64_t env_begin, int64_t env_count, uint32_t *re
  * fresh world (cooking_env.py:197-198) and, if obs != NULL (host, [env_count][A][F] float64), returns observe(). */
 int cz_reset(cz_handle h, int64_t env_begin, int64_t env_count, const int32_t *layout_ids,
              const uint8_t *recipe_ids, const uint32_t *pool_words, double *obs);
+
+/* reset() (cooking_env.py:178-210) for CHOSEN envs of the handle, decided and carried out on the device: every pointer is a device
+ * pointer, the call is ONE kernel launch on the handle's stream - no copy, no query, no wait; legal inside a stream capture - and
+ * takes no env-step, unlike the next-step auto-reset pass.  With auto_reset = 0 it is what un-freezes finished envs without a
+ * host round trip.
+ * Chosen: d_mask == NULL - every env whose status word has the done bit (what the auto-reset pass would restart); otherwise d_mask is
+ * uint8 [N] and env e is chosen when d_mask[e] != 0, finished or in mid-episode.
+ * A chosen env: episode += 1; its layout is d_layout_ids[e] when d_layout_ids != NULL and d_layout_ids[e] >= 0 (any slot of the
+ * pool, as in cz_reset), else the keyed draw of the auto-reset pass - cz_next_layout_group(env_id_base + e, new episode, the
+ * record's pool word, n_layouts, groups, active) with the layout-control words of cz_set_layout_group.  The rest is cz_reset's work:
+ * the record is the pool's init record, t = 0, status 0 (everybody present and the grace period running while despawn / respawn is
+ * on), recipe ids and pool word kept from the old record, the recipe marks evaluated on the fresh world (cooking_env.py:197-198),
+ * the running returns zeroed.
+ * An explicit layout id >= n_layouts is REFUSED: the env stays exactly as it was - no episode bump, no row - and a device counter is
+ * incremented; cz_reset_device_refused reads it (envs refused since cz_create; waits for the stream; -1 on error).
+ * Statistics: a chosen env that was not done adds its t to the env-step count, as cz_reset does (no episode is counted for it);
+ * cz_get_stats after this call equals cz_get_stats after cz_reset calls on the same envs.
+ * Outputs, each may be NULL and each is laid out for the WHOLE batch: d_obs float64 [N][A][F], d_obs32 float [N][A][F] (dense, the
+ * rounding of cz_step_device_f32), d_codes uint8 [N][A][cz_codes_pitch] (padding 255) - observe() (cooking_env.py:271,352-373) of
+ * the fresh world in rows e of the chosen, not refused envs; every other byte stays untouched, so after a step has written
+ * everyone's rows the call overwrites just the rows of the envs that restarted.  cz_set_compact_output / cz_set_f32_output are
+ * ignored, as the rollouts ignore them. */
+int cz_reset_device(cz_handle h, const uint8_t *d_mask, const int32_t *d_layout_ids,
+                    double *d_obs, float *d_obs32, uint8_t *d_codes);
+int64_t cz_reset_device_refused(cz_handle h);
 
 /* observe() (cooking_env.py:271,352-373) of the current state of envs [env_begin, env_begin+env_count):
  * host buffer [env_count][A][F] float64. */
