@@ -80,8 +80,9 @@ __global__ __launch_bounds__(256) void k_stats_tree(const unsigned long long *__
     }
 }
 
-// cz_reset_stats: zero the counters; steps already taken by episodes in flight must not be counted again
-__global__ void k_stats_clear(uint32_t *su, double *sf, const uint32_t *__restrict__ state, int RW, int N) {
+// cz_reset_stats: zero the counters, the last-episode row and what cz_episodes_collect has seen; steps already taken by episodes in
+// flight must not be counted again
+__global__ void k_stats_clear(uint32_t *su, double *sf, uint32_t *ep_seen, const uint32_t *__restrict__ state, int RW, int N) {
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     uint32_t *p = su + (size_t)e * SU_WORDS;
@@ -89,6 +90,90 @@ __global__ void k_stats_clear(uint32_t *su, double *sf, const uint32_t *__restri
     for (int j = 0; j < (int)SU_WORDS; ++j) p[j] = 0;
     p[SU_STEPS] = (rec[W_STATUS] & ST_DONE) ? 0u : (uint32_t)(-(int)rec[W_T]);
     for (int a = 0; a < 4; ++a) sf[(size_t)e * SF_WORDS + SF_SUM0 + a] = 0.0;
+    for (int a = 0; a < 4; ++a) sf[(size_t)e * SF_WORDS + SF_LAST0 + a] = 0.0;
+    ep_seen[e] = 0u;
+}
+
+// cz_episodes_collect: which envs finished an episode since the last collect (cooking_env.py:248,264,329 - the `episode` entries of
+// `infos` - for the whole batch).  Env e is found when its episode counter, stat_u[e][SU_EPISODES], differs from ep_seen[e], the
+// counter's value at the last collect; what is reported is the env's last-episode row, which the wave that ended the episode left in
+// stat_u / stat_f (step_kernel).  The packed list is in ascending env order by construction: a found env's rank is the number of found
+// envs in front of it - the blocks in front of its block (k_episodes_count's totals, added up in block order), the waves in front of
+// its wave, the lanes in front of its lane (ballot and prefix count).  No atomic decides an order.  The counter words and the row were
+// written by earlier launches: device-scope loads.
+constexpr int EP_BLOCK = 256;
+__device__ __forceinline__ uint32_t ep_load_u32(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double ep_load_f64(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// how many envs of each block are found: block_count[blockIdx.x] (launched only when a rank is needed: d_list or d_count)
+__global__ __launch_bounds__(EP_BLOCK) void k_episodes_count(const uint32_t *su, const uint32_t *ep_seen, int N, int32_t *block_count) {
+    __shared__ int32_t wave_count[EP_BLOCK / 64];
+    const int e = (int)blockIdx.x * EP_BLOCK + (int)threadIdx.x;
+    bool found = false;
+    if (e < N) found = ep_load_u32(su + (size_t)e * SU_WORDS + SU_EPISODES) != ep_load_u32(ep_seen + e);
+    const uint64_t b = ballot(found);
+    if ((threadIdx.x & 63u) == 0u) wave_count[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        int32_t n = 0;
+        for (int w = 0; w < EP_BLOCK / 64; ++w) n += wave_count[w];
+        block_count[blockIdx.x] = n;
+    }
+}
+// the outputs, and the mark.  block_count: null when neither the list nor the count was asked for.
+__global__ __launch_bounds__(EP_BLOCK) void k_episodes_collect(const uint32_t *su, const double *sf, uint32_t *ep_seen, int N, int A,
+                                                               int64_t env_id_base, const int32_t *block_count, uint8_t *mask,
+                                                               double *ret, int32_t *length, uint32_t *flags, cz_episode *list,
+                                                               int32_t capacity, int32_t *count) {
+    __shared__ int32_t wave_count[EP_BLOCK / 64];
+    __shared__ int32_t before, total;
+    const int e = (int)blockIdx.x * EP_BLOCK + (int)threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    if (threadIdx.x == 0u) { before = 0; total = 0; }
+    uint32_t episodes = 0u, seen = 0u;
+    if (e < N) {
+        episodes = ep_load_u32(su + (size_t)e * SU_WORDS + SU_EPISODES);
+        seen = ep_load_u32(ep_seen + e);
+    }
+    const bool found = episodes != seen;
+    const uint64_t b = ballot(found);
+    if (lane == 0) wave_count[wave] = __popcll(b);
+    __syncthreads();
+    int32_t rank = 0;
+    if (block_count) {
+        // found envs in the blocks in front of this one (and, block 0: in all of them) - integer sums, the same in any order
+        int32_t mine = 0, all = 0;
+        for (int j = (int)threadIdx.x; j < (int)gridDim.x; j += EP_BLOCK) {
+            const int32_t c = block_count[j];
+            all += c;
+            if (j < (int)blockIdx.x) mine += c;
+        }
+        if (mine) atomicAdd(&before, mine);
+        if (blockIdx.x == 0u && all) atomicAdd(&total, all);
+        __syncthreads();
+        rank = before;
+        for (int w = 0; w < wave; ++w) rank += wave_count[w];
+        rank += __popcll(b & ((1ull << lane) - 1ull));
+        if (count && blockIdx.x == 0u && threadIdx.x == 0u) *count = total;
+    }
+    if (e >= N) return;
+    if (mask) mask[e] = found ? (uint8_t)1 : (uint8_t)0;
+    if (!found) return;
+    ep_seen[e] = episodes;
+    const uint32_t *p = su + (size_t)e * SU_WORDS;
+    const double *q = sf + (size_t)e * SF_WORDS + SF_LAST0;
+    const uint32_t len = ep_load_u32(p + SU_LAST_LENGTH), fl = ep_load_u32(p + SU_LAST_FLAGS);
+    double r[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int a = 0; a < A; ++a) r[a] = ep_load_f64(q + a);
+    if (ret) for (int a = 0; a < A; ++a) ret[(size_t)e * A + a] = r[a];
+    if (length) length[e] = (int32_t)len;
+    if (flags) flags[e] = fl;
+    if (list && rank < capacity) {
+        cz_episode ep;
+        ep.env = env_id_base + e;
+        ep.episode = ep_load_u32(p + SU_LAST_EPISODE); ep.length = len; ep.flags = fl; ep.finished = episodes - seen;
+        for (int a = 0; a < 4; ++a) ep.ret[a] = r[a];
+        list[rank] = ep;
+    }
 }
 
 // cz_reset on envs whose episode is still running: their steps stay counted as env-steps
@@ -191,6 +276,8 @@ struct cz_handle_s {
     uint32_t spawn_bits = 5;               // width of the countdown fields the resident records are packed with (spawn_grace_bits)
     uint32_t *d_stat_u = nullptr;
     double *d_stat_f = nullptr;
+    uint32_t *d_ep_seen = nullptr;     // [N]: stat_u[e][SU_EPISODES] at the last cz_episodes_collect
+    int32_t *d_ep_blocks = nullptr;    // [ceil(N / EP_BLOCK)]: found envs per block, between the two launches of a collect
     cz_stats *d_stats_out = nullptr;
     unsigned long long *d_stats_part = nullptr;   // [256 chains][16 columns] between the two stages of the reduction
     double *d_lut = nullptr;
@@ -411,6 +498,9 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     CREATE_CHK(hipMalloc(&h->d_stat_f, N * SF_WORDS * 8));
     CREATE_CHK(hipMemsetAsync(h->d_stat_u, 0, N * SU_WORDS * 4, h->stream));
     CREATE_CHK(hipMemsetAsync(h->d_stat_f, 0, N * SF_WORDS * 8, h->stream));
+    CREATE_CHK(hipMalloc(&h->d_ep_seen, N * 4));
+    CREATE_CHK(hipMemsetAsync(h->d_ep_seen, 0, N * 4, h->stream));
+    CREATE_CHK(hipMalloc(&h->d_ep_blocks, ((N + EP_BLOCK - 1) / EP_BLOCK) * sizeof(int32_t)));
     CREATE_CHK(hipMalloc(&h->d_stats_out, sizeof(cz_stats)));
     CREATE_CHK(hipMalloc(&h->d_dump, N * MAX_AGENTS * sizeof(double)));
     CREATE_CHK(hipMalloc(&h->d_reset_words, N * 3 * sizeof(int32_t)));
@@ -483,7 +573,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1940,10 +2030,26 @@ extern "C" int cz_get_stats(cz_handle h, cz_stats *out) {
 extern "C" int cz_reset_stats(cz_handle h) {
     if (!h) return fail(nullptr, "null handle");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    hipLaunchKernelGGL(k_stats_clear, dim3((h->P.N + 255) / 256), dim3(256), 0, h->stream, h->d_stat_u, h->d_stat_f, h->d_state,
-                       h->P.RW, h->P.N);
+    hipLaunchKernelGGL(k_stats_clear, dim3((h->P.N + 255) / 256), dim3(256), 0, h->stream, h->d_stat_u, h->d_stat_f, h->d_ep_seen,
+                       h->d_state, h->P.RW, h->P.N);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The per-env episode records (cookingzoo.h; cooking_env.py:248,264,329): one launch, two when the packed list or the count is asked
+// for, on the handle's stream - no copy, no query, no wait, so the call is legal inside a capture of the caller.
+extern "C" int32_t cz_sizeof_episode(void) { return (int32_t)sizeof(cz_episode); }
+extern "C" int cz_episodes_collect(cz_handle h, uint8_t *d_mask, double *d_return, int32_t *d_length, uint32_t *d_flags,
+                                   cz_episode *d_list, int32_t capacity, int32_t *d_count) {
+    if (begin_device_call(h, capacity >= 0, "cz_episodes_collect: capacity is negative")) return 1;
+    const int N = h->P.N;
+    const dim3 grid((unsigned)((N + EP_BLOCK - 1) / EP_BLOCK)), block(EP_BLOCK);
+    const bool ranked = d_list || d_count;
+    if (ranked) hipLaunchKernelGGL(k_episodes_count, grid, block, 0, h->stream, h->d_stat_u, h->d_ep_seen, N, h->d_ep_blocks);
+    hipLaunchKernelGGL(k_episodes_collect, grid, block, 0, h->stream, h->d_stat_u, h->d_stat_f, h->d_ep_seen, N, h->P.A, h->P.env_id_base,
+                       ranked ? h->d_ep_blocks : nullptr, d_mask, d_return, d_length, d_flags, d_list, capacity, d_count);
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 

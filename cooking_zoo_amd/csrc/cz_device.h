@@ -52,8 +52,12 @@ constexpr int LUT_Y0 = 63, LUT_ZERO = 126, LUT_ONE = 127;
 // Everything else up to 255 is 0.0: the "absent" zone (entry 255 minus an agent coordinate stays inside 224..255).
 constexpr int LUT_NDONE0 = 128, LUT_CH0 = 132, LUT_MA0 = 136, LUT_CF0 = 140, LUT_OR0 = 144;
 // per-env statistics: u32 words and doubles
-enum : uint32_t { SU_EPISODES = 0, SU_STEPS, SU_LENSUM, SU_TRUNC, SU_TERM, SU_COMPLETED0, SU_WORDS = 16 };
-enum : uint32_t { SF_CUR0 = 0, SF_SUM0 = 4, SF_WORDS = 8 };
+// (words 9..11 and doubles 0..3: the env's last finished episode, overwritten by the wave that ends one - length, episode index, flags
+// and the return of every agent; k_episodes_collect reads them, nothing else does)
+enum : uint32_t { SU_EPISODES = 0, SU_STEPS, SU_LENSUM, SU_TRUNC, SU_TERM, SU_COMPLETED0, SU_LAST_LENGTH = 9, SU_LAST_EPISODE, SU_LAST_FLAGS,
+                  SU_WORDS = 16 };
+enum : uint32_t { SF_LAST0 = 0, SF_SUM0 = 4, SF_WORDS = 8 };
+static_assert(SU_COMPLETED0 + 4 <= SU_LAST_LENGTH, "the counters of four recipes end in front of the last-episode words");
 
 struct Params {
     uint32_t *state;               // [N][RW]

@@ -981,6 +981,14 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
                                  : lane == (int)SU_TERM ? (uint32_t)o.term : a_of < (uint32_t)NA ? root : 0u;
             if (lane < (int)SU_COMPLETED0 + NA && lane != (int)SU_STEPS) stg<uint32_t>(su, (uint32_t)lane * 4u, su_old + inc);
             if (lane < NA) stg<double>(sf, (uint32_t)(SF_SUM0 + lane) * 8u, sf_old + ret_done);
+            // the env's "last finished episode" row (cz_episodes_collect; cooking_env.py:248,264,329): plain overwrites of words no
+            // step reads - length, episode index, flags (bit 0 terminated, bit 1 truncated, bit 4 + a the root mark of recipe a) in
+            // the counters' free words, the per-agent returns in the doubles in front of the sums
+            const uint32_t roots = (uint32_t)(ballot(a_of < (uint32_t)NA && root != 0u) >> SU_COMPLETED0) & 0xFu;
+            const uint32_t last = lane == (int)SU_LAST_LENGTH ? e.t : lane == (int)SU_LAST_EPISODE ? e.episode
+                                  : (uint32_t)o.term | ((uint32_t)o.trunc << 1) | (roots << 4);
+            if (lane >= (int)SU_LAST_LENGTH && lane <= (int)SU_LAST_FLAGS) stg<uint32_t>(su, (uint32_t)lane * 4u, last);
+            if (lane < NA) stg<double>(sf, (uint32_t)(SF_LAST0 + lane) * 8u, ret_done);
         }
         CZ_STAMP(6);
     }

@@ -65,6 +65,13 @@ def plan_shards(num_envs: int, world_size: int, devices_per_process: int) -> Lis
     return [czd.shard_range(num_envs, G, g) for g in range(G)]
 
 
+def concat_episodes(parts: Sequence[np.ndarray]) -> np.ndarray:
+    """the shards' `finished_episodes()` arrays joined in shard order: shards own ascending ranges of global env ids and each
+    array is in env order, so the result is in global env order however the batch is cut"""
+    dt = np.dtype(_native.EPISODE_DTYPE)
+    return np.concatenate([np.asarray(p, dtype=dt) for p in parts]) if len(parts) else np.empty(0, dtype=dt)
+
+
 class ShardedVecEnv:
     def __init__(self, num_envs, level, meta_file, num_agents, max_steps, recipes, end_condition_all_dishes=False,
                  action_scheme="scheme1", reward_scheme=None, *, device_ids: Sequence[int] = (0,), world_size: int = 1, rank: int = 0,
@@ -318,6 +325,19 @@ class ShardedVecEnv:
         int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""
         P = self._part
         self._each(lambda i, env: env.reset_device(P(d_mask, i), P(d_layout_ids, i), P(d_obs, i), P(d_obs32, i), P(d_codes, i)))
+
+    def collect_episodes(self, d_mask=None, d_return=None, d_length=None, d_flags=None, d_list=None, capacity=0, d_count=None):
+        """`CookingVecEnv.collect_episodes` on every shard, one call each.  d_mask, d_return, d_length, d_flags: ShardedBuffers, cut
+        along the env axis like every other array of the batch.  The packed list has no env axis, so d_list and d_count are sequences
+        with one device buffer per local shard (`[env.alloc((capacity,), _native.EPISODE_DTYPE) for env in self.shards]`, and
+        `(1,)` int32 for the counts): every shard packs its own envs, under their GLOBAL ids, and shard order is global env order."""
+        P = self._part
+        self._each(lambda i, env: env.collect_episodes(P(d_mask, i), P(d_return, i), P(d_length, i), P(d_flags, i), P(d_list, i),
+                                                        capacity, P(d_count, i)))
+
+    def finished_episodes(self):
+        """`CookingVecEnv.finished_episodes` of every local shard, joined in shard order: global env order, whatever the cut"""
+        return concat_episodes(self._each(lambda i, env: env.finished_episodes()))
 
     def reset_device_refused(self):
         """envs `reset_device` refused (explicit layout id past the pool), summed over the local shards"""

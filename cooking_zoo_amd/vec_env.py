@@ -266,6 +266,7 @@ class CookingVecEnv:
         _native.check(self._h, L.cz_load_recipes(self._h, _ptr(self.recipe_table), len(self.book_names), self.recipe_nodes))
         self._upload_layouts()
         self._buffers = []
+        self._ep_bufs = None                  # finished_episodes: the packed list and the count
         self._steps = 0                       # env steps issued so far (every stepping method counts; `advance` adds replayed ones)
         self.captured_steps = 0               # steps captured into graphs of the caller (they run at replay, see `advance`)
         self._caller_stream, self._warned_capture = False, False
@@ -860,7 +861,34 @@ class CookingVecEnv:
         return st.as_dict()
 
     def reset_stats(self):
+        """zero the statistics; episodes no `collect_episodes` has reported yet are forgotten with them"""
         _native.check(self._h, _native.lib().cz_reset_stats(self._h))
+
+    def collect_episodes(self, d_mask=None, d_return=None, d_length=None, d_flags=None, d_list=None, capacity=0, d_count=None):
+        """Which envs finished an episode since the last collect - the `episode` / `_episode` entries of the reference's `infos`
+        (cooking_env.py:248,264,329) for the whole batch, on the device: stream-ordered launches, no copy and no wait, legal inside a
+        capture.  d_mask uint8 [N] (every byte written: 1 = finished); d_return float64 [N, A], d_length int32 [N], d_flags uint32 [N]
+        (bit 0 terminated, bit 1 truncated, bit 4 + a recipe a complete): rows of envs with mask 0 stay untouched.  d_list: `capacity`
+        entries of `_native.EPISODE_DTYPE` (56 bytes each), the same set packed in ascending env order, cut at `capacity`; d_count
+        int32 [1]: how many envs were found, also beyond `capacity`.  Everything is optional; every env found is marked seen, so a call
+        without buffers just marks.  An env that finished several episodes since the last collect reports the last one (`finished` in
+        the list says how many).  Buffers as in `step_device`."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_episodes_collect(self._h, p(d_mask), p(d_return), p(d_length), p(d_flags), p(d_list),
+                                                                 int(capacity) if d_list is not None else 0, p(d_count)))
+
+    def finished_episodes(self):
+        """host convenience: `collect_episodes` into buffers the env owns, a wait, and the episodes found as a numpy structured array
+        (`_native.EPISODE_DTYPE`: env - the GLOBAL id -, episode, length, flags, finished, ret[4]) in env order"""
+        if self._ep_bufs is None:
+            self._ep_bufs = (self.alloc((self.num_envs,), _native.EPISODE_DTYPE), self.alloc((1,), np.int32))
+        d_list, d_count = self._ep_bufs
+        self.collect_episodes(d_list=d_list, capacity=self.num_envs, d_count=d_count)
+        n = int(d_count.to_host()[0])                          # (cz_memcpy_d2h waits for the stream)
+        out = np.empty(n, dtype=np.dtype(_native.EPISODE_DTYPE))
+        if n:
+            _native.check(self._h, _native.lib().cz_memcpy_d2h(self._h, _ptr(out), d_list.ptr, out.nbytes))
+        return out
 
     def close(self):
         if getattr(self, "_rot", None) is not None:

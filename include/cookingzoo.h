@@ -82,6 +82,20 @@ typedef struct cz_stats {
     double return_sum[4];            /* per agent slot: sum of finished-episode returns */
 } cz_stats;
 
+/* The un-aggregated form: the last episode one env finished, as the reference reports it through `infos` at the step that ends an
+ * episode (cooking_env.py:248,264,329) - one entry of cz_episodes_collect's packed list. */
+typedef struct cz_episode {          /* cz_sizeof_episode() */
+    int64_t  env;                    /* GLOBAL env id (env_id_base + e) */
+    uint32_t episode;                /* index of the episode in its env (the record's episode word while it ran) */
+    uint32_t length;                 /* world steps of the episode */
+    uint32_t flags;                  /* bit 0 terminated; bit 1 truncated; bit 4 + a: recipe a was complete at the end */
+    uint32_t finished;               /* episodes this env finished since the last collect (>= 1; > 1: the ones before this one are not itemised) */
+    double   ret[4];                 /* per agent slot; slots >= A are 0.0 */
+} cz_episode;
+#define CZ_EPISODE_TERMINATED 1u
+#define CZ_EPISODE_TRUNCATED 2u
+#define CZ_EPISODE_ROOT0 16u         /* << a */
+
 /* ---- lifetime ------------------------------------------------------------------------------------- */
 int cz_create(const cz_config *cfg, cz_handle *out);
 int cz_destroy(cz_handle h);
@@ -90,6 +104,7 @@ int32_t cz_record_words(cz_handle h);
 int32_t cz_abi_version(void);
 int32_t cz_sizeof_config(void);                           /* sizeof(cz_config), for binding self-checks */
 int32_t cz_sizeof_stats(void);
+int32_t cz_sizeof_episode(void);                          /* sizeof(cz_episode) */
 int cz_debug_set_stamps(cz_handle h, void *d_buf);       /* diagnostic builds only (make prof): phase stamp buffer */
 /* timeline builds only (make timeline, tools/timeline.py): every step-kernel launch k writes two uint64 per env - entry and
  * exit time of the env's wave on the device-wide 100 MHz clock, with the hardware ids in the upper halves - to
@@ -102,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -424,7 +439,23 @@ int cz_probe_policy(cz_handle h, const double *d_obs, const uint8_t *d_codes, in
 
 /* ---- statistics + multi-GPU ------------------------------------------------------------------------- */
 int cz_get_stats(cz_handle h, cz_stats *out);              /* device reduction over this handle's envs */
-int cz_reset_stats(cz_handle h);
+int cz_reset_stats(cz_handle h);                           /* ... and forgets the episodes no cz_episodes_collect has reported yet */
+/* Which envs finished an episode since the last collect, with what return per agent, after how many steps, and how it ended: the
+ * `episode` / `_episode` entries of the reference's `infos` (cooking_env.py:248,264,329) for the whole batch, resident on the device.
+ * The wave that ends an episode keeps the env's last finished episode - every kernel, every mode, always; an episode cut short by
+ * cz_reset / cz_reset_device leaves nothing - and this call reports every env whose episode counter moved since the previous call:
+ *   d_mask   uint8  [N]     1 where an episode finished since the last collect, else 0 - every byte is written;
+ *   d_return double [N][A]  the return of every agent, the float64 sum of its rewards in step order, bit for bit;
+ *   d_length int32  [N]     world steps of the episode;
+ *   d_flags  uint32 [N]     cz_episode::flags.            Rows of envs with mask 0 stay untouched in these three;
+ *   d_list   cz_episode [capacity]  the same set packed in ascending env order (a function of the state alone: ballots and prefix
+ *            counts, no atomic append); entries whose rank is >= capacity are dropped from the list only;
+ *   d_count  int32  [1]     the number of envs found, also when it exceeds capacity.
+ * Every pointer is a device pointer and may be NULL; every env found is marked seen whatever the capacity is, so a call with all
+ * outputs NULL just marks.  An env that finished several episodes in between (a fused rollout) reports the last one and says how many
+ * in `finished`.  One or two kernel launches on the handle's stream: no copy, no query, no wait - legal inside a stream capture. */
+int cz_episodes_collect(cz_handle h, uint8_t *d_mask, double *d_return, int32_t *d_length, uint32_t *d_flags,
+                        cz_episode *d_list, int32_t capacity, int32_t *d_count);
 /* RCCL over xGMI: the only collective of the path is an all-gather of one cz_stats per rank. */
 int cz_comm_unique_id(uint8_t id[128]);
 int cz_comm_init(cz_handle h, int32_t n_ranks, int32_t rank, const uint8_t id[128]);
