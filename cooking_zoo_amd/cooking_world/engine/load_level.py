@@ -45,9 +45,15 @@ def level_max_dyn(level_object) -> int:
     return max(n, 1)          # the record always has at least one (possibly unused) slot
 
 
-def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layout:
+def instantiate(level_object, meta: dict, num_agents: int, rng=_random, stats=None) -> Layout:
     """One draw of the level (parsing.py:5-151).  `rng` defaults to the global `random` module,
-    like the reference; pass a `random.Random` to keep the global stream untouched."""
+    like the reference; pass a `random.Random` to keep the global stream untouched.
+    `stats` (a dict, optional) receives what the draw went through, also when it raises: `max_streak` the longest run of
+    rejected attempts of one object or agent, `far_edge` positions drawn on the far edge (x == width or y == height, which the
+    reference accepts and never finds a cell at), `static_optional_stops` static objects their OPTIONAL test left out."""
+    if stats is None:
+        stats = {}
+    stats.update(max_streak=0, far_edge=0, static_optional_stops=0)
     rows = level_object["LEVEL_LAYOUT"].splitlines()
     height = len(rows)
     width = len(rows[-1])
@@ -71,6 +77,8 @@ def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layou
         y = rng.sample(spec["Y_POSITION"], 1)[0]
         if x < 0 or y < 0 or x > width or y > height:
             raise ValueError(f"Position {x} {y} is out of bounds set by the level layout!")
+        if x == width or y == height:
+            stats["far_edge"] += 1
         return x, y
 
     # parse_static_objects (parsing.py:21-76): a static replaces the Counter or Floor at the drawn cell
@@ -81,6 +89,7 @@ def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layou
             time_out = 0
             while True:
                 if "OPTIONAL" in spec and spec["OPTIONAL"] <= rng.random():
+                    stats["static_optional_stops"] += 1
                     break
                 x, y = draw(spec)
                 here = cell_type.get((x, y))
@@ -91,6 +100,7 @@ def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layou
                     lists.setdefault(name, []).append((x, y))
                     break
                 time_out += 1
+                stats["max_streak"] = max(stats["max_streak"], time_out)
                 if time_out > 10000:
                     raise ValueError(f"Can't find valid position for object: {entry} in {time_out} steps")
 
@@ -113,6 +123,7 @@ def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layou
                     occupied.add((x, y))
                     break
                 time_out += 1
+                stats["max_streak"] = max(stats["max_streak"], time_out)
                 if time_out > 10000:
                     raise ValueError(f"Can't find valid position for object: {entry} in {time_out} steps")
 
@@ -136,6 +147,7 @@ def instantiate(level_object, meta: dict, num_agents: int, rng=_random) -> Layou
                     agents.append((int(x), int(y)))
                     break
                 time_out += 1
+                stats["max_streak"] = max(stats["max_streak"], time_out)
                 if time_out > 1000:
                     raise ValueError(f"Can't find valid position for agent: {agent_object} in {time_out} steps")
 

@@ -1457,6 +1457,23 @@ extern "C" int32_t cz_diag_last_step_mode(cz_handle h) { return h ? h->last_step
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_instance_edges.py): the kernel instance the handle's launches use,
 // 0 small (Inst<1,1>), 1 large (Inst<2,4>), 2 huge (Inst<4,16>); -1 for a null handle
 extern "C" int32_t cz_diag_instance(cz_handle h) { return h ? h->instance : -1; }
+// diagnostic, not part of cookingzoo.h (tests/test_gpu_layout_generate_matrix.py): rows [first, first + count) of the resident layout
+// pool as the device holds them - init records into `records` [count][record words], observation descriptors into `desc`
+// [count][feat_len] (either may be null) - after everything issued on the handle's stream so far.  Reads only.
+extern "C" int cz_diag_read_layout_pool(cz_handle h, int32_t first, int32_t count, uint32_t *records, uint32_t *desc) {
+    if (ready(h)) return 1;
+    if (!h->d_lay_init || !h->d_lay_desc) return fail(h, "cz_diag_read_layout_pool: no layout pool loaded");
+    if (first < 0 || count < 0 || (int64_t)first + count > h->n_layouts)
+        return fail(h, "cz_diag_read_layout_pool: slots [%d, %d) outside the resident pool of %d layouts", first, first + count, h->n_layouts);
+    if (count == 0) return 0;
+    if (set_device(h)) return 1;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (records)
+        HIPCHK(h, hipMemcpy(records, h->d_lay_init + (size_t)first * h->P.RW, (size_t)count * h->P.RW * 4, hipMemcpyDeviceToHost));
+    if (desc)
+        HIPCHK(h, hipMemcpy(desc, h->d_lay_desc + (size_t)first * h->P.F, (size_t)count * h->P.F * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int cz_obs_table(cz_handle h, double *table) {
     if (!h || !table) return fail(h, "cz_obs_table: null argument");
     memcpy(table, h->obs_table, sizeof h->obs_table);

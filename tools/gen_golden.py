@@ -1077,6 +1077,7 @@ def main():
     sets["api_traces"] = lambda: api_traces(args.out)
     sets["layouts_ref"] = lambda: layout_draws(args.out)
     sets["layouts_keyed_ref"] = lambda: layout_draws_keyed(args.out)
+    sets["layouts_keyed_stress_ref"] = lambda: layout_draws_keyed_stress(args.out)
     sets["aec_traces"] = lambda: aec_traces(args.out)
     sets["symbolic_traces"] = lambda: symbolic_traces(args.out)
     sets["custom_recipes"] = lambda: custom_recipes(args.out)          # (registers recipes in the reference: keep last)
@@ -1486,6 +1487,87 @@ def layout_draws_keyed(out_dir):
         json.dump(out, f, separators=(",", ":"))
     print(f"[golden] layouts_keyed_ref: {len(out)} levels x {len(keys)} keys, most draws {max(d['n_draws'] for c in out for d in c['draws'])}, "
           f"{os.path.getsize(path) / 1024:.0f} KiB")
+
+
+STRESS_SEED = 1717                      # tests/test_gpu_layout_generate_matrix.py draws its pools under this seed
+STRESS_LEVELS = [("stress_object_timeout", "meta_stress", None), ("stress_agent_timeout", "meta_stress", None),
+                 ("stress_second_switch", "meta_stress", None), ("stress_counter_overflow", "meta_stress_counter21", None),
+                 ("stress_slots", "meta_stress", 4), ("stress_meta_cap", "meta_stress", None)]          # (level, meta, max_dyn)
+
+
+def layout_draws_keyed_stress(out_dir):
+    """layout_draws_keyed over every shipped level at every agent count its meta file allows, and over the stress levels of
+    tests/levels/ (authored for the failure branches of cz_generate_layouts).  The same two patched random sources, the reference
+    otherwise unmodified.  Where the reference raises, the draw is recorded as {"raises": type, "message": first 60 characters,
+    "n_draws": draws taken until then} instead of a layout.  The keys lie in the pool ranges the device test redraws (seed
+    STRESS_SEED, generations 1 and 2, slots 64..95), plus the two keys with large fields of layout_draws_keyed; the stress levels
+    take 24 consecutive slots, so that failed and successful draws both occur.  Written gzipped, like the trace fixtures: the
+    Counter lists of the large levels make 1 MiB of JSON text."""
+    import gzip
+    from cooking_zoo.cooking_world.cooking_world import CookingWorld
+    from cooking_zoo.cooking_world.actions import ActionScheme3
+    from cooking_zoo_amd import spawn as czspawn
+    from cooking_zoo_amd.cooking_world.engine.level_program import LAYOUT_TAG
+    L = os.path.join(REPO, "cooking_zoo_amd", "utils", "level")
+    M = os.path.join(REPO, "cooking_zoo_amd", "utils", "meta_files")
+    T = os.path.join(REPO, "tests", "levels")
+    shipped = [("coop_test", "example"), ("coexistence_test", "example"), ("switch_test", "example"), ("crowded_6x5", "crowded_6x5"),
+               ("dense_8x8", "dense_8x8"), ("edge_8x8", "edge"), ("edge_9x8", "edge"), ("edge_empty", "edge"), ("limit_32x8", "limits"),
+               ("limit_8x31", "limits"), ("large_16x16", "large_16x16"), ("dense_16x16", "dense_16x16"),
+               ("huge_objs_16x16", "huge_objs_16x16"), ("huge_20x20", "huge_20x20"), ("huge_32x32", "huge_32x32")]
+    assert sorted(l for l, _ in shipped) == sorted(os.path.splitext(f)[0] for f in os.listdir(L))
+    big = [(0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF, 65534), ((1 << 40) + 17, 2, 200)]
+    keys = [(STRESS_SEED, 1, 64), (STRESS_SEED, 1, 65), (STRESS_SEED, 1, 80), (STRESS_SEED, 2, 66), (STRESS_SEED, 2, 67),
+            (STRESS_SEED, 2, 95)] + big
+    stress_keys = [(STRESS_SEED, 1, s) for s in range(64, 80)] + [(STRESS_SEED, 2, s) for s in range(80, 88)] + big
+    jobs = [(os.path.join(L, l + ".json"), os.path.join(M, m + ".json"), None, keys, False) for l, m in shipped]
+    jobs += [(os.path.join(T, l + ".json"), os.path.join(T, m + ".json"), d, stress_keys, True) for l, m, d in STRESS_LEVELS]
+    out = []
+    orig_random, orig_sample = random.random, random.sample
+    for level, meta, max_dyn, level_keys, stress in jobs:
+        with open(meta) as f:
+            max_agents = next(list(d.values())[0] for d in json.load(f) if "Agent" in d)
+        for A in range(1, max_agents + 1):
+            draws = []
+            for seed, generation, slot in level_keys:
+                st = {"n": 0}
+
+                def keyed_random():
+                    u = float(czspawn.uniform(seed, slot, generation, LAYOUT_TAG, st["n"]))
+                    st["n"] += 1
+                    return u
+
+                def keyed_sample(population, k):
+                    assert k == 1
+                    return [population[int(keyed_random() * len(population))]]
+
+                random.random, random.sample = keyed_random, keyed_sample
+                key = {"seed": seed, "generation": generation, "slot": slot}
+                try:
+                    w = CookingWorld(ActionScheme3, meta)
+                    w.load_level(level, A)
+                except Exception as exc:                                       # what the device counts as a failed draw
+                    draws.append({**key, "raises": type(exc).__name__, "message": str(exc)[:60], "n_draws": st["n"]})
+                    continue
+                finally:
+                    random.random, random.sample = orig_random, orig_sample
+                statics = {k: [[o.location[0], o.location[1]] for o in v] for k, v in w.world_objects.items()
+                           if issubclass(wo.StringToClass[k], StaticObject)}
+                dyn = [[k, [[o.location[0], o.location[1]] for o in v]] for k, v in w.world_objects.items()
+                       if issubclass(wo.StringToClass[k], DynamicObject) and v]
+                draws.append({**key, "n_draws": st["n"], "width": w.width, "height": w.height, "statics": statics, "dynamics": dyn,
+                              "agents": [[a.location[0], a.location[1]] for a in w.agents]})
+            case = {"level": os.path.splitext(os.path.basename(level))[0], "meta": os.path.splitext(os.path.basename(meta))[0],
+                    "num_agents": A, "stress": stress, "draws": draws}
+            if max_dyn is not None:
+                case["max_dyn"] = max_dyn
+            out.append(case)
+    path = os.path.join(out_dir, "layouts_keyed_stress_ref.json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        f.write(json.dumps(out, separators=(",", ":")).encode())
+    raised = sum("raises" in d for c in out for d in c["draws"])
+    print(f"[golden] layouts_keyed_stress_ref: {len(out)} cases, {sum(len(c['draws']) for c in out)} draws, {raised} raised, "
+          f"most draws {max(d['n_draws'] for c in out for d in c['draws'])}, {os.path.getsize(path) / 1024:.0f} KiB")
 
 
 if __name__ == "__main__":
