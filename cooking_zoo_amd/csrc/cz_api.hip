@@ -244,6 +244,25 @@ __global__ void k_count_aborted(uint32_t *su, const uint32_t *__restrict__ state
     if (!(rec[W_STATUS] & ST_DONE)) su[(size_t)(env_begin + i) * SU_WORDS + SU_STEPS] += rec[W_T];
 }
 
+// A record leaves the batch (cz_save_device): env e copies its RW words, the running-return words included, to row slot[e] of the
+// caller's archive uint32[capacity][RW] (no slot array: row e; the host has checked capacity >= N).  A negative slot skips the env, a
+// slot >= capacity writes nothing.  One wavefront per env and workgroup; nothing of the handle changes.  Two envs that name one row
+// race for it: the caller's contract.
+__global__ __launch_bounds__(64) void k_save_where(const uint32_t *__restrict__ state, int32_t RW, const int32_t *__restrict__ slot,
+                                                   uint32_t *__restrict__ records, int64_t capacity) {
+    const uint32_t env = blockIdx.x;
+    int64_t s = (int64_t)env;
+    if (slot) {
+        const int32_t v = (int32_t)rfl((uint32_t)slot[env]);
+        if (v < 0) return;
+        s = v;
+    }
+    if (s >= capacity) return;
+    const uint32_t *rec = state + (size_t)env * RW;
+    uint32_t *row = records + (size_t)s * RW;
+    for (uint32_t w = threadIdx.x; w < (uint32_t)RW; w += 64u) stg<uint32_t>(row, w * 4u, ldg<uint32_t>(rec, w * 4u));
+}
+
 // ======================================================================================================
 // host: handle + C-ABI
 // ======================================================================================================
@@ -284,6 +303,7 @@ struct cz_handle_s {
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
     unsigned long long *d_reset_refused = nullptr;   // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
+    unsigned long long *d_restore_refused = nullptr; // cz_restore_device: envs whose slot or row was refused (cz_restore_device_refused)
     uint8_t *codes = nullptr;          // cz_set_compact_output: one-step launches also write the compact observation here
     float *obs32 = nullptr;            // cz_set_f32_output: one-step launches called with d_obs = NULL write float32 rows here
     void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
@@ -363,7 +383,7 @@ static int fail(cz_handle h, const char *fmt, ...) {
 extern "C" const char *cz_last_error(cz_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 // Is the stream this handle's work goes to (a stream of the caller, cz_set_stream) being captured - hipStreamBeginCapture,
-// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*) and cz_reset_device are then pure
+// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*), cz_reset_device, cz_save_device and cz_restore_device are then pure
 // kernel launches: nothing that queries or synchronises (a staged layout update stays staged until the first call outside the
 // capture; no graphs of the library's own inside the caller's), so the capture stays valid and replays do what the launches did.
 static bool caller_capturing(cz_handle h) {
@@ -506,6 +526,8 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     CREATE_CHK(hipMalloc(&h->d_reset_words, N * 3 * sizeof(int32_t)));
     CREATE_CHK(hipMalloc(&h->d_reset_refused, sizeof(unsigned long long)));
     CREATE_CHK(hipMemsetAsync(h->d_reset_refused, 0, sizeof(unsigned long long), h->stream));
+    CREATE_CHK(hipMalloc(&h->d_restore_refused, sizeof(unsigned long long)));
+    CREATE_CHK(hipMemsetAsync(h->d_restore_refused, 0, sizeof(unsigned long long), h->stream));
     CREATE_CHK(hipMalloc(&h->d_stats_part, (size_t)STAT_CHAINS * 16 * sizeof(unsigned long long)));
     CREATE_CHK(hipStreamSynchronize(h->stream));
     P.state = h->d_state; P.stat_u = h->d_stat_u; P.stat_f = h->d_stat_f;
@@ -573,7 +595,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1383,6 +1405,42 @@ extern "C" int64_t cz_reset_device_refused(cz_handle h) {
     unsigned long long n = 0;
     if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
         hipMemcpy(&n, h->d_reset_refused, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_reset_device_refused: copy failed"); return -1; }
+    return (int64_t)n;
+}
+
+// An archive of records in device memory, owned by the caller: uint32 [capacity][RW].  cz_save_device gathers records out of the batch
+// (k_save_where), cz_restore_device scatters rows back in - many envs may take one row, the fork - and writes the restored envs' first
+// observation (k_restore_where).  Each is one launch on the handle's stream: no copy, no query, no wait, legal inside a capture of the
+// caller, and no step.  Without a slot array env e and row e belong together, and the archive must hold N rows: checked here, in front
+// of everything that needs the device.
+extern "C" int cz_save_device(cz_handle h, const int32_t *d_slot, uint32_t *d_records, int64_t capacity) {
+    if (!h) return fail(nullptr, "null handle");
+    if (!d_records || capacity < 0) return fail(h, "cz_save_device: the archive pointer is null or the capacity negative");
+    if (!d_slot && capacity < h->P.N) return fail(h, "cz_save_device: without slots the archive needs a row per env (capacity %lld < %d envs)", (long long)capacity, h->P.N);
+    if (begin_device_call(h, true, "")) return 1;
+    hipLaunchKernelGGL(k_save_where, dim3((unsigned)h->P.N), dim3(64), 0, h->stream, (const uint32_t *)h->d_state, h->P.RW, d_slot, d_records, capacity);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+// The handle's cz_set_compact_output / cz_set_f32_output settings play no part: the call writes the forms it names, rows of the
+// restored envs only (cooking_env.py:271,352-373), with plain stores.
+extern "C" int cz_restore_device(cz_handle h, const int32_t *d_slot, const uint32_t *d_records, int64_t capacity, double *d_obs,
+                                 float *d_obs32, uint8_t *d_codes) {
+    if (!h) return fail(nullptr, "null handle");
+    if (!d_records || capacity < 0) return fail(h, "cz_restore_device: the archive pointer is null or the capacity negative");
+    if (!d_slot && capacity < h->P.N) return fail(h, "cz_restore_device: without slots the archive needs a row per env (capacity %lld < %d envs)", (long long)capacity, h->P.N);
+    if (begin_device_call(h, true, "")) return 1;
+    Params P = h->P;
+    P.wt = 0;
+    HIPCHK(h, h->kl.restore_where(P, h->stream, d_slot, d_records, capacity, (uint32_t)h->n_recipes, d_obs, d_obs32, d_codes, h->d_restore_refused));
+    return 0;
+}
+// envs that cz_restore_device left alone since cz_create because their slot was >= capacity or their row failed cz_set_state's checks (waits for the stream); -1 on error
+extern "C" int64_t cz_restore_device_refused(cz_handle h) {
+    if (!h) return -1;
+    unsigned long long n = 0;
+    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&n, h->d_restore_refused, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_restore_device_refused: copy failed"); return -1; }
     return (int64_t)n;
 }
 

@@ -1166,6 +1166,88 @@ __global__ __launch_bounds__(64) void k_reset_where(const Params P, const uint8_
     }
 }
 
+// A record enters the batch (cz_restore_device): env e becomes row slot[e] of the caller's archive, word for word (no slot array:
+// row e; the host has checked capacity >= N); any number of envs may name one row.  One wavefront per env and workgroup: the wave of
+// an env whose slot is negative leaves behind one load, before anything is staged, and strands no barrier.  The row is read with
+// per-lane loads - the raw words (lane l: words l, l + 64, ...) and load_env's typed view of them, neither of which uses a word of
+// the row as an index - and then checked as cz_set_state checks a record on the host: layout id < L, each of the P.R recipe ids <
+// n_recipes, the pool slice inside the pool, no dead slot with a container tag (a ballot over the lanes that hold the slots).  A
+// slot >= capacity or a failing row is refused: the env and its rows stay as they were, `refused` counts it.  Otherwise the raw
+// words go to the env's record (byte-exact: store_env plays no part), lane 0 corrects SU_STEPS - plus the old record's t when that
+// episode was running (k_count_aborted's rule: its steps stay counted), minus the new record's t when this one is (k_stats_clear's
+// rule: steps that arrive already taken are not this handle's) - and the rows of whichever forms were asked for are written as
+// k_reset_where writes them, from the env load_env made of the row: the same words as the new record, but read from memory this
+// kernel does not write (load_env's header load goes through the scalar cache, which a store of this wave does not update).
+// The archive must not overlap the handle's own records.  P.wt is 0 here (plain stores).
+template <int OPL, int CPL>
+constexpr int record_chunks() { return ((CELL_WORD0 + 16 * CPL + 128 * OPL + 15) / 16 * 16 + 63) / 64; }   // 64-word chunks that cover the largest RW of the instance
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_restore_where(const Params P, const int32_t *__restrict__ slot, const uint32_t *__restrict__ records,
+                                                      int64_t capacity, uint32_t n_recipes, double *obs_out, float *obs32_out,
+                                                      uint8_t *codes_out, unsigned long long *refused) {
+    __shared__ Lds<CPL> lds;
+    __shared__ double lut[LUT_SIZE];
+    __shared__ float lutf[LUT_SIZE];
+    constexpr int NW = record_chunks<OPL, CPL>();
+    const uint32_t env = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    int64_t s = (int64_t)env;
+    if (slot) {
+        const int32_t v = (int32_t)rfl((uint32_t)slot[env]);
+        if (v < 0) return;
+        s = v;
+    }
+    if (s >= capacity) {                                             // refused: nothing of the env or of its rows is touched
+        if (lane == 0) atomicAdd(refused, 1ull);
+        return;
+    }
+    const uint32_t *row = records + (size_t)s * P.RW;
+    uint32_t *rec = P.state + (size_t)env * P.RW;
+    const uint32_t RW = (uint32_t)P.RW;
+    uint32_t raw[NW];
+#pragma unroll
+    for (int k = 0; k < NW; ++k) raw[k] = ldg<uint32_t>(row, min((uint32_t)lane + 64u * k, RW - 1u) * 4u);   // clamped, like load_env's
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, row);
+    // the checks of cz_set_state, before any of these words is an index
+    bool ok = e.layout < (uint32_t)P.L;
+    for (int k = 0; k < P.R; ++k) ok = ok && ((e.recipes >> (8 * k)) & 0xFFu) < n_recipes;
+    const uint32_t pool_base = e.pool & 0xFFFFu, pool_count = e.pool >> 16;
+    ok = ok && !(pool_count && pool_base + pool_count > (uint32_t)P.L);
+    bool tagged_dead = false;
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) tagged_dead = tagged_dead || (!(e.d0[k] & D_ALIVE) && (e.d1[k] & 0xFFu));   // (lanes past D hold zeros)
+    ok = ok && ballot(tagged_dead) == 0ull;
+    if (!ok) {
+        if (lane == 0) atomicAdd(refused, 1ull);
+        return;
+    }
+    // the old record's words, read before anything overwrites them
+    const uint32_t old_status = rfl(rec[W_STATUS]), old_t = rfl(rec[W_T]);
+    const uint32_t correction = ((old_status & ST_DONE) ? 0u : old_t) - ((e.status & ST_DONE) ? 0u : e.t);
+    if (lane == 0) P.stat_u[(size_t)env * SU_WORDS + SU_STEPS] += correction;       // a signed word (k_stats_chains)
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const uint32_t w = (uint32_t)lane + 64u * k;
+        if (w < RW) stg<uint32_t>(rec, w * 4u, raw[k]);
+    }
+    init_lds<CPL>(P, cx, lds);
+    const uint32_t submask = load_submask(P, lane);
+    if (obs_out || codes_out) {
+        if (obs_out) init_lut(P, lut, lane, 64);
+        uint32_t dsc[OBS_CHUNK];
+        load_desc(P, e.layout, 0, lane, dsc);
+        observe(P, e, cx, lds, lut, dsc, submask, obs_out ? obs_out + (size_t)env * NA * P.F : nullptr, true, true,
+                codes_out ? codes_out + (size_t)env * NA * codes_pitch(P.F) : nullptr);
+    }
+    if (obs32_out) {
+        for (int i = lane; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
+        if (!(obs_out || codes_out)) build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);      // (else observe has built it)
+        write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs32_out + (size_t)env * NA * P.F, nullptr);
+    }
+}
+
 // launchers exported by each instantiation unit
 struct StepChoice { StepMode mode; bool lean; };       // which variant a launch takes (choose_step, cz_api.hip)
 struct Launchers {
@@ -1177,6 +1259,9 @@ struct Launchers {
     hipError_t (*observe_f32)(const Params &, hipStream_t, int64_t, int, float *);
     // k_reset_where over all P.N envs: mask, layout ids, float64 rows, float32 rows, codes, refused counter
     hipError_t (*reset_where)(const Params &, hipStream_t, const uint8_t *, const int32_t *, double *, float *, uint8_t *, unsigned long long *);
+    // k_restore_where over all P.N envs: slots, archive, its rows, recipes in the table, float64 rows, float32 rows, codes, refused counter
+    hipError_t (*restore_where)(const Params &, hipStream_t, const int32_t *, const uint32_t *, int64_t, uint32_t, double *, float *, uint8_t *,
+                                unsigned long long *);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1254,7 +1339,15 @@ struct Inst {
             return hipGetLastError();
         });
     }
-    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where}; }
+    static hipError_t restore_where(const Params &P, hipStream_t st, const int32_t *slot, const uint32_t *records, int64_t capacity,
+                                    uint32_t n_recipes, double *obs, float *obs32, uint8_t *codes, unsigned long long *refused) {
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_restore_where<OPL, CPL, decltype(na)::value>), dim3((unsigned)P.N), dim3(64), 0, st, P, slot, records, capacity,
+                               n_recipes, obs, obs32, codes, refused);
+            return hipGetLastError();
+        });
+    }
+    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where}; }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

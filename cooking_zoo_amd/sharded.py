@@ -343,6 +343,29 @@ class ShardedVecEnv:
         """envs `reset_device` refused (explicit layout id past the pool), summed over the local shards"""
         return sum(self._each(lambda i, env: env.reset_device_refused()))
 
+    def save_device(self, d_records, d_slot=None):
+        """`CookingVecEnv.save_device` on every shard, over its part of the buffers: d_records a ShardedBuffer of uint32 with per-env
+        shape (record_words,) - one row per env of the shard - or a list of one archive per shard; d_slot int32 per env.  Slots
+        are LOCAL: they count rows of the shard's own archive."""
+        P = self._part
+        self._each(lambda i, env: env.save_device(P(d_records, i), P(d_slot, i)))
+
+    def restore_device(self, d_records, d_slot=None, d_obs=None, d_obs32=None, d_codes=None):
+        """`CookingVecEnv.restore_device` on every shard, over its part of the buffers (slots local to the shard's archive, as in
+        `save_device`).  Keyed draws use global env ids: behind the call the batch behaves like one handle given the same rows."""
+        P = self._part
+        self._each(lambda i, env: env.restore_device(P(d_records, i), P(d_slot, i), P(d_obs, i), P(d_obs32, i), P(d_codes, i)))
+
+    def restore_device_refused(self):
+        """envs `restore_device` / `fork_device` refused, summed over the local shards"""
+        return sum(self._each(lambda i, env: env.restore_device_refused()))
+
+    def fork_device(self, d_src, d_obs=None, d_obs32=None, d_codes=None):
+        """`CookingVecEnv.fork_device` on every shard: d_src[e] names an env of the SAME shard by its local index (0 .. envs of the
+        shard - 1; negative: keep).  Forks across shards are out of scope: a record would have to travel between devices."""
+        P = self._part
+        self._each(lambda i, env: env.fork_device(P(d_src, i), P(d_obs, i), P(d_obs32, i), P(d_codes, i)))
+
     def step_device_ring(self, K, d_ring, action_period, first_slot, d_obs, d_rewards, d_term, d_trunc):
         """K steps; step k reads slot (first_slot + k) % action_period of `d_ring` (ShardedBuffer with leading = (action_period,))"""
         P = self._part

@@ -267,6 +267,7 @@ class CookingVecEnv:
         self._upload_layouts()
         self._buffers = []
         self._ep_bufs = None                  # finished_episodes: the packed list and the count
+        self._fork_buf = None                 # fork_device: the scratch archive, one row per env
         self._steps = 0                       # env steps issued so far (every stepping method counts; `advance` adds replayed ones)
         self.captured_steps = 0               # steps captured into graphs of the caller (they run at replay, see `advance`)
         self._caller_stream, self._warned_capture = False, False
@@ -759,6 +760,58 @@ class CookingVecEnv:
         if n < 0:
             _native.check(self._h, 1)
         return n
+
+    @staticmethod
+    def _archive_rows(d_records, capacity):
+        """rows of an archive: `capacity`, or the leading dimension of a buffer that has a shape (DeviceBuffer, torch tensor)"""
+        if capacity is None:
+            shape = getattr(d_records, "shape", None)
+            if shape is None or len(shape) != 2:
+                raise ValueError("an archive given as a raw address needs capacity=")
+            capacity = shape[0]
+        return int(capacity)
+
+    def save_device(self, d_records, d_slot=None, capacity=None):
+        """Records out of the batch, on the device: env e writes its whole record (`record_words` uint32, running returns included) to
+        row d_slot[e] of the archive d_records, uint32 [capacity, record_words] - `alloc((capacity, record_words), np.uint32)` or a
+        torch tensor; a raw address needs `capacity`.  d_slot int32 [N]: a negative slot skips the env, a slot >= capacity writes
+        nothing (and is not counted); None: row e, and the archive needs N rows.  Two envs that name one row leave it unspecified.
+        One launch on the env's stream, no copy and no wait, legal inside a capture; not a step; nothing of the env changes."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_save_device(self._h, p(d_slot), p(d_records), self._archive_rows(d_records, capacity)))
+
+    def restore_device(self, d_records, d_slot=None, d_obs=None, d_obs32=None, d_codes=None, capacity=None):
+        """Records into the batch, on the device: env e becomes row d_slot[e] of the archive (`save_device`), word for word - layout,
+        recipes, pool slice, status with despawn bits and countdowns, episode, t, marks, running returns.  A negative slot leaves the
+        env alone; None: row e.  Any number of envs may name one row: they fork it, and diverge wherever draws are made, which stay
+        keyed by each env's own global id (auto-reset layouts, the on-device action stream, despawn / respawn).  A slot >= capacity
+        or a row that `set_state` would reject is refused - the env and its rows stay as they were, `restore_device_refused` counts
+        it.  d_obs float64 [N, A, F], d_obs32 float32 [N, A, F], d_codes uint8 [N, A, codes_pitch]: whole-batch buffers of which only
+        the rows of the restored envs are written, with the observation of the restored state.  `stats()["env_steps"]` keeps counting
+        the steps this env took: a running episode that is overwritten keeps its steps, one that arrives brings none; no episode is
+        counted, and an episode cut short shows up in no `finished_episodes()`.  The archive must fit the layout pool it was saved
+        under (a rewritten slot gives the record's own cells and objects, encoded with the slot's new descriptor row: not checked).
+        One launch on the env's stream, no copy and no wait, legal inside a capture; not a step."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_restore_device(self._h, p(d_slot), p(d_records), self._archive_rows(d_records, capacity),
+                                                               p(d_obs), p(d_obs32), p(d_codes)))
+
+    def restore_device_refused(self):
+        """envs `restore_device` / `fork_device` left alone (slot past the archive, or a row `set_state` would reject) since the env
+        was created (waits)"""
+        n = int(_native.lib().cz_restore_device_refused(self._h))
+        if n < 0:
+            _native.check(self._h, 1)
+        return n
+
+    def fork_device(self, d_src, d_obs=None, d_obs32=None, d_codes=None):
+        """env e becomes a copy of env d_src[e] (int32 [N]; negative: e keeps its state; >= N: refused and counted) as the batch is
+        when the call starts: an identity `save_device` into a scratch archive of the env's own (allocated at the first call, freed
+        by `close`), then `restore_device` with d_src as the slots - two launches, so sources may be destinations as well."""
+        if self._fork_buf is None:
+            self._fork_buf = self.alloc((self.num_envs, self.dims.RW), np.uint32)
+        self.save_device(self._fork_buf)
+        self.restore_device(self._fork_buf, d_src, d_obs, d_obs32, d_codes)
 
     def set_compact_output(self, d_codes=None):
         """every one-step launch from now on (step_device, step_device_ring, step) also writes the compact observation to d_codes

@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -259,6 +259,46 @@ int cz_reset(cz_handle h, int64_t env_begin, int64_t env_count, const int32_t *l
 int cz_reset_device(cz_handle h, const uint8_t *d_mask, const int32_t *d_layout_ids,
                     double *d_obs, float *d_obs32, uint8_t *d_codes);
 int64_t cz_reset_device_refused(cz_handle h);
+
+/* SAVE, RESTORE AND FORK env states on the device.  A record is a self-contained value - layout id, recipe ids, pool slice, status,
+ * episode, t, marks, running returns, cells and objects, cz_record_words words in all - so an ARCHIVE of records in device memory,
+ * d_records = uint32 [capacity][cz_record_words], owned by the caller, is all that tree search, archives of interesting states,
+ * restarts from saved curriculum states or copying the best env over the worst need.  Every pointer is a device pointer; each call
+ * is ONE kernel launch on the handle's stream - no copy, no query, no wait; legal inside a stream capture - and no step (the
+ * host-pointer way is cz_get_state / cz_set_state, which copy and wait).  The archive must not overlap memory of the handle.
+ *
+ * cz_save_device: env e writes its whole record, the running-return words included, to row d_slot[e].  d_slot == NULL: row e, and
+ * capacity >= num_envs is required (checked on the host, before anything is launched).  A negative slot skips the env.  A slot >=
+ * capacity writes nothing, and NO counter is kept for it.  Two envs that name the same row leave that row unspecified: distinct rows
+ * are the caller's contract.  Nothing of the handle changes.
+ *
+ * cz_restore_device: env e takes row d_slot[e]; d_slot == NULL: row e, capacity >= num_envs required as above.  A negative slot
+ * leaves the env alone (its wavefront reads that one word and leaves).  ANY NUMBER of envs may name the same row: that is the fork.
+ * A chosen env's record becomes the row word for word: its layout id, recipe ids and pool word, its status with the despawn bits
+ * and grace countdowns, its episode word, t, recipe marks and running returns.  Keyed draws stay keyed by the env's own global id
+ * (env_id_base + e) - the layout an auto-reset takes, the on-device action stream of cz_rollout, despawn / respawn draws - so forks
+ * of one state DIVERGE wherever a draw is made, and stay identical where none is (same actions, no auto-reset, no spawn draws).
+ * REFUSED: a row is checked on the device before any word of it is used as an index, by the checks of cz_set_state - layout id <
+ * n_layouts, each of the num_recipes recipe ids < the recipe table's size, the pool slice inside the pool, no slot that is not alive
+ * but carries a container tag.  An env whose slot is >= capacity or whose row fails stays exactly as it was, none of its output rows
+ * is touched, and a device counter is incremented; cz_restore_device_refused reads it (envs refused since cz_create; waits for the
+ * stream; -1 on error).
+ * Statistics: env_steps keeps meaning steps this handle took.  A restored env adds the old record's t to its step count if the old
+ * record was not done (an episode cut short: its steps stay counted, as after cz_reset) and subtracts the new record's t if the new
+ * record is not done (steps that arrive already taken, as cz_reset_stats treats episodes in flight).  No episode is counted; the
+ * env's last-episode row is left alone, so an episode cut short by a restore leaves no record in cz_episodes_collect; a restored
+ * episode that later ends reports the record's whole length and the inherited return plus the later rewards in step order.
+ * Outputs, each may be NULL and each is laid out for the WHOLE batch: d_obs float64 [N][A][F], d_obs32 float [N][A][F] (dense, the
+ * rounding of cz_step_device_f32), d_codes uint8 [N][A][cz_codes_pitch] (padding 255) - observe() (cooking_env.py:271,352-373) of
+ * the restored state in rows e of the chosen, not refused envs; every other byte stays untouched.  cz_set_compact_output /
+ * cz_set_f32_output are ignored.
+ * The caller keeps the archive consistent with the layout pool: a record saved before its layout slot was rewritten
+ * (cz_update_layouts, cz_generate_layouts) restores its own cells and objects but is encoded with the slot's CURRENT descriptor row.
+ * This is not checked. */
+int cz_save_device(cz_handle h, const int32_t *d_slot, uint32_t *d_records, int64_t capacity);
+int cz_restore_device(cz_handle h, const int32_t *d_slot, const uint32_t *d_records, int64_t capacity,
+                      double *d_obs, float *d_obs32, uint8_t *d_codes);
+int64_t cz_restore_device_refused(cz_handle h);
 
 /* observe() (cooking_env.py:271,352-373) of the current state of envs [env_begin, env_begin+env_count):
  * host buffer [env_count][A][F] float64. */
