@@ -382,6 +382,26 @@ static int fail(cz_handle h, const char *fmt, ...) {
 
 extern "C" const char *cz_last_error(cz_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
 
+// one counter (a T) in device memory, as it stands behind everything on the handle's stream (waits for it); -1 on error
+template <class T>
+static int64_t read_counter(cz_handle h, const void *d_counter, const char *who) {
+    T n = 0;
+    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&n, d_counter, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "%s: copy failed", who); return -1; }
+    return (int64_t)n;
+}
+// the level of every slot of the resident pool (`level_of`; null: all of them level 0), each < n_levels: `misfit` is the caller's
+// message for a slot that is not - its slot, its level, n_levels
+static int pool_levels(cz_handle h, const uint8_t *level_of, int32_t n_levels, const char *misfit, std::vector<uint8_t> &levels) {
+    levels.assign((size_t)h->n_layouts, 0);
+    for (int i = 0; i < h->n_layouts; ++i) {
+        const int lv = level_of ? level_of[i] : 0;
+        if (lv >= n_levels) return fail(h, misfit, i, lv, n_levels);
+        levels[(size_t)i] = (uint8_t)lv;
+    }
+    return 0;
+}
+
 // Is the stream this handle's work goes to (a stream of the caller, cz_set_stream) being captured - hipStreamBeginCapture,
 // torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*), cz_reset_device, cz_save_device and cz_restore_device are then pure
 // kernel launches: nothing that queries or synchronises (a staged layout update stays staged until the first call outside the
@@ -660,12 +680,7 @@ extern "C" int cz_set_spawn(cz_handle h, double despawn_rate, double respawn_rat
                 memcpy(b + 4, spawn_x + ((size_t)l * h->P.A + a) * stride, (size_t)stride);
                 memcpy(b + 4 + stride, spawn_y + ((size_t)l * h->P.A + a) * stride, (size_t)stride);
             }
-        levels.assign((size_t)h->n_layouts, 0);
-        for (int i = 0; i < h->n_layouts; ++i) {
-            const int lv = level_of_layout ? level_of_layout[i] : 0;
-            if (lv >= n_levels) return fail(h, "cz_set_spawn: layout %d is of level %d, but only %d level(s) have spawn areas", i, lv, n_levels);
-            levels[(size_t)i] = (uint8_t)lv;
-        }
+        if (pool_levels(h, level_of_layout, n_levels, "cz_set_spawn: layout %d is of level %d, but only %d level(s) have spawn areas", levels)) return 1;
     }
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -702,10 +717,7 @@ extern "C" int cz_set_spawn(cz_handle h, double despawn_rate, double respawn_rat
 extern "C" int64_t cz_spawn_exhausted(cz_handle h) {
     if (!h) return -1;
     if (!h->d_spawn_tables) return 0;
-    uint32_t n = 0;
-    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&n, h->d_spawn_tables, 4, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_spawn_exhausted: copy failed"); return -1; }
-    return (int64_t)n;
+    return read_counter<uint32_t>(h, h->d_spawn_tables, "cz_spawn_exhausted");
 }
 // the draw the device takes (host mirror, for parity tests): uniform in [0, 1), keyed by (seed, global env id, episode << 32 | t,
 // agent, draw index)
@@ -819,7 +831,7 @@ static int validate_layouts(cz_handle h, const char *who, const uint32_t *init_r
     for (int32_t l = 0; l < n; ++l) {
         const uint32_t *r = init_records + (size_t)l * h->P.RW;
         for (int s2 = 0; s2 < h->P.D; ++s2)
-            if (!(r[h->P.dyn0_off + s2] & D_ALIVE) && (r[h->P.dyn1_off + s2] & 0xFFu))
+            if (slot_dead_but_tagged(r[h->P.dyn0_off + s2], r[h->P.dyn1_off + s2]))
                 return fail(h, "%s: layout %d: slot %d is not alive but carries a container tag", who, l, s2);
     }
     return 0;
@@ -1040,12 +1052,8 @@ extern "C" int cz_load_level_programs(cz_handle h, const uint32_t *programs, int
         pos += programs[pos + GH_WORDS];
     }
     if (pos != words) return fail(h, "cz_load_level_programs: %lld words given, the %d programs hold %lld", (long long)words, n_levels, (long long)pos);
-    std::vector<uint8_t> levels((size_t)h->n_layouts, 0);
-    for (int i = 0; i < h->n_layouts; ++i) {
-        const int lv = level_of_slot ? level_of_slot[i] : 0;
-        if (lv >= n_levels) return fail(h, "cz_load_level_programs: slot %d is of level %d, but only %d program(s) were given", i, lv, n_levels);
-        levels[(size_t)i] = (uint8_t)lv;
-    }
+    std::vector<uint8_t> levels;
+    if (pool_levels(h, level_of_slot, n_levels, "cz_load_level_programs: slot %d is of level %d, but only %d program(s) were given", levels)) return 1;
     // the pool slice of a slot = the run of consecutive slots of its level (cooking_zoo_amd keeps one contiguous slice per level)
     h->gen_slices.assign((size_t)h->n_layouts, {0, 0});
     for (int i = 0; i < h->n_layouts;) {
@@ -1116,10 +1124,18 @@ extern "C" int cz_generate_layouts(cz_handle h, int32_t first, int32_t count, ui
 extern "C" int64_t cz_generate_failures(cz_handle h) {
     if (!h) return -1;
     if (!h->d_gen_tables) return 0;
-    uint32_t n = 0;
-    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&n, h->d_gen_tables, 4, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_generate_failures: copy failed"); return -1; }
-    return (int64_t)n;
+    return read_counter<uint32_t>(h, h->d_gen_tables, "cz_generate_failures");
+}
+
+// The tail of a call that answers into a host buffer: behind the launch (`rc`: what it returned) the copy of the staged bytes (none
+// when `dst` is null), then the wait - also when the launch failed, since host memory the stream may still read must outlive the
+// call - and the launch's or the copy's error is reported before the wait's.
+static int copy_back_and_wait(cz_handle h, hipError_t rc, void *dst, const void *src, size_t bytes) {
+    if (rc == hipSuccess && dst) rc = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t rs = hipStreamSynchronize(h->stream);
+    HIPCHK(h, rc);
+    HIPCHK(h, rs);
+    return 0;
 }
 
 static int check_range(cz_handle h, int64_t b, int64_t c) {
@@ -1135,15 +1151,19 @@ extern "C" int cz_set_state(cz_handle h, int64_t b, int64_t c, const uint32_t *r
     // the words the kernels use as table indices must be in range (everything else lives in registers / LDS)
     for (int64_t i = 0; i < c; ++i) {
         const uint32_t *r = records + (size_t)i * h->P.RW;
-        if (h->n_layouts > 0 && r[W_LAYOUT] >= (uint32_t)h->n_layouts) return fail(h, "cz_set_state: record %lld: layout id %u out of range", (long long)i, r[W_LAYOUT]);
-        for (int k = 0; k < h->P.R; ++k)
-            if (h->n_recipes > 0 && ((r[W_RECIPES] >> (8 * k)) & 0xFFu) >= (uint32_t)h->n_recipes)
-                return fail(h, "cz_set_state: record %lld: recipe id %u out of range", (long long)i, (r[W_RECIPES] >> (8 * k)) & 0xFFu);
-        const uint32_t base = r[W_POOL] & 0xFFFFu, count = r[W_POOL] >> 16;
-        if (count && h->n_layouts > 0 && (int)(base + count) > h->n_layouts) return fail(h, "cz_set_state: record %lld: layout pool slice out of range", (long long)i);
-        // a slot that is not alive carries no container tag: the kernels take "tagged" to imply "alive" (Ops::content_of)
+        // (the rules k_restore_where applies on the device, cz_device.h; a rule waits while its table is not loaded)
+        uint32_t faults = record_header_faults(r[W_LAYOUT], r[W_RECIPES], r[W_POOL], (uint32_t)h->n_layouts, h->P.R, (uint32_t)h->n_recipes);
+        if (h->n_layouts == 0) faults &= ~(HDR_LAYOUT | HDR_POOL);
+        if (h->n_recipes == 0) faults &= ~HDR_RECIPE;
+        if (faults & HDR_LAYOUT) return fail(h, "cz_set_state: record %lld: layout id %u out of range", (long long)i, r[W_LAYOUT]);
+        if (faults & HDR_RECIPE) {
+            uint32_t shift = 0;                                      // the first id that is out of range
+            while (((r[W_RECIPES] >> shift) & 0xFFu) < (uint32_t)h->n_recipes) shift += 8;
+            return fail(h, "cz_set_state: record %lld: recipe id %u out of range", (long long)i, (r[W_RECIPES] >> shift) & 0xFFu);
+        }
+        if (faults & HDR_POOL) return fail(h, "cz_set_state: record %lld: layout pool slice out of range", (long long)i);
         for (int s2 = 0; s2 < h->P.D; ++s2)
-            if (!(r[h->P.dyn0_off + s2] & D_ALIVE) && (r[h->P.dyn1_off + s2] & 0xFFu))
+            if (slot_dead_but_tagged(r[h->P.dyn0_off + s2], r[h->P.dyn1_off + s2]))
                 return fail(h, "cz_set_state: record %lld: slot %d is not alive but carries a container tag", (long long)i, s2);
     }
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1308,12 +1328,8 @@ extern "C" int cz_reset(cz_handle h, int64_t b, int64_t c, const int32_t *layout
     Params P = h->P;
     hipLaunchKernelGGL(k_count_aborted, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, h->d_stat_u, h->d_state, h->P.RW,
                        (long long)b, (int)c);
-    hipError_t rc = h->kl.reset(P, h->stream, b, (int)c, d_lay, d_rec, d_pool, obs ? h->d_obs : nullptr);
-    if (rc == hipSuccess && obs) rc = hipMemcpyAsync(obs, h->d_obs, ob, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t rs = hipStreamSynchronize(h->stream);            // (pools, a host vector, must outlive its copy)
-    HIPCHK(h, rc);
-    HIPCHK(h, rs);
-    return 0;
+    const hipError_t rc = h->kl.reset(P, h->stream, b, (int)c, d_lay, d_rec, d_pool, obs ? h->d_obs : nullptr);
+    return copy_back_and_wait(h, rc, obs, h->d_obs, ob);            // (pools, a host vector, must outlive its copy)
 }
 
 // observe() of the current state (after cz_set_state), host buffer [count][A][F]
@@ -1325,12 +1341,7 @@ extern "C" int cz_observe(cz_handle h, int64_t b, int64_t c, double *obs) {
     size_t ob = (size_t)c * h->P.A * h->P.F * 8;
     if (!h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, (size_t)h->P.N * h->P.A * h->P.F * 8));
     Params P = h->P;
-    hipError_t rc = h->kl.observe(P, h->stream, b, (int)c, h->d_obs, nullptr);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(obs, h->d_obs, ob, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t rs = hipStreamSynchronize(h->stream);
-    HIPCHK(h, rc);
-    HIPCHK(h, rs);
-    return 0;
+    return copy_back_and_wait(h, h->kl.observe(P, h->stream, b, (int)c, h->d_obs, nullptr), obs, h->d_obs, ob);
 }
 
 // observe() of the current state into DEVICE buffers, float64 rows and / or the compact form (either may be NULL): what a consumer
@@ -1356,12 +1367,7 @@ extern "C" int cz_observe_compact(cz_handle h, int64_t b, int64_t c, uint8_t *co
     if (!h->d_codes_stage) HIPCHK(h, hipMalloc(&h->d_codes_stage, (size_t)h->P.N * row));
     Params P = h->P;
     P.wt = 0;
-    hipError_t rc = h->kl.observe(P, h->stream, b, (int)c, nullptr, (uint8_t *)h->d_codes_stage);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(codes, h->d_codes_stage, (size_t)c * row, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t rs = hipStreamSynchronize(h->stream);
-    HIPCHK(h, rc);
-    HIPCHK(h, rs);
-    return 0;
+    return copy_back_and_wait(h, h->kl.observe(P, h->stream, b, (int)c, nullptr, (uint8_t *)h->d_codes_stage), codes, h->d_codes_stage, (size_t)c * row);
 }
 
 static int set_device(cz_handle h) {
@@ -1375,6 +1381,13 @@ static int set_device(cz_handle h) {
 // Begins a call that works on device pointers: the handle is ready, the entry point's own arguments are good (`bad_args`: its message
 // otherwise), a fused rollout (`rollout`: the entry point's name) stays inside the span the kernel addresses, the handle's device is
 // current, and a staged layout update whose time may have come is flushed - unless the caller is capturing.
+// the archive arguments of cz_save_device / cz_restore_device (`who`), in front of everything that needs the device
+static int check_archive(cz_handle h, const char *who, const int32_t *d_slot, const uint32_t *d_records, int64_t capacity) {
+    if (!h) return fail(nullptr, "null handle");
+    if (!d_records || capacity < 0) return fail(h, "%s: the archive pointer is null or the capacity negative", who);
+    if (!d_slot && capacity < h->P.N) return fail(h, "%s: without slots the archive needs a row per env (capacity %lld < %d envs)", who, (long long)capacity, h->P.N);
+    return 0;
+}
 static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, const char *rollout = nullptr, int32_t T = 0) {
     if (ready(h)) return 1;
     if (!args_ok) return fail(h, "%s", bad_args);
@@ -1401,11 +1414,7 @@ extern "C" int cz_reset_device(cz_handle h, const uint8_t *d_mask, const int32_t
 }
 // envs that cz_reset_device left alone since cz_create because their explicit layout id was >= the pool size (waits for the stream); -1 on error
 extern "C" int64_t cz_reset_device_refused(cz_handle h) {
-    if (!h) return -1;
-    unsigned long long n = 0;
-    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&n, h->d_reset_refused, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_reset_device_refused: copy failed"); return -1; }
-    return (int64_t)n;
+    return h ? read_counter<unsigned long long>(h, h->d_reset_refused, "cz_reset_device_refused") : -1;
 }
 
 // An archive of records in device memory, owned by the caller: uint32 [capacity][RW].  cz_save_device gathers records out of the batch
@@ -1414,10 +1423,7 @@ extern "C" int64_t cz_reset_device_refused(cz_handle h) {
 // caller, and no step.  Without a slot array env e and row e belong together, and the archive must hold N rows: checked here, in front
 // of everything that needs the device.
 extern "C" int cz_save_device(cz_handle h, const int32_t *d_slot, uint32_t *d_records, int64_t capacity) {
-    if (!h) return fail(nullptr, "null handle");
-    if (!d_records || capacity < 0) return fail(h, "cz_save_device: the archive pointer is null or the capacity negative");
-    if (!d_slot && capacity < h->P.N) return fail(h, "cz_save_device: without slots the archive needs a row per env (capacity %lld < %d envs)", (long long)capacity, h->P.N);
-    if (begin_device_call(h, true, "")) return 1;
+    if (check_archive(h, "cz_save_device", d_slot, d_records, capacity) || begin_device_call(h, true, "")) return 1;
     hipLaunchKernelGGL(k_save_where, dim3((unsigned)h->P.N), dim3(64), 0, h->stream, (const uint32_t *)h->d_state, h->P.RW, d_slot, d_records, capacity);
     HIPCHK(h, hipGetLastError());
     return 0;
@@ -1426,10 +1432,7 @@ extern "C" int cz_save_device(cz_handle h, const int32_t *d_slot, uint32_t *d_re
 // restored envs only (cooking_env.py:271,352-373), with plain stores.
 extern "C" int cz_restore_device(cz_handle h, const int32_t *d_slot, const uint32_t *d_records, int64_t capacity, double *d_obs,
                                  float *d_obs32, uint8_t *d_codes) {
-    if (!h) return fail(nullptr, "null handle");
-    if (!d_records || capacity < 0) return fail(h, "cz_restore_device: the archive pointer is null or the capacity negative");
-    if (!d_slot && capacity < h->P.N) return fail(h, "cz_restore_device: without slots the archive needs a row per env (capacity %lld < %d envs)", (long long)capacity, h->P.N);
-    if (begin_device_call(h, true, "")) return 1;
+    if (check_archive(h, "cz_restore_device", d_slot, d_records, capacity) || begin_device_call(h, true, "")) return 1;
     Params P = h->P;
     P.wt = 0;
     HIPCHK(h, h->kl.restore_where(P, h->stream, d_slot, d_records, capacity, (uint32_t)h->n_recipes, d_obs, d_obs32, d_codes, h->d_restore_refused));
@@ -1437,11 +1440,7 @@ extern "C" int cz_restore_device(cz_handle h, const int32_t *d_slot, const uint3
 }
 // envs that cz_restore_device left alone since cz_create because their slot was >= capacity or their row failed cz_set_state's checks (waits for the stream); -1 on error
 extern "C" int64_t cz_restore_device_refused(cz_handle h) {
-    if (!h) return -1;
-    unsigned long long n = 0;
-    if (hipSetDevice(h->cfg.device_id) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&n, h->d_restore_refused, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) { fail(h, "cz_restore_device_refused: copy failed"); return -1; }
-    return (int64_t)n;
+    return h ? read_counter<unsigned long long>(h, h->d_restore_refused, "cz_restore_device_refused") : -1;
 }
 
 extern "C" int cz_step_device(cz_handle h, const int32_t *d_actions, double *d_obs, double *d_rewards, uint8_t *d_term,

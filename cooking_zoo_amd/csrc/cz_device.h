@@ -180,6 +180,23 @@ __host__ __device__ inline uint32_t spawn_initial_status(uint32_t packed_grace, 
     for (int a = 0; a < n_agents; ++a) st |= grace << (SPAWN_GRACE0 + bits * a);
     return st;
 }
+
+// What a record must satisfy before the kernels may use its words as indices, written once for everybody who lets a record in:
+// cz_set_state and validate_layouts on the host, k_restore_where on the device.
+// The header: the layout id indexes the pool's tables (< L), each of the R recipe ids the recipe table (< n_recipes), and the pool
+// slice [base, base + count) of a redraw lies inside the pool (count 0: no slice).  Returns the rules that fail: 0 = usable.
+enum : uint32_t { HDR_LAYOUT = 1u, HDR_RECIPE = 2u, HDR_POOL = 4u };
+__host__ __device__ inline uint32_t record_header_faults(uint32_t layout, uint32_t recipes, uint32_t pool, uint32_t L, int R, uint32_t n_recipes) {
+    uint32_t faults = layout < L ? 0u : HDR_LAYOUT;
+    for (int k = 0; k < R; ++k)
+        if (((recipes >> (8 * k)) & 0xFFu) >= n_recipes) faults |= HDR_RECIPE;
+    const uint32_t base = pool & 0xFFFFu, count = pool >> 16;
+    if (count && base + count > L) faults |= HDR_POOL;
+    return faults;
+}
+// A slot (its two words): not alive, yet with a container tag - the kernels take "tagged" to imply "alive" (Ops::content_of)
+__host__ __device__ inline bool slot_dead_but_tagged(uint32_t d0, uint32_t d1) { return !(d0 & D_ALIVE) && (d1 & 0xFFu); }
+
 __host__ __device__ inline uint64_t spawn_mix(uint64_t x) {                      // splitmix64 finaliser
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;

@@ -1034,6 +1034,52 @@ __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean(uint32_t 
                                                                        int32_t e_dyn1, const Params P0) {
     step_kernel<OPL, CPL, NA, SCHEME, StepTraits<STEP, true>>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
 }
+// ---- what the five off-step kernels below share; nothing here is inlined by a step kernel ----
+// the float32 table: every entry of the quotient table rounded to nearest even, staged by one wavefront
+__device__ __forceinline__ void init_lut_f32(const Params &P, float *lutf, int lane) {
+    for (int i = lane; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);
+}
+// row `i` of a buffer with `pitch` elements per row; no buffer: null
+template <class T>
+__device__ __forceinline__ T *row_of(T *base, size_t i, size_t pitch) { return base ? base + i * pitch : nullptr; }
+// The rows of one env in whichever forms were asked for: `obs`, `obs32` and `codes` are the buffers, any of them null, and `row` is
+// this env's row in them (its pointers are taken where they are used: taken by the caller, their null checks stood in front of the
+// subtrahend-mask load and on the path of a call without rows - 3 us of k_restore_where's 27 at 65 536 envs, profiles/r18/README.md).
+// The float64 table is staged only when float64 rows are wanted, the float32 one only for float32 rows - which are gathered from the
+// image observe has built, or from one built here when neither other form is wanted.  A kernel that cannot write a form passes a
+// literal null for it and for its table: the branch folds away, and the kernel carries no __shared__ table for that form.
+template <int OPL, int CPL, int NA>
+__device__ __forceinline__ void write_forms(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &lds, double *lut, float *lutf,
+                                            double *obs, float *obs32, uint8_t *codes, size_t row) {
+    const uint32_t submask = load_submask(P, cx.lane);
+    if (obs || codes) {
+        if (obs) init_lut(P, lut, cx.lane, 64);
+        uint32_t dsc[OBS_CHUNK];
+        load_desc(P, e.layout, 0, cx.lane, dsc);
+        observe(P, e, cx, lds, lut, dsc, submask, row_of(obs, row, (size_t)NA * P.F), true, true, row_of(codes, row, (size_t)NA * codes_pitch(P.F)));
+    }
+    if (obs32) {
+        init_lut_f32(P, lutf, cx.lane);
+        if (!(obs || codes)) build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);      // (else observe has built it)
+        write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs32 + row * NA * P.F, nullptr);
+    }
+}
+// A fresh episode on layout `lay` (reset(), cooking_env.py:178-210): the layout's initial record with t and the status word zeroed
+// (despawn on: everybody present, grace running), every recipe's marks from scratch, stored to `rec`, and the running returns zeroed.
+// (The auto-reset pass of step_env keeps a copy of its own: sharing this one would change the step kernels.)
+template <int OPL, int CPL, int NA>
+__device__ __forceinline__ void begin_episode(const Params &P, Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &lds, uint32_t *rec, uint32_t lay,
+                                              uint32_t episode, uint32_t recipes, uint32_t pool) {
+    load_env(P, e, cx, P.lay_init + (size_t)lay * P.RW);
+    e.t = 0; e.layout = lay; e.status = 0; e.episode = episode; e.recipes = recipes; e.pool = pool;
+    if (P.auto_reset & 2)
+        e.status = spawn_initial_status(rfl(reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET)->grace_period), NA);
+    uint32_t rowv = load_recipe_rows(P, e.recipes, cx.lane);
+    all_marks(P, e, cx, rowv, lds);
+    store_env(P, e, cx, rec, true, true);
+    if (cx.lane < MAX_AGENTS) reinterpret_cast<double *>(rec + RET_WORD0)[cx.lane] = 0.0;
+}
+
 // reset(): cooking_env.py:178-210 for envs [env_begin, env_begin + count)
 template <int OPL, int CPL, int NA>
 __global__ __launch_bounds__(64) void k_reset(const Params P, int64_t env_begin, const int32_t *__restrict__ layout_ids,
@@ -1041,30 +1087,14 @@ __global__ __launch_bounds__(64) void k_reset(const Params P, int64_t env_begin,
                                               double *obs_out) {
     __shared__ Lds<CPL> lds;
     __shared__ double lut[LUT_SIZE];
-    init_lut(P, lut, (int)threadIdx.x, 64);
     const int i = blockIdx.x;
-    const int64_t env = env_begin + i;
-    const int lane = (int)threadIdx.x;
-    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)threadIdx.x};
     init_lds<CPL>(P, cx, lds);
     Env<OPL, CPL, NA> e;
-    uint32_t *rec = P.state + (size_t)env * P.RW;
-    const uint32_t lay = rfl((uint32_t)layout_ids[i]);
+    uint32_t *rec = P.state + (size_t)(env_begin + i) * P.RW;
     const uint32_t old_episode = rfl(rec[W_EPISODE]);
-    load_env(P, e, cx, P.lay_init + (size_t)lay * P.RW);
-    e.t = 0; e.layout = lay; e.status = 0; e.episode = old_episode; e.recipes = rfl(recipe_words[i]);
-    if (P.auto_reset & 2)
-        e.status = spawn_initial_status(rfl(reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET)->grace_period), NA);
-    e.pool = rfl(pool_words[i]);
-    uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
-    all_marks(P, e, cx, rowv, lds);
-    store_env(P, e, cx, rec, true, true);
-    if (lane < MAX_AGENTS) reinterpret_cast<double *>(rec + RET_WORD0)[lane] = 0.0;
-    if (obs_out) {
-        uint32_t dsc[OBS_CHUNK];
-        load_desc(P, e.layout, 0, lane, dsc);
-        observe(P, e, cx, lds, lut, dsc, load_submask(P, lane), obs_out + (size_t)i * NA * P.F);
-    }
+    begin_episode(P, e, cx, lds, rec, rfl((uint32_t)layout_ids[i]), old_episode, rfl(recipe_words[i]), rfl(pool_words[i]));
+    write_forms(P, e, cx, lds, lut, nullptr, obs_out, nullptr, nullptr, (size_t)i);
 }
 
 // observe() only (after cz_set_state)
@@ -1072,34 +1102,27 @@ template <int OPL, int CPL, int NA>
 __global__ __launch_bounds__(64) void k_observe(const Params P, int64_t env_begin, double *obs_out, uint8_t *codes_out) {
     __shared__ Lds<CPL> lds;
     __shared__ double lut[LUT_SIZE];
-    init_lut(P, lut, (int)threadIdx.x, 64);
     const int i = blockIdx.x;
-    const int lane = (int)threadIdx.x;
-    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)threadIdx.x};
     init_lds<CPL>(P, cx, lds);
     Env<OPL, CPL, NA> e;
     load_env(P, e, cx, P.state + (size_t)(env_begin + i) * P.RW);
-    uint32_t dsc[OBS_CHUNK];
-    load_desc(P, e.layout, 0, lane, dsc);
-    observe(P, e, cx, lds, lut, dsc, load_submask(P, lane), obs_out ? obs_out + (size_t)i * NA * P.F : nullptr, true, true,
-            codes_out ? codes_out + (size_t)i * NA * codes_pitch(P.F) : nullptr);
+    write_forms(P, e, cx, lds, lut, nullptr, obs_out, nullptr, codes_out, (size_t)i);
 }
 
 // ... as float32 rows float[count][A][F] (cz_observe_device_f32): the form of STEP_F32, for the first observation after cz_reset /
-// cz_set_state.  A kernel of its own, so that k_observe stays the code it was.
+// cz_set_state.  A kernel of its own next to k_observe: each carries one table in LDS, and both are write_forms with the other
+// forms literally null.
 template <int OPL, int CPL, int NA>
 __global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_begin, float *obs_out) {
     __shared__ Lds<CPL> lds;
     __shared__ float lutf[LUT_SIZE];
-    for (int i = (int)threadIdx.x; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
     const int i = blockIdx.x;
-    const int lane = (int)threadIdx.x;
-    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)threadIdx.x};
     init_lds<CPL>(P, cx, lds);
     Env<OPL, CPL, NA> e;
     load_env(P, e, cx, P.state + (size_t)(env_begin + i) * P.RW);
-    build_image<OPL, CPL, NA>(P, e, cx, lds, load_submask(P, lane), true, true);
-    write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs_out + (size_t)i * NA * P.F, nullptr);
+    write_forms(P, e, cx, lds, nullptr, lutf, nullptr, obs_out, nullptr, (size_t)i);
 }
 
 // reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
@@ -1107,7 +1130,7 @@ __global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_
 // env, without spending a step.  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load,
 // before anything is staged, and strands no barrier.  A chosen env: episode + 1; the layout is layout_ids[e] when that is >= 0, else
 // the keyed draw of the auto-reset pass (same control words); an explicit id >= L is refused - the env stays as it was, `refused`
-// counts it.  Then k_reset's work - recipes and pool word are the old record's - and the rows of whichever forms were asked for, in
+// counts it.  Then k_reset's work (begin_episode) - recipes and pool word are the old record's - and write_forms' rows, in
 // buffers laid out for the whole batch: rows e of the chosen envs only.  P.wt is 0 here (plain stores).
 template <int OPL, int CPL, int NA>
 __global__ __launch_bounds__(64) void k_reset_where(const Params P, const uint8_t *__restrict__ mask, const int32_t *__restrict__ layout_ids,
@@ -1143,36 +1166,16 @@ __global__ __launch_bounds__(64) void k_reset_where(const Params P, const uint8_
     Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
     init_lds<CPL>(P, cx, lds);
     Env<OPL, CPL, NA> e;
-    load_env(P, e, cx, P.lay_init + (size_t)lay * P.RW);
-    e.t = 0; e.layout = lay; e.status = 0; e.episode = episode; e.recipes = recipes; e.pool = pool;
-    if (P.auto_reset & 2)
-        e.status = spawn_initial_status(rfl(reinterpret_cast<const SpawnCfg *>(reinterpret_cast<const char *>(P.lut) + SPAWN_CFG_OFFSET)->grace_period), NA);
-    uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
-    all_marks(P, e, cx, rowv, lds);
-    store_env(P, e, cx, rec, true, true);
-    if (lane < MAX_AGENTS) reinterpret_cast<double *>(rec + RET_WORD0)[lane] = 0.0;
-    const uint32_t submask = load_submask(P, lane);
-    if (obs_out || codes_out) {
-        if (obs_out) init_lut(P, lut, lane, 64);
-        uint32_t dsc[OBS_CHUNK];
-        load_desc(P, e.layout, 0, lane, dsc);
-        observe(P, e, cx, lds, lut, dsc, submask, obs_out ? obs_out + (size_t)env * NA * P.F : nullptr, true, true,
-                codes_out ? codes_out + (size_t)env * NA * codes_pitch(P.F) : nullptr);
-    }
-    if (obs32_out) {
-        for (int i = lane; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
-        if (!(obs_out || codes_out)) build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);      // (else observe has built it)
-        write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs32_out + (size_t)env * NA * P.F, nullptr);
-    }
+    begin_episode(P, e, cx, lds, rec, lay, episode, recipes, pool);
+    write_forms(P, e, cx, lds, lut, lutf, obs_out, obs32_out, codes_out, env);
 }
 
 // A record enters the batch (cz_restore_device): env e becomes row slot[e] of the caller's archive, word for word (no slot array:
 // row e; the host has checked capacity >= N); any number of envs may name one row.  One wavefront per env and workgroup: the wave of
 // an env whose slot is negative leaves behind one load, before anything is staged, and strands no barrier.  The row is read with
 // per-lane loads - the raw words (lane l: words l, l + 64, ...) and load_env's typed view of them, neither of which uses a word of
-// the row as an index - and then checked as cz_set_state checks a record on the host: layout id < L, each of the P.R recipe ids <
-// n_recipes, the pool slice inside the pool, no dead slot with a container tag (a ballot over the lanes that hold the slots).  A
-// slot >= capacity or a failing row is refused: the env and its rows stay as they were, `refused` counts it.  Otherwise the raw
+// the row as an index - and then checked by the functions cz_set_state checks a record with on the host: record_header_faults and,
+// in a ballot over the lanes that hold the slots, slot_dead_but_tagged (cz_device.h).  A slot >= capacity or a failing row is refused: the env and its rows stay as they were, `refused` counts it.  Otherwise the raw
 // words go to the env's record (byte-exact: store_env plays no part), lane 0 corrects SU_STEPS - plus the old record's t when that
 // episode was running (k_count_aborted's rule: its steps stay counted), minus the new record's t when this one is (k_stats_clear's
 // rule: steps that arrive already taken are not this handle's) - and the rows of whichever forms were asked for are written as
@@ -1210,16 +1213,11 @@ __global__ __launch_bounds__(64) void k_restore_where(const Params P, const int3
     Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
     Env<OPL, CPL, NA> e;
     load_env(P, e, cx, row);
-    // the checks of cz_set_state, before any of these words is an index
-    bool ok = e.layout < (uint32_t)P.L;
-    for (int k = 0; k < P.R; ++k) ok = ok && ((e.recipes >> (8 * k)) & 0xFFu) < n_recipes;
-    const uint32_t pool_base = e.pool & 0xFFFFu, pool_count = e.pool >> 16;
-    ok = ok && !(pool_count && pool_base + pool_count > (uint32_t)P.L);
+    // the record rules of cz_set_state (cz_device.h), before any of these words is an index
     bool tagged_dead = false;
 #pragma unroll
-    for (int k = 0; k < OPL; ++k) tagged_dead = tagged_dead || (!(e.d0[k] & D_ALIVE) && (e.d1[k] & 0xFFu));   // (lanes past D hold zeros)
-    ok = ok && ballot(tagged_dead) == 0ull;
-    if (!ok) {
+    for (int k = 0; k < OPL; ++k) tagged_dead = tagged_dead || slot_dead_but_tagged(e.d0[k], e.d1[k]);   // (lanes past D hold zeros)
+    if (record_header_faults(e.layout, e.recipes, e.pool, (uint32_t)P.L, P.R, n_recipes) || ballot(tagged_dead) != 0ull) {
         if (lane == 0) atomicAdd(refused, 1ull);
         return;
     }
@@ -1233,19 +1231,7 @@ __global__ __launch_bounds__(64) void k_restore_where(const Params P, const int3
         if (w < RW) stg<uint32_t>(rec, w * 4u, raw[k]);
     }
     init_lds<CPL>(P, cx, lds);
-    const uint32_t submask = load_submask(P, lane);
-    if (obs_out || codes_out) {
-        if (obs_out) init_lut(P, lut, lane, 64);
-        uint32_t dsc[OBS_CHUNK];
-        load_desc(P, e.layout, 0, lane, dsc);
-        observe(P, e, cx, lds, lut, dsc, submask, obs_out ? obs_out + (size_t)env * NA * P.F : nullptr, true, true,
-                codes_out ? codes_out + (size_t)env * NA * codes_pitch(P.F) : nullptr);
-    }
-    if (obs32_out) {
-        for (int i = lane; i < LUT_SIZE; i += 64) lutf[i] = (float)ldg<double>(P.lut, (uint32_t)i * 8u);   // round to nearest even
-        if (!(obs_out || codes_out)) build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);      // (else observe has built it)
-        write_rows_f32<OPL, CPL, NA>(P, e, cx, lds, lutf, obs32_out + (size_t)env * NA * P.F, nullptr);
-    }
+    write_forms(P, e, cx, lds, lut, lutf, obs_out, obs32_out, codes_out, env);
 }
 
 // launchers exported by each instantiation unit
@@ -1313,40 +1299,31 @@ struct Inst {
             });
         });
     }
+    // one launch of an off-step kernel K<OPL, CPL, NA>, one wavefront per env: `envs` workgroups, Params first
+#define CZ_LAUNCH_PER_ENV(K, envs, ...)                                                                                             \
+    with_agents(P.A, [&](auto na) {                                                                                                 \
+        hipLaunchKernelGGL((K<OPL, CPL, decltype(na)::value>), dim3((unsigned)(envs)), dim3(64), 0, st, P, __VA_ARGS__);            \
+        return hipGetLastError();                                                                                                   \
+    })
     static hipError_t reset(const Params &P, hipStream_t st, int64_t b, int n, const int32_t *lay, const uint32_t *rec,
                             const uint32_t *pool, double *obs) {
-        return with_agents(P.A, [&](auto na) {
-            hipLaunchKernelGGL((k_reset<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, lay, rec, pool, obs);
-            return hipGetLastError();
-        });
+        return CZ_LAUNCH_PER_ENV(k_reset, n, b, lay, rec, pool, obs);
     }
     static hipError_t observe(const Params &P, hipStream_t st, int64_t b, int n, double *obs, uint8_t *codes) {
-        return with_agents(P.A, [&](auto na) {
-            hipLaunchKernelGGL((k_observe<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, obs, codes);
-            return hipGetLastError();
-        });
+        return CZ_LAUNCH_PER_ENV(k_observe, n, b, obs, codes);
     }
     static hipError_t observe_f32(const Params &P, hipStream_t st, int64_t b, int n, float *obs) {
-        return with_agents(P.A, [&](auto na) {
-            hipLaunchKernelGGL((k_observe_f32<OPL, CPL, decltype(na)::value>), dim3(n), dim3(64), 0, st, P, b, obs);
-            return hipGetLastError();
-        });
+        return CZ_LAUNCH_PER_ENV(k_observe_f32, n, b, obs);
     }
     static hipError_t reset_where(const Params &P, hipStream_t st, const uint8_t *mask, const int32_t *lay, double *obs, float *obs32,
                                   uint8_t *codes, unsigned long long *refused) {
-        return with_agents(P.A, [&](auto na) {
-            hipLaunchKernelGGL((k_reset_where<OPL, CPL, decltype(na)::value>), dim3((unsigned)P.N), dim3(64), 0, st, P, mask, lay, obs, obs32, codes, refused);
-            return hipGetLastError();
-        });
+        return CZ_LAUNCH_PER_ENV(k_reset_where, P.N, mask, lay, obs, obs32, codes, refused);
     }
     static hipError_t restore_where(const Params &P, hipStream_t st, const int32_t *slot, const uint32_t *records, int64_t capacity,
                                     uint32_t n_recipes, double *obs, float *obs32, uint8_t *codes, unsigned long long *refused) {
-        return with_agents(P.A, [&](auto na) {
-            hipLaunchKernelGGL((k_restore_where<OPL, CPL, decltype(na)::value>), dim3((unsigned)P.N), dim3(64), 0, st, P, slot, records, capacity,
-                               n_recipes, obs, obs32, codes, refused);
-            return hipGetLastError();
-        });
+        return CZ_LAUNCH_PER_ENV(k_restore_where, P.N, slot, records, capacity, n_recipes, obs, obs32, codes, refused);
     }
+#undef CZ_LAUNCH_PER_ENV
     static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where}; }
 };
 

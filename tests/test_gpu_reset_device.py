@@ -150,6 +150,7 @@ class Bufs:
 
 
 ALL_FORMS = ("obs", "obs32", "codes")
+FORM_SUBSETS = [tuple(f for k, f in enumerate(ALL_FORMS) if m >> k & 1) for m in range(1, 8)]      # the seven non-empty ones
 
 
 def check_rows(ctx, env, before, got, rows, forms=ALL_FORMS):
@@ -172,17 +173,21 @@ def check_rows(ctx, env, before, got, rows, forms=ALL_FORMS):
             assert np.array_equal(got[1][e], codes[e]), f"{ctx}: codes of env {e} were touched"
 
 
-def replay(env, script, forms=ALL_FORMS, prepare=None):
-    """the script on the device: step (float64 rows for everyone; codes and float32 rows keep their sentinel), then reset_device"""
+def replay(env, script, forms=ALL_FORMS, prepare=None, calls=None):
+    """the script on the device: step (float64 rows for everyone; codes and float32 rows keep their sentinel), then reset_device.
+    `calls`: the steps whose reset call is made, a range - the steps in front of it must choose nobody, those behind it are left out"""
     b = Bufs(env)
     env.reset(return_obs=False)
     assert np.array_equal(strip(env.get_state()), script.rec0)
     if prepare:
         prepare()
-    for t, s in enumerate(script.steps):
+    for t, s in enumerate(script.steps if calls is None else script.steps[:calls[-1] + 1]):
         b.fill()
         b.act.from_host(s["acts"])
         env.step_device(b.act, b.obs, b.rew, b.term, b.trunc)
+        if calls is not None and t not in calls:
+            assert not s["mask"].any() and not script.null_mask      # (without its call the records are still the script's)
+            continue
         b.mask.from_host(s["mask"])
         if s["ids"] is not None:
             b.ids.from_host(s["ids"])
@@ -205,6 +210,26 @@ def test_mixed_run_all_three_forms():
     assert s.sensitive(37), s.count                 # (the oracle alone: each of the four kinds of env at least N times)
     env = make(37, **COOP)
     replay(env, s)
+    assert env.reset_device_refused() == 0
+    env.close()
+
+
+MIXED_CALLS = range(1, 25)          # the mixed script's calls 1..24: in each of them somebody is chosen (call 0 chooses nobody)
+
+
+@pytest.mark.parametrize("forms", FORM_SUBSETS, ids="+".join)
+def test_every_subset_of_forms(forms):
+    """k_reset_where's rows come from one writer shared with the other off-step kernels: each form alone, each pair - float32 rows
+    from the image observe built, the float64 table staged or not - and all three; a buffer the call does not name keeps its sentinel"""
+    s = coop_script("mixed")
+    kinds = np.zeros(4, dtype=int)                  # (the oracle alone) per call somebody chosen and somebody left alone ...
+    for t in MIXED_CALLS:
+        chosen, done = s.steps[t]["mask"] != 0, (s.steps[t]["stepped"][:, soa.W_STATUS] & 1) != 0
+        assert chosen.any() and not chosen.all() and sorted(s.steps[t]["rows"]) == np.nonzero(chosen)[0].tolist(), t
+        kinds += [(chosen & done).sum(), (chosen & ~done).sum(), (~chosen & done).sum(), (~chosen & ~done).sum()]
+    assert (kinds >= 20).all(), kinds               # ... and over the calls each of the four kinds of env, often
+    env = make(37, **COOP)
+    replay(env, s, forms, calls=MIXED_CALLS)
     assert env.reset_device_refused() == 0
     env.close()
 

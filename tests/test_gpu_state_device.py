@@ -13,7 +13,7 @@ from cooking_zoo_amd import _native, soa
 from fuzz_policy import BumperActions
 from oracle_binding import VecOracle
 from test_gpu_f32_obs import SENTINEL
-from test_gpu_reset_device import ALL_FORMS, COOP, INSTANCE_CASES, SENT8, SENT64, TWO, Bufs, check_rows, make, strip, tables_of
+from test_gpu_reset_device import ALL_FORMS, COOP, FORM_SUBSETS, INSTANCE_CASES, SENT8, SENT64, TWO, Bufs, check_rows, make, strip, tables_of
 from test_state_device_host import env_steps, row_ok, steps_correction
 
 pytestmark = pytest.mark.gpu
@@ -269,6 +269,28 @@ def test_fork_device_with_overlapping_sources_and_destinations():
     for k in range(5):
         step_both(env, b, tw, f"step {k} behind the forks")
     assert_stats(env, tw, "behind the forks")
+    env.close()
+
+
+@pytest.mark.parametrize("forms", FORM_SUBSETS, ids="+".join)
+def test_every_subset_of_forms(forms):
+    """k_restore_where's rows come from one writer shared with the other off-step kernels: each form alone, each pair - float32 rows
+    from the image observe built, the float64 table staged or not - and all three; a buffer the call does not name keeps its sentinel"""
+    t, env, tw, b = start(37, False, 6, **COOP)
+    done = mixed_ages(env, b, tw)
+    arch = archive_of(env, 37)
+    env.save_device(arch)
+    row_done = done.copy()
+    for k in range(14, 16):
+        step_both(env, b, tw, f"step {k}")
+    slots = ((np.arange(37) * 7 + 3) % 37).astype(np.int32)
+    slots[::3] = -1
+    chosen, done = slots >= 0, tw.done()
+    # (the oracle alone) envs that are chosen and envs that are left alone, finished and running ones of each; rows of both kinds
+    assert min((chosen & done).sum(), (chosen & ~done).sum(), (~chosen & done).sum(), (~chosen & ~done).sum()) >= 3
+    assert row_done[slots[chosen]].any() and (~row_done[slots[chosen]]).any()
+    rows = restore_both(env, b, tw, "restore", arch, slots, forms)
+    assert sorted(rows) == np.nonzero(chosen)[0].tolist() and env.restore_device_refused() == 0
     env.close()
 
 
