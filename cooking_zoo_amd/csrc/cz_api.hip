@@ -342,6 +342,8 @@ struct cz_handle_s {
     int n_ranks = 1, rank = 0;
     int wt_override = -1;          // CZ_WT experiment switch, read once
     bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
+    bool lean_cfg_enabled = true;  // CZ_LEAN_CFG=0: lean launches always take k_step_lean, never a k_step_lean_cfg (A/B runs)
+    int last_step_variant = -1;    // cz_diag_last_step_variant
     int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
     int last_step_mode = -1;       // the StepMode of that launch (cz_diag_last_step_mode)
     bool huge = false;             // the 256-slot / 1024-cell instance (its own LDS image layout)
@@ -510,6 +512,7 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     P.T = 1;
     if (const char *s = getenv("CZ_WT")) h->wt_override = atoi(s);
     if (const char *s = getenv("CZ_LEAN")) h->lean_enabled = atoi(s) != 0;
+    if (const char *s = getenv("CZ_LEAN_CFG")) h->lean_cfg_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_GRAPHS")) h->graphs_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_GRAPH_MIN_RUN")) h->graph_min_run = atoi(s) < 4 ? 4 : (atoi(s) > 256 ? 256 : atoi(s));   // 4..RING_MAX_GRAPH
     if (const char *s = getenv("CZ_RING_PREFIX")) h->ring_prefix = atoi(s) < 0 ? 0 : (atoi(s) > 16 ? 16 : atoi(s));
@@ -1237,11 +1240,14 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 //   one step without P.actions        -> hipErrorInvalidValue
 static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c) {
     c.lean = false;
+    c.cfg = -1;
     if (fused && form == OBS_F32) c.mode = P.actions ? ROLLOUT_ACTIONS_F32 : ROLLOUT_F32;
     else if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : form != OBS_CODES ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
     else c.mode = form == OBS_F32 ? STEP_F32 : form == OBS_CODES ? STEP_CODES : STEP;
     if (c.mode == STEP)
         c.lean = h->lean_enabled && h->kl.has_lean && P.obs && !P.marks_out && !P.wide && !(P.auto_reset & 2) && P.F <= 128 * OBS_PAIRS && P.wt == 1;
+    // ... and of the lean kernels the one with the handle's recipe count, end condition and walk_touches fixed, where one exists
+    if (c.lean && h->lean_cfg_enabled) c.cfg = lean_cfg_of(P);
     return !fused && !P.actions ? hipErrorInvalidValue : hipSuccess;
 }
 
@@ -1295,6 +1301,7 @@ static int launch_step(cz_handle h, const StepCall &call) {
     const hipError_t chosen = choose_step(h, P, fused, form, choice);
     h->last_step_lean = choice.lean ? 1 : 0;
     h->last_step_mode = choice.mode;
+    h->last_step_variant = !choice.lean ? -1 : choice.cfg < 0 ? 0 : (0x100 | P.R | (P.end_all << 4) | (P.walk_touches << 5));
     HIPCHK(h, chosen);
     HIPCHK(h, h->kl.step(P, stream, choice));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
@@ -1511,6 +1518,9 @@ extern "C" int cz_obs_table_f32(cz_handle h, float *table) {
 extern "C" int32_t cz_diag_last_step_lean(cz_handle h) { return h ? h->last_step_lean : -1; }
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_kernel_matrix.py): the StepMode (cz_kernels.h) of that launch, -1 before the first
 extern "C" int32_t cz_diag_last_step_mode(cz_handle h) { return h ? h->last_step_mode : -1; }
+// ... and which lean kernel: -1 none (or no launch yet), 0 k_step_lean, 0x100 | R | end_all << 4 | walk_touches << 5 the k_step_lean_cfg
+// with those settings fixed at compile time
+extern "C" int32_t cz_diag_last_step_variant(cz_handle h) { return h ? h->last_step_variant : -1; }
 // diagnostic, not part of cookingzoo.h (tests/test_gpu_instance_edges.py): the kernel instance the handle's launches use,
 // 0 small (Inst<1,1>), 1 large (Inst<2,4>), 2 huge (Inst<4,16>); -1 for a null handle
 extern "C" int32_t cz_diag_instance(cz_handle h) { return h ? h->instance : -1; }

@@ -100,6 +100,70 @@ struct Params {
 static_assert(sizeof(Params) <= 264 && sizeof(Params) % 8 == 0, "argument block: see the note above");
 #endif
 
+// The argument block of the lean one-step kernels (k_step_lean, k_step_lean_cfg): what they read and nothing else, in the order of
+// first use.  Everything the lean traits exclude is gone (marks_out, codes / obs32, seed, T, step0, scheme, A, wide, wt, the spawn bit
+// of auto_reset is never set), and what travels as leading scalars (state, actions, lut, N, RW, W, H, D, dyn0_off, dyn1_off) is not
+// repeated.  Behind the 56 bytes of leading scalars the fields up to `obs` end the second 64-byte line: a wave on the common path -
+// nobody finishes an episode, no recipe mark changes - touches two lines, both with the prologue's loads; the rest is read where it
+// is used (late_params).  A field of the common path in the third line is a cold round trip behind the workgroup's barrier: with R,
+// end_all and walk_touches there as three ints k_step_lean lost 0.07 us per launch (profiles/r19/README.md), so they travel packed
+// in one word of the second line.
+struct LeanParams {
+    const uint32_t *recipes;       // prologue: the env's recipe rows
+    const uint32_t *lay_desc;      //           the descriptor words, a buffer resource over [L][F]
+    int32_t L, F;
+    int32_t max_steps;             // step_env: truncation
+    uint32_t settings;             // k_step_lean only (k_step_lean_cfg has them as template arguments): R | end_all << 8 | walk_touches << 16
+    double reward_idle;
+    double *rewards;               // outputs, as in Params
+    uint8_t *term, *trunc;
+    double *obs;
+    // ---- line 3 and 4: off the common path
+    int32_t auto_reset;            // the reset pass (bit 0; bit 1, despawn / respawn, is never set here)
+    int32_t reserved;
+    uint32_t *stat_u;              // a wave that ends an episode
+    double *stat_f;
+    const uint32_t *lay_init;      // the reset pass
+    int64_t env_id_base;
+    double node_reward, recipe_reward, recipe_penalty, time_penalty_step;   // a recipe mark changed
+#ifdef CZ_PROFILE
+    unsigned long long *stamps;
+#endif
+#ifdef CZ_TIMELINE
+    unsigned long long *timeline;
+#endif
+};
+constexpr int LEADING_SCALAR_BYTES = 56;        // 3 pointers + 7 ints, padded to the block's alignment (StepArgsMirror)
+#if !defined(CZ_TIMELINE) && !defined(CZ_PROFILE)
+static_assert(LEADING_SCALAR_BYTES + sizeof(LeanParams) <= 4 * 64, "the lean argument block: four 64-byte lines with the leading scalars");
+#endif
+static_assert(LEADING_SCALAR_BYTES + offsetof(LeanParams, obs) + sizeof(double *) == 2 * 64, "the common path's fields end the second line");
+// What the shared device functions read through `P` in a lean kernel: the block, the leading scalars, and - as constants, so that a
+// test like `!LEAN && P.wide` still names something - the settings the lean traits fix.
+struct LeanView : LeanParams {
+    uint32_t *state;
+    const int32_t *actions;
+    const double *lut;
+    int32_t N, RW, W, H, D, dyn0_off, dyn1_off;
+    static constexpr int32_t wide = 0, wt = 1, T = 1;
+    static constexpr uint32_t step0 = 0u;
+    static constexpr uint64_t seed = 0u;
+    static constexpr uint8_t *codes = nullptr;
+    int32_t R, end_all, walk_touches;          // unpacked from `settings`
+    LeanView() = default;
+    __host__ __device__ explicit LeanView(const LeanParams &b)
+        : LeanParams(b), R((int32_t)(b.settings & 0xFFu)), end_all((int32_t)((b.settings >> 8) & 1u)), walk_touches((int32_t)((b.settings >> 16) & 1u)) {}
+};
+// ... with the handle's recipe count, end condition and walk_touches fixed as well (k_step_lean_cfg): the names hide the block's fields
+template <int R_, int END_ALL, int WALK_TOUCHES>
+struct LeanViewFixed : LeanView {       // (the names hide LeanView's unpacked fields, which nothing reads then)
+    static_assert(R_ >= 1 && R_ <= 4 && (END_ALL | 1) == 1 && (WALK_TOUCHES | 1) == 1, "no such handle");
+    static constexpr int32_t R = R_, end_all = END_ALL, walk_touches = WALK_TOUCHES;
+    using LeanView::LeanView;
+};
+// the argument block a view is made of
+template <class PB> using block_of = std::conditional_t<std::is_base_of<LeanParams, PB>::value, LeanParams, Params>;
+
 #ifndef CZ_PRIO
 #define CZ_PRIO 1
 #endif

@@ -32,13 +32,20 @@ namespace cz {
 // kernel (~30 SGPRs: spills in the non-fused kernel, ~90 spilled SGPRs in the fused one).
 typedef const __attribute__((address_space(4))) Params *KParams;
 struct StepArgsMirror { uint32_t *a; const int32_t *b; const double *c; int32_t i[8]; Params p; };   // k_step's argument list (7 ints + one of padding)
-__device__ __forceinline__ KParams late_params(unsigned offset) {
+struct LeanArgsMirror { uint32_t *a; const int32_t *b; const double *c; int32_t i[8]; LeanParams p; };   // ... and k_step_lean's / k_step_lean_cfg's
+static_assert(offsetof(LeanArgsMirror, p) == LEADING_SCALAR_BYTES && offsetof(StepArgsMirror, p) == LEADING_SCALAR_BYTES, "leading scalars");
+template <class B> constexpr unsigned block_offset() {
+    return std::is_same<B, LeanParams>::value ? (unsigned)offsetof(LeanArgsMirror, p) : (unsigned)offsetof(StepArgsMirror, p);
+}
+// (B: the block of the kernel that asks - Params or LeanParams)
+template <class B = Params>
+__device__ __forceinline__ const __attribute__((address_space(4))) B *late_params(unsigned offset) {
     const __attribute__((address_space(4))) char *k =
         (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));                      // loads through the result stay behind this point
-    return reinterpret_cast<KParams>(k + offset);
+    return reinterpret_cast<const __attribute__((address_space(4))) B *>(k + offset);
 }
-#define CZ_LATE_STEP() late_params((unsigned)offsetof(StepArgsMirror, p))
+#define CZ_LATE_STEP() late_params<typename V::Block>(block_offset<typename V::Block>())
 
 // The variants of the step kernel: cz::k_step<OPL, CPL, NA, SCHEME, mode> and, for STEP only, cz::k_step_lean<OPL, CPL, NA, SCHEME>.
 // (choose_step in cz_api.hip says which launch gets which; DESIGN.md section 4 has the same table.)
@@ -88,6 +95,14 @@ struct StepTraits {
     // buffer (choose_step in cz_api.hip picks it when all of that holds).  The code is the one-step kernel with those tests folded
     // away: same results, fewer scalar instructions and registers per wave.
     static constexpr bool lean = LEAN;
+    // the argument block of the kernel, and what its device functions read it through (LeanView: the block plus the leading scalars)
+    using Block = std::conditional_t<LEAN, LeanParams, Params>;
+    using View = std::conditional_t<LEAN, LeanView, Params>;
+};
+// k_step_lean_cfg: the lean kernel with the handle's recipe count, end condition and walk_touches fixed too (LeanViewFixed)
+template <int R, int END_ALL, int WALK_TOUCHES>
+struct LeanCfgTraits : StepTraits<STEP, true> {
+    using View = LeanViewFixed<R, END_ALL, WALK_TOUCHES>;
 };
 // (The pieces below the kernel - load_env, all_marks, observe, step_env - are templates over the one or two properties they ask
 // for, fed from the traits by step_kernel: k_reset / k_observe and several variants then share one instance of each, as they always
@@ -147,8 +162,8 @@ typedef uint32_t uint2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t uint4_t __attribute__((ext_vector_type(4)));
 
 // Loads are clamped instead of exec-masked (no branches): every address stays inside the record.
-template <int OPL, int CPL, int NA, bool LEAN = false>
-__device__ __forceinline__ void load_env(const Params &P, Env<OPL, CPL, NA> &e, const Ctx &cx, const uint32_t *__restrict__ rec) {
+template <int OPL, int CPL, int NA, bool LEAN = false, class PB>
+__device__ __forceinline__ void load_env(const PB &P, Env<OPL, CPL, NA> &e, const Ctx &cx, const uint32_t *__restrict__ rec) {
     const uint32_t lane = (uint32_t)cx.lane;
     // header words: wave-uniform, one scalar load (nothing in this kernel writes a record before its loads are done, and the
     // scalar cache is cold at kernel start like every other cache)
@@ -185,8 +200,8 @@ __device__ __forceinline__ void load_env(const Params &P, Env<OPL, CPL, NA> &e, 
 }
 
 // header + agents in one 12-lane store (v_writelane assembles the words), cells / objects only when they changed;
-template <int OPL, int CPL, int NA>
-__device__ __forceinline__ void store_env(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t *__restrict__ rec,
+template <int OPL, int CPL, int NA, class PB>
+__device__ __forceinline__ void store_env(const PB &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t *__restrict__ rec,
                                           bool cells_dirty, bool objs_dirty, bool header_dirty = true) {
     const uint32_t lane = (uint32_t)cx.lane;
     if (header_dirty) {
@@ -227,18 +242,21 @@ __device__ __forceinline__ void store_env(const Params &P, const Env<OPL, CPL, N
 // a constant of the lane, made by the host: 8 r | 4 i << 8; lanes past the rows repeat the last word)
 // (the selector does not depend on the record: step_kernel fetches it with its first loads, load_row_selector, and hands it over -
 // fetched here, behind the wait for the header's `recipes`, it is a second memory round trip in front of the row's load)
-__device__ __forceinline__ uint32_t load_row_selector(const Params &P, int lane) { return ldg<uint32_t>(P.lut, ROWSEL_TABLE_OFFSET + (uint32_t)lane * 4u); }
-__device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t recipes, uint32_t sel) {
+template <class PB>
+__device__ __forceinline__ uint32_t load_row_selector(const PB &P, int lane) { return ldg<uint32_t>(P.lut, ROWSEL_TABLE_OFFSET + (uint32_t)lane * 4u); }
+template <class PB>
+__device__ __forceinline__ uint32_t load_recipe_rows(const PB &P, uint32_t recipes, uint32_t sel) {
     const uint32_t id = (recipes >> (sel & 0xFFu)) & 0xFFu;
     return ldg<uint32_t>(P.recipes, __umul24(id, (1u + MAX_NODES) * 4u) + (sel >> 8));
 }
-__device__ __forceinline__ uint32_t load_recipe_rows(const Params &P, uint32_t recipes, int lane) {
+template <class PB>
+__device__ __forceinline__ uint32_t load_recipe_rows(const PB &P, uint32_t recipes, int lane) {
     return load_recipe_rows(P, recipes, load_row_selector(P, lane));
 }
 
 // every recipe of the env from scratch (reset): sets e.marks (and e.marks_hi for wide tables)
-template <int OPL, int CPL, int NA, bool LEAN = false>
-__device__ __forceinline__ void all_marks(const Params &P, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t rowv, Lds<CPL> &s) {
+template <int OPL, int CPL, int NA, bool LEAN = false, class PB>
+__device__ __forceinline__ void all_marks(const PB &P, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t rowv, Lds<CPL> &s) {
     uint32_t lo = 0, hi = 0;
     if (!LEAN && __builtin_expect(P.wide != 0, 0)) {
 #pragma nounroll
@@ -259,7 +277,8 @@ __device__ __forceinline__ void all_marks(const Params &P, Env<OPL, CPL, NA> &e,
 }
 
 // the per-lane constant of the subtrahend table (observe): word `lane` behind the 256 doubles of the quotient table
-__device__ __forceinline__ uint32_t load_submask(const Params &P, int lane) { return ldg<uint32_t>(P.lut, (uint32_t)(LUT_SIZE * 8 + lane * 4)); }
+template <class PB>
+__device__ __forceinline__ uint32_t load_submask(const PB &P, int lane) { return ldg<uint32_t>(P.lut, (uint32_t)(LUT_SIZE * 8 + lane * 4)); }
 
 // once per kernel and workgroup: the quotient table (thread `tid` of `nthreads`), followed by a workgroup barrier
 __device__ __forceinline__ void init_lut(const Params &P, double *lut, int tid, int nthreads) {
@@ -270,8 +289,8 @@ __device__ __forceinline__ void init_lut(const Params &P, double *lut, int tid, 
 // (the table's words are constants of the lane, load_coord_words: step_kernel fetches them with its first loads and hands them over;
 // k_reset and k_observe, which wait for nothing in front of this, fetch them here)
 template <int CPL> struct CoordWords { uint32_t w[CPL]; };
-template <int CPL>
-__device__ __forceinline__ CoordWords<CPL> load_coord_words(const Params &P, int lane) {
+template <int CPL, class PB>
+__device__ __forceinline__ CoordWords<CPL> load_coord_words(const PB &P, int lane) {
     CoordWords<CPL> cw;
 #pragma unroll
     for (int k = 0; k < CPL; ++k) cw.w[k] = ldg<uint32_t>(P.lut, COORD_TABLE_OFFSET + (uint32_t)(lane + 64 * k) * 4u);
@@ -288,8 +307,8 @@ __device__ __forceinline__ void init_lds(const Ctx &cx, Lds<CPL> &s, const Coord
         img32[(Img<CPL>::CELL0 >> 1) + 2 * c] = cw.w[k];
     }
 }
-template <int CPL>
-__device__ __forceinline__ void init_lds(const Params &P, const Ctx &cx, Lds<CPL> &s) {
+template <int CPL, class PB>
+__device__ __forceinline__ void init_lds(const PB &P, const Ctx &cx, Lds<CPL> &s) {
     const int lane = cx.lane;
     s.img[Img<CPL>::ZERO] = (uint16_t)(LUT_ABSENT * 8);
     uint32_t *img32 = reinterpret_cast<uint32_t *>(s.img);
@@ -304,7 +323,8 @@ __device__ __forceinline__ void init_lds(const Params &P, const Ctx &cx, Lds<CPL
 // Buffer loads over one resource that spans the whole descriptor table (the layout's row is the scalar offset): no clamps, no
 // masks, no branches on F.  Words past the row's F descriptors are the next layout's - valid image offsets like any other,
 // read for nothing since the stores of features past F are out of their row's range - or, behind the table's end, 0.
-__device__ __forceinline__ void load_desc(const Params &P, uint32_t layout, int chunk, int lane, uint32_t (&dsc)[OBS_CHUNK]) {
+template <class PB>
+__device__ __forceinline__ void load_desc(const PB &P, uint32_t layout, int chunk, int lane, uint32_t (&dsc)[OBS_CHUNK]) {
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(P.lay_desc), 0, P.L * P.F * 4, 0x00020000);
     const uint32_t row = layout * (uint32_t)P.F * 4u;                                       // uniform
 #pragma unroll
@@ -333,7 +353,8 @@ __host__ __device__ inline int codes_pitch(int F) { return (F + 15) & ~15; }
 // the descriptor words of this lane's first four features, fetched with the prologue's loads (layout: which row they are of)
 constexpr int CODES_PREFETCH = 2;               // rounds of 256 features (F = 278: both)
 struct CodesPrefetch { uint4_t d[CODES_PREFETCH]; uint32_t layout; };
-__device__ __forceinline__ uint4_t load_desc4(const Params &P, uint32_t layout, uint32_t f) {
+template <class PB>
+__device__ __forceinline__ uint4_t load_desc4(const PB &P, uint32_t layout, uint32_t f) {
     const auto rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(P.lay_desc), 0, P.L * P.F * 4, 0x00020000);
     return __builtin_bit_cast(uint4_t, __builtin_amdgcn_raw_buffer_load_b128(rd, f * 4u, layout * (uint32_t)P.F * 4u, 0));
 }
@@ -343,8 +364,8 @@ __device__ __forceinline__ uint32_t pk_sub_u16(uint32_t a, uint32_t b) {        
 }
 // The LDS image of one env, which every form of the observation is gathered from: objects, cells, agents and the per-observer
 // subtrahend table, up to the wave barrier behind them.
-template <int OPL, int CPL, int NA>
-__device__ __forceinline__ void build_image(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s, uint32_t submask,
+template <int OPL, int CPL, int NA, class PB>
+__device__ __forceinline__ void build_image(const PB &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s, uint32_t submask,
                                             bool objs_changed, bool cells_changed) {
     uint32_t *img32 = reinterpret_cast<uint32_t *>(s.img);
     const uint32_t dead = (uint32_t)(LUT_ABSENT * 8) * 0x10001u;
@@ -453,8 +474,8 @@ __device__ __forceinline__ void write_rows_f32(const Params &P, const Env<OPL, C
 // time - one chunk, no store-flavour switch, no descriptor reload.  F64 = false: the codes-only variant, which carries no float64 path.
 // (The codes loop and the float64 loop stay in this function: moved into functions of their own, 20 of the small instance's 76
 // instruction streams change by an instruction - k_reset, k_observe and some k_step<..., 3 / 5> among them.)
-template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false>
-__device__ __forceinline__ void observe(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
+template <int OPL, int CPL, int NA, bool F64 = true, bool LEAN = false, class PB>
+__device__ __forceinline__ void observe(const PB &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s,
                                         const double *lut, uint32_t (&dsc)[OBS_CHUNK], uint32_t submask, double *__restrict__ out /* [A][F] of this env */,
                                         bool objs_changed = true, bool cells_changed = true, uint8_t *__restrict__ codes = nullptr /* [A][Fp] */,
                                         CodesPrefetch *pre = nullptr) {
@@ -557,8 +578,8 @@ struct StepOut {
 // FUSED (CZ_RARE): the reset pass and the end of an episode are laid out off the fall-through path - one step in max_steps + 1
 // takes them; in the one-step kernels the same hint cost the launches under a cooking policy 1.5 % (profiles/r05/ab_experiments.txt)
 #define CZ_RARE(hint, x) ((hint) ? __builtin_expect(!!(x), 0) : !!(x))
-template <int OPL, int CPL, int NA, int SCHEME, bool FUSED, bool LEAN>
-__device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t acts,
+template <int OPL, int CPL, int NA, int SCHEME, bool FUSED, bool LEAN, class PB>
+__device__ __forceinline__ void step_env(const PB &P, unsigned kp_off, Env<OPL, CPL, NA> &e, const Ctx &cx, uint32_t acts,
                                          int64_t env_global, uint32_t &rowv, Lds<CPL> &lds, uint32_t (&dsc)[OBS_CHUNK], Dirty &dt, StepOut &o) {
     using O = Ops<OPL, CPL, NA, SCHEME>;
     o.myrew = 0.0;
@@ -574,7 +595,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
         if (P.auto_reset & 1) {
             // next-step autoreset: reset() of cooking_env.py:178-210 from the layout pool
             e.episode += 1;
-            const uint32_t *const lay0 = late_params(kp_off)->lay_init;
+            const uint32_t *const lay0 = late_params<block_of<PB>>(kp_off)->lay_init;
             // (the control words are constant while a kernel runs: the host changes them between launches, in stream order)
             typedef const __attribute__((address_space(4))) uint32_t *kconst_u32;
             const kconst_u32 ctl = (kconst_u32)(lay0 - LAY_CTL_WORDS);
@@ -639,7 +660,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
                     const int goals_before = __popc(~mb_r & countmask), goals_after = __popc(~ma & countmask);
                     const bool completed = ma & 1, completion_before = mb_r & 1;
                     const bool malus = !completed && completion_before, bonus = completed && !completion_before;
-                    const KParams kp = late_params(kp_off);
+                    const auto kp = late_params<block_of<PB>>(kp_off);
                     double x = 0.0;
                     x += (double)(goals_before - goals_after) * kp->node_reward;
                     x += (bonus ? 1.0 : 0.0) * kp->recipe_reward;
@@ -680,7 +701,7 @@ __device__ __forceinline__ void step_env(const Params &P, unsigned kp_off, Env<O
                 const int goals_before = __popc(~mb_r & countmask), goals_after = __popc(~ma & countmask);
                 const bool completed = ma & 1, completion_before = mb_r & 1;
                 const bool malus = !completed && completion_before, bonus = completed && !completion_before;
-                const KParams kp = late_params(kp_off);
+                const auto kp = late_params<block_of<PB>>(kp_off);
                 double x = 0.0;
                 x += (double)(goals_before - goals_after) * kp->node_reward;
                 x += (bonus ? 1.0 : 0.0) * kp->recipe_reward;
@@ -765,14 +786,14 @@ __host__ __device__ inline Early early_of(const Params &P) {
 template <int OPL, int CPL, int NA, int SCHEME, class V>
 __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                             int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
-                                            int32_t e_dyn1, const Params &P0) {
+                                            int32_t e_dyn1, const typename V::Block &P0) {
 #ifdef CZ_TIMELINE
     // Timeline build (make timeline -> libcookingzoo_hip_tl.so): the shipped kernel plus two reads of the device-wide 100 MHz
     // clock per wave - at its first instruction and behind its last store - and
     // one 16-byte store of lane 0.  No waits are added in between (unlike the phase stamps of `make prof`).
     const uint64_t tl_in = wall_clock64();
 #endif
-    Params P = P0;
+    typename V::View P{P0};
     P.state = e_state; P.actions = e_actions; P.lut = e_lut; P.N = e_N; P.RW = e_RW; P.W = e_W; P.H = e_H; P.D = e_D;
     P.dyn0_off = e_dyn0; P.dyn1_off = e_dyn1;
     constexpr int EPW = envs_per_wg<CPL>();
@@ -823,7 +844,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     double ret = ldg<double>(retp, ((uint32_t)lane & 3u) * 8u);                                       // running episode return, lane a = agent a
     Env<OPL, CPL, NA> e;
     load_env<OPL, CPL, NA, V::lean>(P, e, cx, rec);
-    if (TABLES_EARLY) init_lds<CPL>(cx, lds, coordw); else init_lds<CPL>(P, cx, lds);
+    if constexpr (TABLES_EARLY) init_lds<CPL>(cx, lds, coordw); else init_lds<CPL>(P, cx, lds);
     uint32_t rowv = TABLES_EARLY ? load_recipe_rows(P, e.recipes, rowsel) : load_recipe_rows(P, e.recipes, lane);
     uint32_t dsc[OBS_CHUNK];
     if (V::f64 && (V::lean || P.obs)) load_desc(P, e.layout, 0, lane, dsc);
@@ -863,8 +884,8 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     for (int t = 0; t < T; ++t) {
         // The fused kernel re-reads its argument block every step (scalar loads that hit the constant cache): nothing of
         // it then stays live across the loop's back edge, which is what used to spill ~90 SGPRs.
-        Params Pt;
-        if (V::fused) {
+        typename V::View Pt;
+        if constexpr (V::fused) {
             static_assert(sizeof(Params) % 8 == 0, "copied as 64-bit words");
             typedef uint64_t __attribute__((may_alias)) word_t;
             const __attribute__((address_space(4))) word_t *src = (const __attribute__((address_space(4))) word_t *)CZ_LATE_STEP();
@@ -892,7 +913,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         } else acts = action_hash(Pt.seed, env_global, lane & 3, Pt.step0 + (uint32_t)t, SCHEME == 3 ? 5u : 8u);
         Dirty dt{};
         StepOut o;
-        step_env<OPL, CPL, NA, SCHEME, V::fused, V::lean>(Pt, (unsigned)offsetof(StepArgsMirror, p), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
+        step_env<OPL, CPL, NA, SCHEME, V::fused, V::lean>(Pt, block_offset<typename V::Block>(), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
 #ifdef CZ_TIMELINE
         tl_dbg |= o.dbg;
 #endif
@@ -903,7 +924,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         // ---- running return (lane a = agent a) and, at episode end only, the per-env statistics
         const double myrew = o.myrew;
         if (o.stepped) ret += myrew;
-        const KParams kp = CZ_LATE_STEP();
+        const auto kp = CZ_LATE_STEP();
         // The statistics are a read-modify-write of words in memory (across launches: device-scope loads, write-through stores,
         // like the record).  A wave that ends an episode issues the loads here and adds / stores behind the encode: the round
         // trip (~1 us after a launch boundary) used to make exactly these waves the last ones of a launch in which nobody acts.
@@ -951,7 +972,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
                 }
             }
         }
-        if (!V::fused && !V::lean) {
+        if constexpr (!V::fused && !V::lean) {
             uint32_t *const marks_out = kp->marks_out;
             if (marks_out && lane < 2) stg<uint32_t>(marks_out, (2u * (uint32_t)env + (uint32_t)lane) * 4u, lane == 0 ? e.marks : e.marks_hi);   // infos["recipe_done"] of the host API
         }
@@ -1031,8 +1052,16 @@ __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) CZ_STEP_ATTR void k_step(u
 template <int OPL, int CPL, int NA, int SCHEME>
 __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
                                                                        int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
-                                                                       int32_t e_dyn1, const Params P0) {
+                                                                       int32_t e_dyn1, const LeanParams P0) {
     step_kernel<OPL, CPL, NA, SCHEME, StepTraits<STEP, true>>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
+}
+// ... with the handle's recipe count, end condition and walk_touches as template arguments (LeanCfgTraits; the combinations that
+// exist: CZ_LEAN_CFGS below)
+template <int OPL, int CPL, int NA, int SCHEME, int R, int END_ALL, int WALK_TOUCHES>
+__global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean_cfg(uint32_t *e_state, const int32_t *e_actions, const double *e_lut, int32_t e_N,
+                                                                           int32_t e_RW, int32_t e_W, int32_t e_H, int32_t e_D, int32_t e_dyn0,
+                                                                           int32_t e_dyn1, const LeanParams P0) {
+    step_kernel<OPL, CPL, NA, SCHEME, LeanCfgTraits<R, END_ALL, WALK_TOUCHES>>(e_state, e_actions, e_lut, e_N, e_RW, e_W, e_H, e_D, e_dyn0, e_dyn1, P0);
 }
 // ---- what the five off-step kernels below share; nothing here is inlined by a step kernel ----
 // the float32 table: every entry of the quotient table rounded to nearest even, staged by one wavefront
@@ -1235,7 +1264,47 @@ __global__ __launch_bounds__(64) void k_restore_where(const Params P, const int3
 }
 
 // launchers exported by each instantiation unit
-struct StepChoice { StepMode mode; bool lean; };       // which variant a launch takes (choose_step, cz_api.hip)
+// cfg: with `lean`, the row of CZ_LEAN_CFGS whose k_step_lean_cfg the launch takes, or -1: k_step_lean
+struct StepChoice { StepMode mode; bool lean; int cfg; };       // which variant a launch takes (choose_step, cz_api.hip)
+// The k_step_lean_cfg kernels of the small instance: X(agents, action scheme, recipes, end_all, walk_touches), nine kernels, all under
+// scheme3.  Two agents - the headline workload and BASELINE configs 3 and 4 are (2, 3, 2, 0, 0) - with every recipe count a handle of
+// two agents can have (cz_create: agents <= recipes <= 4) and both end conditions; one recipe means one agent; walk_touches = 1 where
+// a handle cannot avoid it: more than two agents (cz_load_recipes).
+#define CZ_LEAN_CFGS(X) \
+    X(1, 3, 1, 0, 0) X(1, 3, 1, 1, 0) X(2, 3, 2, 0, 0) X(2, 3, 2, 1, 0) X(2, 3, 3, 0, 0) X(2, 3, 3, 1, 0) X(2, 3, 4, 0, 0) X(2, 3, 4, 1, 0) \
+    X(3, 3, 3, 0, 1)
+struct LeanCfg { int A, scheme, R, end_all, walk_touches; };
+constexpr LeanCfg LEAN_CFGS[] = {
+#define CZ_X(a, s, r, ea, wt) {a, s, r, ea, wt},
+    CZ_LEAN_CFGS(CZ_X)
+#undef CZ_X
+};
+constexpr int N_LEAN_CFGS = (int)(sizeof LEAN_CFGS / sizeof LEAN_CFGS[0]);
+static_assert(N_LEAN_CFGS <= 16, "build time: each row is one more kernel of the small instance");
+// the row a handle's settings select, or -1
+inline int lean_cfg_of(const Params &P) {
+    for (int i = 0; i < N_LEAN_CFGS; ++i) {
+        const LeanCfg &c = LEAN_CFGS[i];
+        if (P.A == c.A && P.scheme == c.scheme && P.R == c.R && P.end_all == c.end_all && P.walk_touches == c.walk_touches) return i;
+    }
+    return -1;
+}
+// the lean block of a launch (choose_step has checked that everything it leaves out is off)
+inline LeanParams lean_block_of(const Params &P) {
+    LeanParams B{};
+    B.recipes = P.recipes; B.lay_desc = P.lay_desc; B.L = P.L; B.F = P.F; B.max_steps = P.max_steps; B.auto_reset = P.auto_reset;
+    B.reward_idle = P.reward_idle; B.rewards = P.rewards; B.term = P.term; B.trunc = P.trunc; B.obs = P.obs;
+    B.settings = (uint32_t)P.R | ((uint32_t)(P.end_all != 0) << 8) | ((uint32_t)(P.walk_touches != 0) << 16);
+    B.stat_u = P.stat_u; B.stat_f = P.stat_f; B.lay_init = P.lay_init; B.env_id_base = P.env_id_base;
+    B.node_reward = P.node_reward; B.recipe_reward = P.recipe_reward; B.recipe_penalty = P.recipe_penalty; B.time_penalty_step = P.time_penalty_step;
+#ifdef CZ_PROFILE
+    B.stamps = P.stamps;
+#endif
+#ifdef CZ_TIMELINE
+    B.timeline = P.timeline;
+#endif
+    return B;
+}
 struct Launchers {
     // lean: k_step_lean (mode STEP, and only where has_lean); otherwise k_step<..., mode>.  Fused modes run P.T steps per launch
     hipError_t (*step)(const Params &, hipStream_t, StepChoice);
@@ -1265,23 +1334,37 @@ inline hipError_t with_scheme(int scheme, F &&f) {
     return scheme == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
 }
 // one launch of a step kernel: one wavefront per env, the leading scalar arguments spelled out for the preload (Early)
-template <int CPL, class K>
-inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) {
+// (`block`: the kernel's by-value block - P itself, or its lean block)
+template <int CPL, class K, class B>
+inline hipError_t launch_step_kernel(K kernel, const Params &P, const B &block_arg, hipStream_t st) {
     constexpr int EPW = envs_per_wg<CPL>();
     const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
     const Early E = early_of(P);
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, P);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, block_arg);
     return hipGetLastError();
 }
+template <int CPL, class K>
+inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) { return launch_step_kernel<CPL>(kernel, P, P, st); }
 
 template <int OPL, int CPL, bool HAS_LEAN = false>
 struct Inst {
     static hipError_t step(const Params &P, hipStream_t st, StepChoice c) {
+        if constexpr (HAS_LEAN) {
+            if (c.lean && c.cfg >= 0) {
+                if (c.cfg != lean_cfg_of(P)) return hipErrorInvalidValue;
+                const LeanParams B = lean_block_of(P);
+                int row = 0;
+#define CZ_X(a, s, r, ea, wt) if (c.cfg == row++) return launch_step_kernel<CPL>(k_step_lean_cfg<OPL, CPL, a, s, r, ea, wt>, P, B, st);
+                CZ_LEAN_CFGS(CZ_X)
+#undef CZ_X
+                return hipErrorInvalidValue;
+            }
+        }
         return with_agents(P.A, [&](auto na) {
             return with_scheme(P.scheme, [&](auto scheme) {
                 constexpr int NA = decltype(na)::value, S = decltype(scheme)::value;
                 if (c.lean) {
-                    if constexpr (HAS_LEAN) return launch_step_kernel<CPL>(k_step_lean<OPL, CPL, NA, S>, P, st);
+                    if constexpr (HAS_LEAN) return launch_step_kernel<CPL>(k_step_lean<OPL, CPL, NA, S>, P, lean_block_of(P), st);
                     return hipErrorInvalidValue;
                 }
                 switch (c.mode) {

@@ -71,5 +71,9 @@ if form in ("step", "cooking"):
     from cooking_zoo_amd import _native
     if getattr(_native.lib(), "cz_diag_last_step_lean", None) is not None and _native.lib().cz_diag_last_step_lean(env._h) == 1:
         kernel = f"k_step_lean<1,1,{A},3>"
+        # ... or one with the handle's recipe count, end condition and walk_touches fixed (cz_diag_last_step_variant: 0x100 | R | ...)
+        v = _native.lib().cz_diag_last_step_variant(env._h) if getattr(_native.lib(), "cz_diag_last_step_variant", None) is not None else 0
+        if v >= 0x100:
+            kernel = f"k_step_lean_cfg<1,1,{A},3,{v & 15},{(v >> 4) & 1},{(v >> 5) & 1}>"
 print(f"{form} instance={inst} steps_per_launch={steps} kernel={kernel}")
 env.close()
