@@ -8,12 +8,11 @@ include/cookingzoo.h; this class only prepares tables (layout pool, recipe table
 from __future__ import annotations
 
 import ctypes as C
-import queue as _queue
 import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, soa
+from cooking_zoo_amd import _native, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -24,33 +23,6 @@ DEFAULT_REWARD_SCHEME = {"recipe_reward": 20, "max_time_penalty": -5, "recipe_pe
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _produce_layouts(q, stop, level_objects, meta, num_agents, dims_tuple, pool_slices, groups, seed, start=0):
-    """Body of the layout-rotation process (CookingVecEnv.rotate_layouts): batch b refills part (start + b) % groups of every
-    level's pool slice (`start` = the part the envs drew from when the rotation began: the first one to be retired); its
-    layouts come from random.Random streams keyed by (seed, b, level), so a run can be replayed."""
-    dims = soa.Dims(*dims_tuple)
-    b = 0
-    while not stop.is_set():
-        g = (start + b) % groups
-        batch = []
-        for li, lv in enumerate(level_objects):
-            base, count = pool_slices[li]
-            sub = count // groups
-            rng = _random.Random((int(seed) * 1000003 + b) * 101 + li)
-            lays = [_ll.instantiate(lv, meta, num_agents, rng) for _ in range(sub)]
-            first = base + g * sub
-            recs = np.stack([l.init_record(dims, first + k) for k, l in enumerate(lays)])
-            desc = np.stack([l.obs_descriptor(meta, dims) for l in lays])
-            batch.append((first, lays, recs, desc))
-        while not stop.is_set():
-            try:
-                q.put(batch, timeout=0.1)
-                break
-            except _queue.Full:
-                pass
-        b += 1
 
 
 class DeviceBuffer:
@@ -272,7 +244,7 @@ class CookingVecEnv:
         self.captured_steps = 0               # steps captured into graphs of the caller (they run at replay, see `advance`)
         self._caller_stream, self._warned_capture = False, False
         self._lay_groups, self._lay_active = 1, 0
-        self._rot = None                      # rotate_layouts state
+        self._rot = None                      # rotate_layouts: the rotation.Rotation while one runs
         self.rotation_events = []             # (step index, "group", groups, active) / (step index, "layouts", first slot, [Layout])
                                               # / (step index, "generated", first slot, count, seed, generation)
         self._programs_for = None             # pool size the level programs on the device were uploaded for (generate_layouts)
@@ -444,76 +416,26 @@ class CookingVecEnv:
             raise ValueError("`every` must be at least max_steps + 3 steps: a part is refilled max_steps + 2 steps after the "
                              "envs stopped drawing from it, and before they draw from it again")
         start = self._lay_active if self._lay_groups == groups else 0        # the part in use now: the first one to be refilled
-        rot = {"groups": int(groups), "every": int(every), "flip_due": self._steps + int(every), "refill_due": None, "n_refills": 0,
-               "blocking": bool(blocking), "start": int(start)}
         if device:
             if self._programs_for != len(self.layouts):
                 self.load_level_programs()
-            rot["device"], rot["seed"] = True, int(seed)
-            self._rot = rot
-            self.set_layout_group(groups, start)
-            return
-
-        # The instantiation is plain Python (engine/load_level.py, the reference's draw order) and takes milliseconds per batch:
-        # in a thread it would hold the interpreter lock against the thread that issues the steps, so it runs in a process of
-        # its own (spawned: a fresh interpreter that never loads the HIP library) and hands finished arrays over a queue.
-        import multiprocessing as _mp
-        ctx = _mp.get_context("spawn")
-        rot["queue"] = ctx.Queue(maxsize=max(1, int(prefetch)))
-        rot["stop"] = ctx.Event()
-        rot["process"] = ctx.Process(target=_produce_layouts, name="cz-layout-rotation", daemon=True,
-                                     args=(rot["queue"], rot["stop"], self.level_objects, self.meta, self.num_agents, self.dims.as_tuple(),
-                                           list(self.pool_slices), int(groups), int(seed), int(start)))
-        # ... and a small thread takes the batches off the process queue (unpickling costs a millisecond) into a local one
-        rot["ready"] = _queue.Queue(maxsize=max(1, int(prefetch)))        # (bounded: when it is full everything upstream sleeps)
-
-        def drain():
-            batch = None
-            while not rot["stop"].is_set():
-                try:
-                    if batch is None:
-                        batch = rot["queue"].get(timeout=0.1)
-                    rot["ready"].put(batch, timeout=0.1)
-                    batch = None
-                except (_queue.Empty, _queue.Full):
-                    pass
-                except (EOFError, OSError):
-                    return
-        import threading as _threading
-        rot["drain"] = _threading.Thread(target=drain, name="cz-layout-rotation-drain", daemon=True)
-        self._rot = rot
-        _native.check(self._h, _native.lib().cz_update_layouts(self._h, 0, 0, None, None))     # copy stream + staging, ahead of time
+            source = _rotation.DeviceRefill(groups, seed)
+        else:
+            _native.check(self._h, _native.lib().cz_update_layouts(self._h, 0, 0, None, None))     # copy stream + staging, ahead of time
+            source = _rotation.ProcessRefill.spawn((self.level_objects, self.meta, self.num_agents, self.dims.as_tuple(),
+                                                    list(self.pool_slices), int(groups), int(seed), int(start)), prefetch, blocking)
+        self._rot = _rotation.Rotation(source, every, groups, start, self._steps)
         self.set_layout_group(groups, start)
-        rot["process"].start()
-        rot["drain"].start()
+        source.start()
 
     def stop_rotation(self):
         if self._rot is not None:
             rot, self._rot = self._rot, None
-            if rot.get("device"):
-                return
-            rot["stop"].set()
-            try:
-                while True:                                   # (a producer blocked on a full queue sees the stop flag within 0.1 s)
-                    rot["queue"].get_nowait()
-            except _queue.Empty:
-                pass
-            rot["drain"].join(timeout=5)
-            rot["process"].join(timeout=10)
-            if rot["process"].is_alive():
-                rot["process"].terminate()
-
-    @staticmethod
-    def _rotation_pending(rot):
-        """a batch still on its way from the producer's queue to the local one"""
-        try:
-            return not rot["queue"].empty()
-        except (OSError, ValueError):
-            return False
+            rot.source.stop()
 
     def rotation_ready(self):
         """refills the background process has ready right now (a measurement may want to start with a full queue)"""
-        return 0 if self._rot is None or self._rot.get("device") else self._rot["ready"].qsize()
+        return 0 if self._rot is None else self._rot.source.ready()
 
     def _issued(self, k):
         """a device-pointer call of k steps has returned: count them - unless the call was CAPTURED into a graph of the caller
@@ -540,45 +462,9 @@ class CookingVecEnv:
     def _advance(self, k):
         """k more env steps have been issued: switch / refill when due"""
         self._steps += int(k)
-        rot = self._rot
-        if rot is None:
+        if self._rot is None:
             return
-        if rot["refill_due"] is not None and self._steps >= rot["refill_due"] and rot.get("device"):
-            g = (rot["start"] + rot["n_refills"]) % rot["groups"]             # the part retired by the last switch
-            for base, count in self.pool_slices:
-                sub = count // rot["groups"]
-                self.generate_layouts(base + g * sub, sub, rot["n_refills"] + 1, seed=rot["seed"], mirror=False)
-            rot["refill_due"] = None
-            rot["n_refills"] += 1
-        if rot["refill_due"] is not None and self._steps >= rot["refill_due"]:
-            batch = None
-            while batch is None:
-                try:
-                    # (blocking: waits for the producer if it is behind - in slices, so that a producer that died is noticed)
-                    batch = rot["ready"].get(timeout=0.25) if rot["blocking"] else rot["ready"].get_nowait()
-                except _queue.Empty:
-                    dead = not rot["process"].is_alive() and rot["ready"].empty() and not self._rotation_pending(rot)
-                    rot["dead_polls"] = rot.get("dead_polls", 0) + 1 if dead else 0   # (twice in a row: a batch may be in the drain thread's hands)
-                    if rot["dead_polls"] >= 2:
-                        code = rot["process"].exitcode
-                        self.stop_rotation()
-                        raise RuntimeError(f"rotate_layouts: the layout producer process died (exit code {code}); rotation stopped, "
-                                           f"the envs keep drawing from part {self._lay_active} of {self._lay_groups}")
-                    if not rot["blocking"]:
-                        return                                              # not ready: next call
-            for first, lays, recs, desc in batch:
-                self._update_layout_arrays(first, lays, recs, desc)
-            rot["refill_due"] = None
-            rot["n_refills"] += 1
-        if rot["refill_due"] is None and self._steps >= rot["flip_due"]:
-            old = self._lay_active
-            if old != (rot["start"] + rot["n_refills"]) % rot["groups"]:      # the part the producer's next batch is made for
-                self.stop_rotation()
-                raise RuntimeError("rotate_layouts: the active layout group was changed behind the rotation's back "
-                                   "(set_layout_group while rotate_layouts runs); rotation stopped")
-            self.set_layout_group(rot["groups"], (old + 1) % rot["groups"])
-            rot["refill_due"] = self._steps + self.max_steps + 2
-            rot["flip_due"] = self._steps + rot["every"]
+        self._rot.advanced(self)
 
     # ------------------------------------------------------------------ reset / step
     def initial_layout_ids(self):
