@@ -105,6 +105,16 @@ class Handle:
         self.close()
 
 
+def strip_golden(rec):
+    """a record as the golden traces can pin it: without the status, layout, episode and pool words (the device's bookkeeping)
+    and the running returns (device-side statistics only)"""
+    r = rec.copy()
+    for w in (soa.W_STATUS, soa.W_LAYOUT, soa.W_EPISODE, soa.W_POOL):
+        r[..., w] = 0
+    r[..., soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
+    return r
+
+
 def handle_for_set(gs, **kw):
     """One env per golden episode of the set, layout i = episode i."""
     eps = gs.episodes

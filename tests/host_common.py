@@ -1,0 +1,150 @@
+"""Helpers of the host tests that GPU tests use as well: the gfx950 code objects inside the built library (`device_code`, a fixture
+a module imports by name: `from host_common import device_code  # noqa: F401`), the numpy models of cz_save_device /
+cz_restore_device's bookkeeping, the reference's despawn / respawn rule for one world, and the user recipes of the custom_wide_*
+golden sets."""
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from cooking_zoo_amd import soa
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(REPO, "include", "cookingzoo.h")
+LIB = os.path.join(REPO, "cooking_zoo_amd", "csrc", "libcookingzoo_hip.so")
+INSTANCES = {"small": (1, 1), "large": (2, 4), "huge": (4, 16)}      # OPL, CPL of cz_inst_*.hip
+LLVM_BIN = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the code objects of the built library
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def code_objects(path):
+    """the gfx950 code objects (ELF images) of every offload bundle in a library built by hipcc"""
+    data = open(path, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    out, at = [], data.find(magic)
+    while at >= 0:
+        (n,) = struct.unpack_from("<Q", data, at + len(magic))
+        p = at + len(magic) + 8
+        for _ in range(n):
+            off, size, tlen = struct.unpack_from("<QQQ", data, p)
+            triple = data[p + 24:p + 24 + tlen].decode()
+            p += 24 + tlen
+            if "gfx950" in triple and size:
+                out.append(data[at + off:at + off + size])
+        at = data.find(magic, at + len(magic))
+    return out
+
+
+@pytest.fixture(scope="module")
+def device_code(tmp_path_factory):
+    """-> (metadata, disassembly): per kernel symbol its .amdgpu_metadata fields and its instruction lines"""
+    readelf, objdump = (shutil.which(t) or os.path.join(LLVM_BIN, t) for t in ("llvm-readelf", "llvm-objdump"))
+    if not (os.path.exists(readelf) and os.path.exists(objdump)):
+        pytest.skip("llvm-readelf / llvm-objdump not found")
+    assert os.path.exists(LIB), "libcookingzoo_hip.so has not been built"
+    objs = code_objects(LIB)
+    assert len(objs) >= 4, f"expected one gfx950 code object per compilation unit, found {len(objs)}"
+    d = tmp_path_factory.mktemp("co")
+    meta, code = {}, {}
+    for i, blob in enumerate(objs):
+        f = str(d / f"unit{i}.co")
+        open(f, "wb").write(blob)
+        notes = subprocess.run([readelf, "--notes", f], capture_output=True, text=True, check=True).stdout
+        for entry in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+            fields = dict(re.findall(r"^\s+\.(\w+):\s+(\S+)\s*$", ".agpr_count:" + entry, flags=re.M))
+            meta[fields["name"]] = fields
+        if b"k_stepILi" not in blob:
+            continue
+        dis = subprocess.run([objdump, "-d", "--no-show-raw-insn", f], capture_output=True, text=True, check=True).stdout
+        for m in re.finditer(r"^[0-9a-f]+ <(_ZN2cz\w+)>:\n(.*?)(?=^\s*$|\Z)", dis, flags=re.S | re.M):
+            code[m.group(1)] = [l.split("//")[0].strip() for l in m.group(2).split("\n") if l.strip()]
+    return meta, code
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the models of save / restore
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def steps_correction(old_status, old_t, new_status, new_t):
+    """what a restore adds to an env's signed correction word SU_STEPS: the old record's t if that episode was still running (its
+    steps stay counted: k_count_aborted's rule), minus the new record's t if this one is (steps that arrive already taken are not
+    this handle's: k_stats_clear's rule).  uint32 arithmetic, read back as int32, like the device's word."""
+    old_status, old_t, new_status, new_t = (np.asarray(x, dtype=np.uint32) for x in (old_status, old_t, new_status, new_t))
+    plus = np.where(old_status & soa.STATUS_DONE, np.uint32(0), old_t)
+    minus = np.where(new_status & soa.STATUS_DONE, np.uint32(0), new_t)
+    return (plus - minus).astype(np.uint32).view(np.int32)
+
+
+def env_steps(su_steps, length_sum, status, t):
+    """cz_get_stats' env_steps from the per-env words (k_stats_chains): the signed correction word, the lengths of the finished
+    episodes, and the steps of the episode in flight"""
+    live = (np.asarray(status) & soa.STATUS_DONE) == 0
+    return int(np.asarray(su_steps, dtype=np.int64).sum() + np.asarray(length_sum, dtype=np.int64).sum()
+               + np.asarray(t, dtype=np.int64)[live].sum())
+
+
+def row_ok(row, dims, n_layouts, n_recipes, recipes_per_env):
+    """cz_set_state's checks of one record: layout id, recipe ids, pool slice, no dead slot with a container tag"""
+    if int(row[soa.W_LAYOUT]) >= n_layouts:
+        return False
+    if any(((int(row[soa.W_RECIPES]) >> (8 * k)) & 0xFF) >= n_recipes for k in range(recipes_per_env)):
+        return False
+    base, count = int(row[soa.W_POOL]) & 0xFFFF, int(row[soa.W_POOL]) >> 16
+    if count and base + count > n_layouts:
+        return False
+    d0, d1 = row[dims.dyn0_word0:dims.dyn0_word0 + dims.D], row[dims.dyn1_word0:dims.dyn1_word0 + dims.D]
+    return not ((((d0 >> 24) & soa.DYN_ALIVE) == 0) & ((d1 & 0xFF) != 0)).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# despawn / respawn of one world; user recipes
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def scalar_rule(book_like, rec, dims, e, step):
+    """handle_agent_spawn for ONE world, written the way the reference writes it (draw only when the `and` chain gets
+    there); state = (active[A], changed[A], grace[A]) lists; returns whether somebody was moved"""
+    from cooking_zoo_amd.spawn import uniform
+    active, grace, changed = book_like["active"], book_like["grace"], book_like["changed"]
+    A = len(active)
+    moved = False
+    for i in range(A):
+        changed[i] = False
+    for i in range(A):
+        if grace[i] > 0:
+            grace[i] -= 1
+            continue
+        if active.count(True) > 1 and active[i] and uniform(book_like["seed"], e, step, i, 0) < book_like["despawn"]:
+            if soa.unpack_agent(rec[soa.AGENT_WORD0 + i])[3] >= 0:
+                continue
+            active[i] = False
+            changed[i] = True
+        elif not active[i] and uniform(book_like["seed"], e, step, i, 1) < book_like["respawn"]:
+            active[i] = True
+            changed[i] = True
+            grace[i] = book_like["grace_period"]
+            moved = True
+    return moved
+
+
+def register_fixture_recipes():
+    """the three recipes of tools/gen_golden.py custom_recipes, built with the build's own classes"""
+    from cooking_zoo_amd.cooking_book import recipe_drawer as rd
+    from cooking_zoo_amd.cooking_book.recipe import Recipe, RecipeNode
+    from cooking_zoo_amd.cooking_world.constants import BlenderFoodStates, ChopFoodStates
+    CH, MA, FRESH_BLEND = ("chop_state", ChopFoodStates.CHOPPED), ("blend_state", BlenderFoodStates.MASHED), ("blend_state", BlenderFoodStates.FRESH)
+    leaf = lambda name, *conds: RecipeNode(root_type=name, id_num=rd.get_next_id(), name=name, conditions=list(conds))
+    plate = lambda *kids: RecipeNode(root_type="Plate", id_num=rd.get_next_id(), name="Plate", contains=list(kids))
+    deliver = lambda *kids: RecipeNode(root_type="Deliversquare", id_num=rd.get_next_id(), name="Deliversquare", contains=list(kids))
+    feast = deliver(plate(leaf("Tomato", CH), leaf("Lettuce", CH), leaf("Apple", CH), leaf("Watermelon", CH)),
+                    plate(leaf("Banana", CH, FRESH_BLEND), leaf("Carrot", MA), leaf("Bread", CH)))
+    picky = deliver(plate(leaf("Banana", CH, FRESH_BLEND)))
+    snack = deliver(plate(leaf("Bread", CH)))
+    for name, root in (("FruitFeast", feast), ("PickyBanana", picky), ("BreadSnack", snack)):
+        rd.register_recipe(Recipe(root, rd.NUM_GOALS, name), name)

@@ -5,6 +5,8 @@ import gzip
 import json
 import os
 
+import numpy as np
+
 from cooking_zoo_amd import soa
 from cooking_zoo_amd.cooking_world.engine import load_level as ll
 from cooking_zoo_amd.cooking_world.layout import feature_length
@@ -16,6 +18,14 @@ CASE_IDS = [f"{c['level']}-A{c['num_agents']}" for c in CASES]
 STRESS_CASES = json.loads(gzip.open(os.path.join(HERE, "golden", "layouts_keyed_stress_ref.json.gz")).read())
 STRESS_IDS = [f"{c['level']}-A{c['num_agents']}" for c in STRESS_CASES]
 LEVELS_DIR = os.path.join(HERE, "levels")
+# tests/golden/layouts_keyed_stress_ref.json.gz: the 15 shipped levels at every agent count their meta files allow, and the stress
+# levels of tests/levels/ - one per way a draw can fail - under keys the device test redraws (test_gpu_layout_generate_matrix.py)
+SHIPPED = {"coop_test": 2, "coexistence_test": 2, "switch_test": 2, "crowded_6x5": 4, "dense_8x8": 4, "edge_8x8": 3, "edge_9x8": 3,
+           "edge_empty": 3, "limit_32x8": 3, "limit_8x31": 3, "large_16x16": 4, "dense_16x16": 4, "huge_objs_16x16": 3,
+           "huge_20x20": 3, "huge_32x32": 4}                               # level -> the Agent count of its meta file
+STRESS = ["stress_object_timeout", "stress_agent_timeout", "stress_second_switch", "stress_counter_overflow", "stress_slots",
+          "stress_meta_cap"]
+FOUR = ["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"]          # the recipes of the device generator's tests: one per agent
 
 
 def case_files(case):
@@ -71,3 +81,16 @@ def failure_kind(message):
         if message.startswith(start):
             return kind
     raise AssertionError(f"an unknown failure: {message!r}")
+
+
+def read_pool(env, slots):
+    """(records, observations) of the env's first len(slots) worlds reset onto pool slots `slots`"""
+    slots = np.asarray(slots, dtype=np.int32)
+    obs = env.reset(layout_ids=slots, env_begin=0, env_count=len(slots))
+    return env.get_state()[:len(slots)], np.array(obs)
+
+
+def host_update(twin, first, layouts):
+    """the model's layouts over the host path; the switch makes the staged copy land before the next call (cz_set_layout_group)"""
+    twin.update_layouts(first, layouts)
+    twin.set_layout_group(1, 0)

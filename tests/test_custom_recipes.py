@@ -10,22 +10,8 @@ import pytest
 from cooking_zoo_amd import soa
 from cooking_zoo_amd.cooking_book import recipe_drawer as rd
 from cooking_zoo_amd.cooking_book.recipe import Recipe, RecipeNode
-from cooking_zoo_amd.cooking_world.constants import BlenderFoodStates, ChopFoodStates
 from golden_io import GoldenSet
-
-
-def register_fixture_recipes():
-    """the three recipes of tools/gen_golden.py custom_recipes, built with the build's own classes"""
-    CH, MA, FRESH_BLEND = ("chop_state", ChopFoodStates.CHOPPED), ("blend_state", BlenderFoodStates.MASHED), ("blend_state", BlenderFoodStates.FRESH)
-    leaf = lambda name, *conds: RecipeNode(root_type=name, id_num=rd.get_next_id(), name=name, conditions=list(conds))
-    plate = lambda *kids: RecipeNode(root_type="Plate", id_num=rd.get_next_id(), name="Plate", contains=list(kids))
-    deliver = lambda *kids: RecipeNode(root_type="Deliversquare", id_num=rd.get_next_id(), name="Deliversquare", contains=list(kids))
-    feast = deliver(plate(leaf("Tomato", CH), leaf("Lettuce", CH), leaf("Apple", CH), leaf("Watermelon", CH)),
-                    plate(leaf("Banana", CH, FRESH_BLEND), leaf("Carrot", MA), leaf("Bread", CH)))
-    picky = deliver(plate(leaf("Banana", CH, FRESH_BLEND)))
-    snack = deliver(plate(leaf("Bread", CH)))
-    for name, root in (("FruitFeast", feast), ("PickyBanana", picky), ("BreadSnack", snack)):
-        rd.register_recipe(Recipe(root, rd.NUM_GOALS, name), name)
+from host_common import register_fixture_recipes
 
 
 @pytest.fixture

@@ -4,21 +4,12 @@ everywhere, the Python layer has the methods, and - read from the gfx950 code ob
 metadata and disassembly - the k_step<..., STEP_F32> kernels exist for all three instance sizes, every agent count and both
 schemes, spill no vector register and write their rows with 16-byte buffer stores."""
 import ctypes as C
-import os
 import re
-import shutil
-import struct
-import subprocess
 
-import pytest
+from host_common import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "cookingzoo.h")
-LIB = os.path.join(REPO, "cooking_zoo_amd", "csrc", "libcookingzoo_hip.so")
 NEW_SYMBOLS = ["cz_step_device_f32", "cz_set_f32_output", "cz_observe_device_f32", "cz_obs_table_f32"]
 STEP_F32 = 6                                                    # cz::StepMode in cz_kernels.h
-INSTANCES = {"small": (1, 1), "large": (2, 4), "huge": (4, 16)}      # OPL, CPL of cz_inst_*.hip
-LLVM_BIN = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
 
 
 def test_header_declares_the_entry_points():
@@ -60,50 +51,6 @@ def test_python_layer_has_the_methods():
         assert "d_obs32" in inspect.signature(cls.observe_device).parameters, cls.__name__
 
 
-def code_objects(path):
-    """the gfx950 code objects (ELF images) of every offload bundle in a library built by hipcc"""
-    data = open(path, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    out, at = [], data.find(magic)
-    while at >= 0:
-        (n,) = struct.unpack_from("<Q", data, at + len(magic))
-        p = at + len(magic) + 8
-        for _ in range(n):
-            off, size, tlen = struct.unpack_from("<QQQ", data, p)
-            triple = data[p + 24:p + 24 + tlen].decode()
-            p += 24 + tlen
-            if "gfx950" in triple and size:
-                out.append(data[at + off:at + off + size])
-        at = data.find(magic, at + len(magic))
-    return out
-
-
-@pytest.fixture(scope="module")
-def device_code(tmp_path_factory):
-    """-> (metadata, disassembly): per kernel symbol its .amdgpu_metadata fields and its instruction lines"""
-    readelf, objdump = (shutil.which(t) or os.path.join(LLVM_BIN, t) for t in ("llvm-readelf", "llvm-objdump"))
-    if not (os.path.exists(readelf) and os.path.exists(objdump)):
-        pytest.skip("llvm-readelf / llvm-objdump not found")
-    assert os.path.exists(LIB), "libcookingzoo_hip.so has not been built"
-    objs = code_objects(LIB)
-    assert len(objs) >= 4, "expected one gfx950 code object per compilation unit"
-    d = tmp_path_factory.mktemp("co")
-    meta, code = {}, {}
-    for i, blob in enumerate(objs):
-        f = str(d / f"unit{i}.co")
-        open(f, "wb").write(blob)
-        notes = subprocess.run([readelf, "--notes", f], capture_output=True, text=True, check=True).stdout
-        for entry in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-            fields = dict(re.findall(r"^\s+\.(\w+):\s+(\S+)\s*$", ".agpr_count:" + entry, flags=re.M))
-            meta[fields["name"]] = fields
-        if b"k_stepILi" not in blob:
-            continue
-        dis = subprocess.run([objdump, "-d", "--no-show-raw-insn", f], capture_output=True, text=True, check=True).stdout
-        for m in re.finditer(r"^[0-9a-f]+ <(_ZN2cz\w+)>:\n(.*?)(?=^\s*$|\Z)", dis, flags=re.S | re.M):
-            code[m.group(1)] = [l.split("//")[0].strip() for l in m.group(2).split("\n") if l.strip()]
-    return meta, code
-
-
 def f32_kernels():
     for inst, (opl, cpl) in INSTANCES.items():
         for na in (1, 2, 3, 4):
@@ -111,7 +58,7 @@ def f32_kernels():
                 yield inst, f"_ZN2cz6k_stepILi{opl}ELi{cpl}ELi{na}ELi{scheme}ELi{STEP_F32}EEEvPjPKiPKdiiiiiiiNS_6ParamsE"
 
 
-def test_every_instance_has_its_float32_step_kernels(device_code):
+def test_every_instance_has_its_float32_step_kernels(device_code):  # noqa: F811
     meta, code = device_code
     missing = [(inst, k) for inst, k in f32_kernels() if k not in meta or k not in code]
     assert not missing, missing
@@ -120,7 +67,7 @@ def test_every_instance_has_its_float32_step_kernels(device_code):
             assert f"_ZN2cz13k_observe_f32ILi{opl}ELi{cpl}ELi{na}EEEvNS_6ParamsElPf" in meta, (opl, cpl, na)
 
 
-def test_float32_kernels_spill_no_vector_register(device_code):
+def test_float32_kernels_spill_no_vector_register(device_code):  # noqa: F811
     meta, _ = device_code
     names = [k for _, k in f32_kernels()] + [k for k in meta if "k_observe_f32" in k]
     assert len(names) == 24 + 12
@@ -128,7 +75,7 @@ def test_float32_kernels_spill_no_vector_register(device_code):
     assert not spills, spills
 
 
-def test_float32_kernels_write_rows_with_16_byte_buffer_stores(device_code):
+def test_float32_kernels_write_rows_with_16_byte_buffer_stores(device_code):  # noqa: F811
     _, code = device_code
     for inst, k in f32_kernels():
         na = int(re.search(r"k_stepILi\d+ELi\d+ELi(\d)E", k).group(1))
@@ -140,7 +87,7 @@ def test_float32_kernels_write_rows_with_16_byte_buffer_stores(device_code):
         assert not [l for l in code[k] if re.match(r"buffer_store_(dword|dwordx2|dwordx3|short|byte)\b", l)], (inst, k)
 
 
-def test_existing_step_kernels_carry_no_float32_path(device_code):
+def test_existing_step_kernels_carry_no_float32_path(device_code):  # noqa: F811
     """the one-step float64 kernel of the headline has its 16-byte stores and nothing of the new stage (same count as the lean one)"""
     _, code = device_code
     k0 = "_ZN2cz6k_stepILi1ELi1ELi2ELi3ELi0EEEvPjPKiPKdiiiiiiiNS_6ParamsE"

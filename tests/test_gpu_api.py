@@ -6,13 +6,11 @@ import random
 import numpy as np
 import pytest
 
+from vec_common import bits
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 TRACES = json.load(open(os.path.join(HERE, "golden", "api_traces.json")))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 @pytest.mark.parametrize("case", TRACES, ids=lambda c: f"{c['kwargs']['level']}-A{c['kwargs']['num_agents']}-{c['kwargs']['action_scheme']}")

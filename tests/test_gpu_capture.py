@@ -4,46 +4,17 @@ times, must leave state and outputs bit for bit what the same launches leave whe
 staged (cz_update_layouts' copy is deferred, never issued from inside the capture).  Reference semantics of every captured step:
 cooking_env.py:243-288."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from cooking_zoo_amd import _native
+from vec_common import CallerStream, bits, buffers, make_env
 
 pytestmark = pytest.mark.gpu
 
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-class Hip:
-    """the few HIP calls a caller's graph needs, from the runtime the step library itself uses"""
-
-    def __init__(self):
-        rccl, hip = C.create_string_buffer(512), C.create_string_buffer(512)
-        _native.lib().cz_runtime_paths(rccl, hip, 512)
-        self.lib = C.CDLL(hip.value.decode())
-        for name in ("hipStreamCreateWithFlags", "hipStreamBeginCapture", "hipStreamEndCapture", "hipGraphInstantiate", "hipGraphLaunch",
-                     "hipStreamSynchronize", "hipGraphExecDestroy", "hipGraphDestroy", "hipStreamDestroy", "hipEventCreate", "hipEventRecord",
-                     "hipEventSynchronize", "hipEventElapsedTime", "hipEventDestroy"):
-            getattr(self.lib, name).restype = C.c_int
-
-    def ck(self, rc, what):
-        assert rc == 0, f"{what} failed with HIP error {rc}"
-
-
-def make(n, **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(action_scheme="scheme3", num_layouts=8, auto_reset=True)
-    args.update(kw)
-    return CookingVecEnv(n, "coop_test", "example", 2, 25, ["TomatoLettuceSalad", "CarrotBanana"], **args)
-
-
-def buffers(env):
-    n, A = env.num_envs, env.num_agents
-    return dict(act=env.alloc((n, A), np.int32), obs=env.alloc((n, A, env.F), np.float64), rew=env.alloc((n, A), np.float64),
-                term=env.alloc((n, A), np.uint8), trunc=env.alloc((n, A), np.uint8), codes=env.alloc((n, A, env.codes_pitch), np.uint8))
+make = functools.partial(make_env, max_steps=25)
 
 
 def closed_loop_eager(env, b, steps, compact):
@@ -59,16 +30,14 @@ def closed_loop_eager(env, b, steps, compact):
 @pytest.mark.parametrize("compact", [False, True])
 @pytest.mark.parametrize("mode", [0, 1, 2])                       # hipStreamCaptureModeGlobal / ThreadLocal / Relaxed
 def test_step_captured_into_a_callers_graph_replays_bit_exact(compact, mode):
-    hip = Hip()
     n, K, R = 1024, 8, 200
     env, ref = make(n), make(n)
     be, br = buffers(env), buffers(ref)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
     for e, b in ((env, be), (ref, br)):
         e.reset(return_obs=False)
         e.observe_device(b["obs"], b["codes"])                        # the first observation, on the device, in both forms
-    env.set_stream(stream)
+    cs = CallerStream(env)
+    hip, stream, gexec = cs.hip, cs.stream, cs.gexec                   # (the timed replays at the end)
     # a staged layout update at capture time: the pool cut in two, the inactive half rewritten while a long rollout still runs -
     # cz_update_layouts cannot copy yet, and the captured steps must not try to (hipEventQuery / copies invalidate a capture)
     for e in (env, ref):
@@ -76,16 +45,11 @@ def test_step_captured_into_a_callers_graph_replays_bit_exact(compact, mode):
     env.rollout(1500, 7, 0); ref.rollout(1500, 7, 0)
     fresh = env.layouts[4:8][::-1]
     env.update_layouts(4, fresh); ref.update_layouts(4, fresh)
-    L, h = _native.lib(), env._h
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, mode), "hipStreamBeginCapture")
-    closed_loop_eager(env, be, K, compact)                             # K x [policy, step]: captured, not executed
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    with cs.capture(mode):
+        closed_loop_eager(env, be, K, compact)                         # K x [policy, step]: captured, not executed
     t_before = env.get_state()[:, 0].copy()                            # (outside the capture: also flushes the staged update)
-    for _ in range(R):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.replay(R)
+    cs.sync()
     ref.sync()
     assert np.array_equal(t_before, ref.get_state()[:, 0]), "capturing must not have stepped anything"
     closed_loop_eager(ref, br, K * R, compact)
@@ -107,16 +71,13 @@ def test_step_captured_into_a_callers_graph_replays_bit_exact(compact, mode):
     print(f"\nreplayed closed loop in the caller's graph ({'codes' if compact else 'float64'}, {n} envs, capture mode {mode}): "
           f"{ms.value * 1e3 / (K * R):.2f} us per step")
     hip.lib.hipEventDestroy(ev0); hip.lib.hipEventDestroy(ev1)
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()
 
 
 def test_ring_runs_and_rollouts_inside_a_capture():
     """cz_step_device_ring inside a caller's capture goes out as plain launches (no nested capture), cz_rollout_actions as its one
     fused launch; what must not be captured says so"""
-    hip = Hip()
     n, A, period = 512, 2, 8
     env, ref = make(n), make(n)
     be, br = buffers(env), buffers(ref)
@@ -124,31 +85,24 @@ def test_ring_runs_and_rollouts_inside_a_capture():
     de, dr = env.alloc((period, n, A), np.int32), ref.alloc((period, n, A), np.int32)
     de.from_host(ring); dr.from_host(ring)
     env.reset(return_obs=False); ref.reset(return_obs=False)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
+    cs = CallerStream(env)
     _native.check(env._h, _native.lib().cz_update_layouts(env._h, 0, 0, None, None))   # (count 0: creates the copy stream, outside the capture)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    env.step_device_ring(12, de, n * A, period, 3, be["obs"], be["rew"], be["term"], be["trunc"])
-    env.rollout_actions(de, period, None, None, None, None)
-    with pytest.raises(_native.NativeError, match="not inside a stream capture"):
-        env.set_layout_group(2, 1)
-    with pytest.raises(_native.NativeError, match="not inside a stream capture"):
-        env.update_layouts(0, env.layouts[:2])
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    with cs.capture():
+        env.step_device_ring(12, de, n * A, period, 3, be["obs"], be["rew"], be["term"], be["trunc"])
+        env.rollout_actions(de, period, None, None, None, None)
+        with pytest.raises(_native.NativeError, match="not inside a stream capture"):
+            env.set_layout_group(2, 1)
+        with pytest.raises(_native.NativeError, match="not inside a stream capture"):
+            env.update_layouts(0, env.layouts[:2])
     for _ in range(5):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
+        cs.replay()
         ref.step_device_ring(12, dr, n * A, period, 3, br["obs"], br["rew"], br["term"], br["trunc"])
         ref.rollout_actions(dr, period, None, None, None, None)
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.sync()
     ref.sync()
     assert np.array_equal(env.get_state(), ref.get_state())
     assert np.array_equal(bits(be["obs"].to_host()), bits(br["obs"].to_host()))
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()
 
 
@@ -157,7 +111,6 @@ def test_rotating_pool_under_replays_of_a_callers_graph():
     switch / refill schedule) does not move at capture time; the caller reports every replay with `advance(K)`, and the pool then
     rotates exactly as under eager launches of the same steps: same events at the same step numbers, same final records."""
     import warnings
-    hip = Hip()
     n, A, K, R = 256, 2, 10, 60
     env, ref = make(n, num_layouts=16, layout_seed=11), make(n, num_layouts=16, layout_seed=11)
     be, br = buffers(env), buffers(ref)
@@ -165,27 +118,22 @@ def test_rotating_pool_under_replays_of_a_callers_graph():
     de, dr = env.alloc((K, n, A), np.int32), ref.alloc((K, n, A), np.int32)
     de.from_host(ring); dr.from_host(ring)
     env.reset(return_obs=False); ref.reset(return_obs=False)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
+    cs = CallerStream(env)
     for e in (env, ref):
         e.rotate_layouts(50, groups=2, seed=3, prefetch=2)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        env.step_device_ring(K, de, n * A, K, 0, be["obs"], be["rew"], be["term"], be["trunc"])
-        with pytest.raises(RuntimeError, match="inside a stream capture"):
-            env.advance(K)
-    assert any("advance(k)" in str(x.message) for x in w)
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    with cs.capture():
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            env.step_device_ring(K, de, n * A, K, 0, be["obs"], be["rew"], be["term"], be["trunc"])
+            with pytest.raises(RuntimeError, match="inside a stream capture"):
+                env.advance(K)
+        assert any("advance(k)" in str(x.message) for x in w)
     assert env._steps == 0 and env.captured_steps == K and len(env.rotation_events) == 1      # (the initial cut of the pool into parts)
     for _ in range(R):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
+        cs.replay()
         env.advance(K)
         ref.step_device_ring(K, dr, n * A, K, 0, br["obs"], br["rew"], br["term"], br["trunc"])
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.sync()
     ref.sync()
     assert env._steps == ref._steps == K * R
     sig = lambda evs: [(e[0], e[1], e[2], e[3] if e[1] == "group" else [l.key() for l in e[3]]) for e in evs]
@@ -193,8 +141,6 @@ def test_rotating_pool_under_replays_of_a_callers_graph():
     assert sum(e[1] == "group" for e in env.rotation_events) >= 10 and sum(e[1] == "layouts" for e in env.rotation_events) >= 8
     assert np.array_equal(env.get_state(), ref.get_state())
     assert np.array_equal(bits(be["obs"].to_host()), bits(br["obs"].to_host()))
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
     env.stop_rotation(); ref.stop_rotation()
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()

@@ -8,42 +8,9 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from vec_common import OBS_CASES as CASES, bits, make_env as make, strip
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def make(n, level, meta, agents, recipes, scheme, max_steps=30, **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(action_scheme=scheme, num_layouts=8, auto_reset=True)
-    args.update(kw)
-    return CookingVecEnv(n, level, meta, agents, max_steps, recipes, **args)
-
-
-CASES = [
-    ("scheme3", "coop_test", 2, ["TomatoLettuceSalad", "CarrotBanana"], "example"),
-    ("scheme3", "coop_test", 2, ["TomatoLettuceSalad", "CarrotBanana"], "example_odd"),          # F = 283: not a multiple of 4
-    ("scheme1", "switch_test", 2, ["MashedCarrotBanana", "TomatoSalad"], "example"),
-    ("scheme3", "coexistence_test", 1, ["TomatoLettuceOnionSalad"], "example"),
-    ("scheme3", "crowded_6x5", 4, ["TomatoSalad", "TomatoLettuceSalad", "no_recipe", "MashedCarrotBanana"], "crowded_6x5"),
-    ("scheme1", "crowded_6x5", 3, ["TomatoSalad", "TomatoLettuceSalad", "MashedCarrotBanana"], "crowded_6x5"),
-    ("scheme3", "large_16x16", 4, ["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"], "large_16x16"),
-    ("scheme1", "dense_16x16", 2, ["TomatoLettuceOnionSalad", "MashedCarrotBanana"], "dense_16x16"),
-    ("scheme3", "edge_8x8", 3, ["TomatoSalad", "MashedCarrotBanana", "TomatoLettuceSalad"], "edge"),
-    ("scheme3", "limit_32x8", 3, ["TomatoSalad", "MashedCarrotBanana", "TomatoLettuceSalad"], "limits"),
-    ("scheme3", "limit_8x31", 2, ["TomatoSalad", "CarrotBanana"], "limits"),
-    ("scheme3", "huge_20x20", 3, ["TomatoLettuceSalad", "MashedCarrotBanana", "TomatoSalad"], "huge_20x20"),
-    ("scheme1", "huge_32x32", 4, ["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"], "huge_32x32"),
-]
 
 
 @pytest.mark.parametrize("scheme,level,agents,recipes,meta", CASES)

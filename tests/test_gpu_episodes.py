@@ -4,7 +4,6 @@ episodes_common.py, which walks the oracle's per-step rewards, flags and records
 the packed list byte for byte - and every output array is pre-filled with a sentinel and guarded behind its end.  The conditions
 that keep a test from passing vacuously (episodes ended, both ways to end, agents gone, several episodes inside one launch) are
 asserted on the model's run, never on the device's."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -13,36 +12,17 @@ import pytest
 from cooking_zoo_amd import _native, soa
 from episodes_common import EP, Collector, EpisodeModel, same_entries
 from fuzz_policy import BumperActions
+from host_common import register_fixture_recipes
 from oracle_binding import VecOracle
-from test_gpu_instance_edges import _diag, instance, last_lean
+from vec_common import (COOP as COOP12, TWO, CallerStream, env_of as make, instance, last_lean, last_mode, oracle_reset, strip,
+                        tables_of)
 
 pytestmark = pytest.mark.gpu
 
-TWO = ["TomatoLettuceSalad", "CarrotBanana"]
 WIDE = ["FruitFeast", "PickyBanana", "BreadSnack", "FruitFeast"]
-COOP = dict(level="coop_test", meta="example", agents=2, recipes=TWO, scheme="scheme3", max_steps=5, num_layouts=3)
+COOP = dict(COOP12, max_steps=5)
 STEP, ROLLOUT_ACTIONS, STEP_CODES, STEP_F32, ROLLOUT_F32 = 0, 2, 3, 6, 7       # StepMode, cz_kernels.h
 EP_BLOCK = 256                                                                # k_episodes_collect's block size (cz_api.hip)
-
-
-def last_mode(env):
-    return _diag(env, "cz_diag_last_step_mode")
-
-
-def tables_of(n, level, meta, agents, recipes, scheme, max_steps, num_layouts, **kw):
-    from cooking_zoo_amd.vec_env import BatchTables
-    return BatchTables(n, level, meta, agents, max_steps, recipes, action_scheme=scheme, num_layouts=num_layouts, **kw)
-
-
-def make(tables, auto_reset=True):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    return CookingVecEnv(tables.num_envs, tables=tables, auto_reset=auto_reset)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
 
 
 class Run:
@@ -144,7 +124,6 @@ def test_every_kernel_family_writes_the_row(name, level, meta, agents, recipes, 
     """N = 11: one full workgroup and a partial one (8 envs per workgroup; the huge instance: two full ones and a partial one)"""
     if name == "wide":                                                  # the user recipes of test_custom_recipes.py: a graph of 10 nodes
         from cooking_zoo_amd.cooking_book import recipe_drawer as rd
-        from test_custom_recipes import register_fixture_recipes
         assert not rd.RECIPE_STORE
         register_fixture_recipes()
     try:
@@ -243,7 +222,6 @@ def kat_tables(n, max_steps, wide):
     gs = GoldenSet("kat_c3")
     ep = gs.episodes[0]
     if wide:
-        from test_custom_recipes import register_fixture_recipes
         assert not rd.RECIPE_STORE
         register_fixture_recipes()
         for name in gs.cfg["recipes"]:                                  # (a user store replaces the default book: the dish goes in too)
@@ -320,7 +298,6 @@ def test_an_agent_truncated_by_despawn_produces_no_record():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_frozen_envs_masked_resets_and_reset_stats():
-    from test_gpu_reset_device import oracle_reset
     n = 11
     t = tables_of(n, **COOP)                                            # max_steps = 5: everybody starts together and ends at step 5
     r = Run(t, auto_reset=False, seed=3)
@@ -383,7 +360,6 @@ def test_frozen_envs_masked_resets_and_reset_stats():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_packed_list_order_capacity_and_guards():
-    from test_gpu_reset_device import oracle_reset
     n = 2 * EP_BLOCK + 37
     ms = 6
     t = tables_of(n, **dict(COOP, max_steps=ms))
@@ -506,8 +482,6 @@ def test_finished_episodes_host_form():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_step_and_collect_inside_a_callers_capture():
-    from test_gpu_capture import Hip
-    hip = Hip()
     n, R = 300, 24
     t = tables_of(n, **dict(COOP, max_steps=5, num_layouts=8))
     env, ref = make(t), make(t)
@@ -529,14 +503,9 @@ def test_step_and_collect_inside_a_callers_capture():
     be, br = B(env), B(ref)
     for e in (env, ref):
         e.reset(return_obs=False)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    issue(env, be)                                                      # [step, collect]: captured, not executed
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    cs = CallerStream(env)
+    with cs.capture():
+        issue(env, be)                                                  # [step, collect]: captured, not executed
     assert last_mode(env) == STEP_F32
     assert np.array_equal(env.get_state(), ref.get_state()), "capturing must not have stepped anything"
     total = 0
@@ -544,8 +513,8 @@ def test_step_and_collect_inside_a_callers_capture():
         acts = rng.integers(0, env.n_actions, (n, env.num_agents)).astype(np.int32)
         be.act.from_host(acts); br.act.from_host(acts)
         be.col.fill(); br.col.fill()
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-        hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+        cs.replay()
+        cs.sync()
         issue(ref, br)
         g, w = be.col.read(), br.col.read()
         for name in g:
@@ -553,9 +522,7 @@ def test_step_and_collect_inside_a_callers_capture():
         total += int(w["count"][0])
     assert total >= 3 * n
     assert np.array_equal(env.get_state(), ref.get_state()) and env.stats()["episodes"] == total
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()
 
 

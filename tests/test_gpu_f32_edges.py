@@ -28,36 +28,13 @@ import pytest
 from cooking_zoo_amd import soa
 from fuzz_policy import BumperActions, EventCounter
 from oracle_binding import VecOracle
-from test_gpu_f32_obs import SENTINEL, GuardedRows, want32
-from test_gpu_instance_edges import (DENSE_RECIPES, PADDED, TWO, instance, junk, make, one_world_trajectory, policy, run_compact, strip,
-                                     widen)
+from vec_common import (CROWDED4, DENSE_RECIPES, HUGE3, PADDED, SENTINEL, TWO, GuardedRows, Sensitivity, bits, instance, junk, make_env,
+                        one_world_trajectory, policy, run_compact, strip, want32, widen)
 
 pytestmark = pytest.mark.gpu
 
-MIN_INEXACT = 0.05
-CROWDED4 = ["TomatoSalad", "TomatoLettuceSalad", "no_recipe", "MashedCarrotBanana"]
-HUGE3 = ["TomatoLettuceSalad", "MashedCarrotBanana", "TomatoSalad"]
+make = functools.partial(make_env, max_steps=40)
 CORE_EVENTS = ["pick_up", "put_down", "chop", "plate_add", "static_accepts", "delivery", "marks_changed", "truncation"]
-
-
-def bits64(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-class Sensitivity:
-    """share of the expected elements whose float64 value is not a float32: what makes the comparison sensitive to the rounding"""
-
-    def __init__(self):
-        self.inexact = self.total = 0
-
-    def add(self, want64):
-        w = np.asarray(want64, dtype=np.float64)
-        self.inexact += int((w.astype(np.float32).astype(np.float64) != w).sum())
-        self.total += w.size
-
-    def check(self, ctx):
-        share = self.inexact / max(self.total, 1)
-        assert share >= MIN_INEXACT, f"{ctx}: only {self.inexact} of {self.total} expected elements are inexact in float32"
 
 
 class Outs32:
@@ -89,7 +66,7 @@ def check32(ctx, got, want):
     assert not len(bad), f"{ctx}: float32 rows differ at (env, agent, feature) {bad[:6].tolist()}" \
                          f"{' - sentinel left' if (rows == SENTINEL).any() else ''}"
     if rew is not None:
-        assert np.array_equal(bits64(rew), bits64(want[1])), f"{ctx}: rewards"
+        assert np.array_equal(bits(rew), bits(want[1])), f"{ctx}: rewards"
     if term is not None:
         assert np.array_equal(term, want[2]), f"{ctx}: terminations"
     if trunc is not None:
@@ -445,7 +422,7 @@ def test_three_unequal_shards_equal_one_handle():
         for got, single, want in zip(s_out, o_out, (ro, to, uo)):
             g, s = got.to_host(), single.to_host()
             assert np.array_equal(g.view(np.uint8), s.view(np.uint8)), t
-            assert np.array_equal(bits64(g), bits64(want)) if g.dtype == np.float64 else np.array_equal(g, want), t
+            assert np.array_equal(bits(g), bits(want)) if g.dtype == np.float64 else np.array_equal(g, want), t
     assert np.array_equal(strip(three.get_state()), orc.records) and np.array_equal(strip(one.get_state()), orc.records)
     assert int(orc.records[:, soa.W_EPISODE].min()) >= 1
     one.close()

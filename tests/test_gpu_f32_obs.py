@@ -10,43 +10,10 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import _native, soa
-from test_gpu_compact_obs import CASES, make, strip
+from host_common import register_fixture_recipes
+from vec_common import GUARD, OBS_CASES as CASES, SENTINEL, CallerStream, GuardedRows, bits, make_env as make, strip, want32
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x7FC0BEEF            # a quiet NaN no table entry equals
-GUARD = 1024                     # float32 words behind the last row
-
-
-def bits64(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def want32(obs64):
-    """what the float32 rows must hold, as uint32"""
-    return np.ascontiguousarray(obs64, dtype=np.float64).astype(np.float32).view(np.uint32)
-
-
-class GuardedRows:
-    """float32 rows [n][A][F] with GUARD sentinel words behind the last one"""
-
-    def __init__(self, env, n=None):
-        self.n = env.num_envs if n is None else n
-        self.shape = (self.n, env.num_agents, env.F)
-        self.words = int(np.prod(self.shape))
-        self.buf = env.alloc((self.words + GUARD,), np.uint32)
-        self.ptr = self.buf.ptr
-        self.fill()
-
-    def fill(self):
-        self.buf.from_host(np.full(self.words + GUARD, SENTINEL, dtype=np.uint32))
-
-    def rows(self):
-        """the rows as uint32 [n][A][F]; asserts the guard is untouched"""
-        got = self.buf.to_host()
-        assert (got[self.words:] == SENTINEL).all(), "a store went past the last row"
-        return got[:self.words].reshape(self.shape)
-
 
 def test_the_cases_are_the_thirteen_of_the_compact_test():
     assert len(CASES) == 13 and any(c[4] == "example_odd" for c in CASES)
@@ -79,14 +46,14 @@ def test_float32_rows_are_the_rounded_oracle_observation(scheme, level, agents, 
         oo, ro, to, uo = orc.step(acts)
         got = rows.rows()
         assert np.array_equal(got, want32(oo)), f"float32 observation at step {t}"
-        assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)), f"rewards at step {t}"
+        assert np.array_equal(bits(d_rew.to_host()), bits(ro)), f"rewards at step {t}"
         assert np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), f"flags at step {t}"
         # the twin walks the same trajectory; every third step through float64 rows, checked against the oracle too
         w_act.from_host(acts)
         twin.step_device(w_act, w_obs if t % 3 == 0 else None, None, None, None)
         if t % 3 == 0:
             twin.sync()
-            assert np.array_equal(bits64(w_obs.to_host()), bits64(oo)), f"float64 observation of the twin at step {t}"
+            assert np.array_equal(bits(w_obs.to_host()), bits(oo)), f"float64 observation of the twin at step {t}"
             assert np.array_equal(strip(twin.get_state()), orc.records) and np.array_equal(strip(env.get_state()), orc.records), t
     assert np.array_equal(strip(env.get_state()), orc.records)
     assert int(env.get_state()[:, soa.W_EPISODE].min()) >= 1          # reset passes were encoded too
@@ -114,7 +81,7 @@ def test_despawn_respawn_on_a_mixed_level_batch():
         env.sync()
         oo, ro, to, uo = orc.step(acts)
         assert np.array_equal(rows.rows(), want32(oo)), t
-        assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
+        assert np.array_equal(bits(d_rew.to_host()), bits(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
         gone_seen += int((((orc.records[:, soa.W_STATUS] >> 8) & 0xF) != 0).sum())
     assert np.array_equal(strip(env.get_state()), orc.records) and gone_seen > 100
     env.close()
@@ -124,7 +91,6 @@ def test_wide_user_book():
     """graphs of more than 8 nodes (custom_wide_* recipes: wide tables, marks in record words 1 and 7)"""
     from cooking_zoo_amd.cooking_book import recipe_drawer as rd
     from oracle_binding import VecOracle
-    from test_custom_recipes import register_fixture_recipes
     assert not rd.RECIPE_STORE
     register_fixture_recipes()
     try:
@@ -144,7 +110,7 @@ def test_wide_user_book():
             env.sync()
             oo, ro, to, uo = orc.step(acts)
             assert np.array_equal(rows.rows(), want32(oo)), t
-            assert np.array_equal(bits64(d_rew.to_host()), bits64(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
+            assert np.array_equal(bits(d_rew.to_host()), bits(ro)) and np.array_equal(d_t.to_host(), to) and np.array_equal(d_u.to_host(), uo), t
         assert np.array_equal(strip(env.get_state()), orc.records)
         env.close()
     finally:
@@ -182,12 +148,12 @@ def test_ring_runs_with_the_float32_output_set_on_the_handle(K, graph):
             oo, ro, to, uo = orc.step(ring_host[k % period], k == K - 1)
         step += K
         if obs is not None:
-            assert np.array_equal(bits64(d_obs.to_host()), bits64(oo)), phase
+            assert np.array_equal(bits(d_obs.to_host()), bits(oo)), phase
             assert (rows.rows() == SENTINEL).all() and (other.rows() == SENTINEL).all(), phase
         else:
             assert np.array_equal(f32.rows(), want32(oo)), phase
             assert ((other if f32 is rows else rows).rows() == SENTINEL).all(), phase
-        assert np.array_equal(bits64(outs[0].to_host()), bits64(ro)) and np.array_equal(outs[2].to_host(), uo), phase
+        assert np.array_equal(bits(outs[0].to_host()), bits(ro)) and np.array_equal(outs[2].to_host(), uo), phase
         assert np.array_equal(strip(env.get_state()), orc.records), phase
     env.close()
 
@@ -243,7 +209,7 @@ def test_first_observation_as_float32_after_reset_and_set_state(scheme, level, a
     d_obs = env.alloc((40, agents, env.F), np.float64)
     env.observe_device(d_obs, None, env_begin=17, env_count=40, d_obs32=part)       # both forms in one call
     env.sync()
-    assert np.array_equal(part.rows(), want32(oo[17:57])) and np.array_equal(bits64(d_obs.to_host()), bits64(oo[17:57]))
+    assert np.array_equal(part.rows(), want32(oo[17:57])) and np.array_equal(bits(d_obs.to_host()), bits(oo[17:57]))
     env.close()
 
 
@@ -298,7 +264,7 @@ def test_host_step_with_the_float32_output_set():
         acts = rng.integers(0, 5, size=(n, A), dtype=np.int32)
         _, rg, tg, ug = env.step(acts, return_obs=False)
         oo, ro, to, uo = orc.step(acts)
-        assert np.array_equal(rows.rows(), want32(oo)) and np.array_equal(bits64(rg), bits64(ro)) and np.array_equal(ug, uo), t
+        assert np.array_equal(rows.rows(), want32(oo)) and np.array_equal(bits(rg), bits(ro)) and np.array_equal(ug, uo), t
     env.close()
 
 
@@ -349,8 +315,6 @@ def test_two_shards_on_one_device_equal_one_handle():
 def test_step_device_f32_captured_into_a_callers_graph_replays_bit_exact():
     """[a host-prepared action ring -> cz_step_device_f32] x K captured with hipStreamBeginCapture on the caller's stream: replays do
     what the same launches do eagerly on the twin, and capturing steps nothing"""
-    from test_gpu_capture import Hip
-    hip = Hip()
     n, A, K, R = 512, 2, 8, 25
     env, ref = (make(n, "coop_test", "example", A, ["TomatoLettuceSalad", "CarrotBanana"], "scheme3", max_steps=25) for _ in range(2))
     ring_host = np.random.default_rng(12).integers(0, 5, size=(K, n, A), dtype=np.int32)
@@ -362,22 +326,16 @@ def test_step_device_f32_captured_into_a_callers_graph_replays_bit_exact():
         bufs.append(dict(ring=ring, rows=GuardedRows(e), rew=e.alloc((n, A), np.float64), term=e.alloc((n, A), np.uint8),
                          trunc=e.alloc((n, A), np.uint8)))
     be, br = bufs
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
+    cs = CallerStream(env)
     slot = lambda b, k: b["ring"].ptr + k * n * A * 4
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    for k in range(K):
-        env.step_device_f32(slot(be, k), be["rows"], be["rew"], be["term"], be["trunc"])
-    env.observe_device(d_obs32=be["rows"])                         # (a pure launch as well; rewrites the rows it finds)
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    with cs.capture():
+        for k in range(K):
+            env.step_device_f32(slot(be, k), be["rows"], be["rew"], be["term"], be["trunc"])
+        env.observe_device(d_obs32=be["rows"])                     # (a pure launch as well; rewrites the rows it finds)
     assert env._steps == 0 and env.captured_steps == K
     assert (env.get_state()[:, soa.W_T] == 0).all(), "capturing must not have stepped anything"
-    for _ in range(R):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.replay(R)
+    cs.sync()
     for _ in range(R):
         for k in range(K):
             ref.step_device_f32(slot(br, k), br["rows"], br["rew"], br["term"], br["trunc"])
@@ -387,10 +345,7 @@ def test_step_device_f32_captured_into_a_callers_graph_replays_bit_exact():
     for k in ("rew", "term", "trunc"):
         assert np.array_equal(be[k].to_host().view(np.uint8), br[k].to_host().view(np.uint8)), k
     assert env.stats() == ref.stats() and env.stats()["episodes"] > n
-    hip.lib.hipGraphExecDestroy(gexec)
-    hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close()
     ref.close()
 
@@ -449,7 +404,7 @@ def test_every_call_writes_the_outputs_it_names_and_no_others():
     state = {"steps": 0}
 
     def codes_ok(codes, oo):
-        return np.array_equal(bits64(table[codes[..., :F]]), bits64(oo)) and (codes[..., F:] == 255).all()
+        return np.array_equal(bits(table[codes[..., :F]]), bits(oo)) and (codes[..., F:] == 255).all()
 
     def expect(what, oracle, named, host=None):
         """`named`: the device buffers the call wrote (all of rew / term / trunc with "outs"); `host`: what a host step returned"""
@@ -460,10 +415,10 @@ def test_every_call_writes_the_outputs_it_names_and_no_others():
             elif key in ("call_codes", "set_codes"):
                 assert codes_ok(B[key].get(), oo), (what, key)
             elif key == "obs":
-                assert np.array_equal(B[key].get(), bits64(oo)), (what, key)
+                assert np.array_equal(B[key].get(), bits(oo)), (what, key)
             else:
                 assert key == "outs"
-                assert np.array_equal(B["rew"].get(), bits64(ro)) and np.array_equal(B["term"].get(), to) and np.array_equal(B["trunc"].get(), uo), what
+                assert np.array_equal(B["rew"].get(), bits(ro)) and np.array_equal(B["term"].get(), to) and np.array_equal(B["trunc"].get(), uo), what
         written = set(named) - {"outs"} | ({"rew", "term", "trunc"} if "outs" in named else set())
         for key, buf in B.items():
             if key not in written:
@@ -471,9 +426,9 @@ def test_every_call_writes_the_outputs_it_names_and_no_others():
             buf.fill()
         if host is not None:
             og, cg, rg, tg, ug = host
-            assert og is None or np.array_equal(bits64(og), bits64(oo)), what
+            assert og is None or np.array_equal(bits(og), bits(oo)), what
             assert cg is None or codes_ok(cg, oo), what
-            assert np.array_equal(bits64(rg), bits64(ro)) and np.array_equal(tg, to) and np.array_equal(ug, uo), what
+            assert np.array_equal(bits(rg), bits(ro)) and np.array_equal(tg, to) and np.array_equal(ug, uo), what
         state["steps"] += 1
         assert np.array_equal(strip(env.get_state()), orc.records), what
 

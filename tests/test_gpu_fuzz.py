@@ -12,16 +12,19 @@ the common ones in the default handful).
 
 Default: a handful of cases (seconds).  CZ_FUZZ_CASES=N widens it for one-off soak runs (200 cases are about
 37 M env-steps); CZ_FUZZ_FIRST=K starts at case K (cases are a function of their index: earlier soaks covered 0 ... 1499)."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
-from test_gpu_f32_obs import GuardedRows, want32
-from test_gpu_rollout import bits, make, oracle_for, strip
+from host_common import register_fixture_recipes
+from vec_common import GuardedRows, bits, make_env, oracle_for, strip, want32
 
 pytestmark = pytest.mark.gpu
+
+make = functools.partial(make_env, num_layouts=16)          # coop_test, two agents, 30 steps; 16 layouts
 
 LEVELS = [("coop_test", "example", 2), ("coexistence_test", "example", 2), ("switch_test", "example", 2),
           ("large_16x16", "large_16x16", 4), ("crowded_6x5", "crowded_6x5", 4), ("edge_8x8", "edge", 3),
@@ -43,8 +46,8 @@ def draw_case(i):
     if rng.random() < 0.5:
         reward = {"recipe_reward": float(rng.integers(1, 30)), "max_time_penalty": float(-rng.integers(0, 9)),
                   "recipe_penalty": float(-rng.integers(0, 50)), "recipe_node_reward": float(rng.integers(0, 4))}
-    kw = dict(level=level, meta_file=meta, num_agents=agents, recipes=recipes,
-              action_scheme="scheme3" if rng.random() < 0.6 else "scheme1", max_steps=int(rng.integers(5, 260)),
+    kw = dict(level=level, meta=meta, agents=agents, recipes=recipes,
+              scheme="scheme3" if rng.random() < 0.6 else "scheme1", max_steps=int(rng.integers(5, 260)),
               end_condition_all_dishes=bool(rng.random() < 0.3), reward_scheme=reward,
               num_layouts=int(rng.integers(1, 40)), layout_seed=int(rng.integers(1 << 20)))
     seed = int(rng.integers(1 << 30))
@@ -81,7 +84,6 @@ def test_random_configuration_matches_oracle(i):
     kw, seed, extra = draw_case(i)
     if extra["wide"]:
         from cooking_zoo_amd.cooking_book import recipe_drawer as rd
-        from test_custom_recipes import register_fixture_recipes
         assert not rd.RECIPE_STORE
         register_fixture_recipes()
     try:
@@ -99,7 +101,7 @@ def run_case(i, kw, seed, extra):
     orc.reset()
     if extra["wide"]:
         assert env.recipe_nodes == 16
-    A = kw["num_agents"]
+    A = kw["agents"]
     chunk = T // 3
     d_rew = env.alloc((chunk, n, A), np.float64)
     d_term = env.alloc((chunk, n, A), np.uint8)
@@ -137,7 +139,7 @@ def run_case(i, kw, seed, extra):
         assert np.array_equal(bits(env.observe()), bits(oo)), ctx
     # ... and on from there with one launch per step and actions from the host (the other kernel variant)
     rng = np.random.default_rng(seed)
-    n_act = 5 if kw["action_scheme"] == "scheme3" else 8
+    n_act = 5 if kw["scheme"] == "scheme3" else 8
     table = env.obs_table()
     for t in range(25):
         acts = rng.integers(0, n_act, size=(n, A), dtype=np.int32)
@@ -230,7 +232,6 @@ def test_biased_actions_match_oracle(i):
     kw, seed, extra = draw_case(i)
     if extra["wide"]:
         from cooking_zoo_amd.cooking_book import recipe_drawer as rd
-        from test_custom_recipes import register_fixture_recipes
         assert not rd.RECIPE_STORE
         register_fixture_recipes()
     try:
@@ -250,7 +251,7 @@ def run_biased_case(i, kw, seed):
     orc = oracle_for(env)
     env.reset(return_obs=False)
     orc.reset()
-    A, F = kw["num_agents"], env.F
+    A, F = kw["agents"], env.F
     ctx = f"biased case {i}: {kw}"
     rng = np.random.default_rng(seed ^ 0x5EED)
     pol = BumperActions(env.dims, env.scheme_class.CODE, rng)

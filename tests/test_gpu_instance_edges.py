@@ -13,113 +13,24 @@ marks are asked for.  Here:
   * which kernel a launch took at F = 384 | 385 and N = 1 | 9 | 10 240 | 10 241, and with null reward / flag outputs.
 Every output buffer is filled with 0xFF bytes before a launch, so a feature or flag the kernel leaves unwritten cannot pass
 for a value written earlier.  cz_diag_instance / cz_diag_last_step_lean say which instance and kernel ran."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-from cooking_zoo_amd import _native, soa
-from fuzz_policy import BumperActions
+from cooking_zoo_amd import soa
 from oracle_binding import ShardedOracle, VecOracle
+from vec_common import (DENSE_RECIPES, PADDED, Outs, bits, check_step, instance, junk, last_lean, make_env, one_world_trajectory, policy,
+                        run_compact, strip, widen)
 
 pytestmark = pytest.mark.gpu
 
-TWO = ["TomatoLettuceSalad", "CarrotBanana"]
-DENSE_RECIPES = ["TomatoSalad", "no_recipe", "TomatoLettuceSalad", "CarrotBanana"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def _diag(env, name):
-    f = getattr(_native.lib(), name)
-    f.restype, f.argtypes = C.c_int32, [C.c_void_p]
-    return int(f(env._h))
-
-
-def instance(env):
-    return _diag(env, "cz_diag_instance")
-
-
-def last_lean(env):
-    return _diag(env, "cz_diag_last_step_lean")
-
-
-def make(n, level="coop_test", meta="example", agents=2, recipes=TWO, scheme="scheme3", max_steps=40, **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(action_scheme=scheme, num_layouts=8, auto_reset=True)
-    args.update(kw)
-    return CookingVecEnv(n, level, meta, agents, max_steps, recipes, **args)
-
-
-def policy(env, seed):
-    return BumperActions(env.dims, env.scheme_class.CODE, np.random.default_rng(seed))
-
-
-def junk(shape, dtype):
-    """0xFF in every byte: NaN for float64, 255 for flags"""
-    return np.full(int(np.prod(shape)) * np.dtype(dtype).itemsize, 0xFF, np.uint8).view(dtype).reshape(shape)
-
-
-def widen(recs, dn, dd):
-    """records of dims dn laid out for dims dd (more slots): shared words copied, every further slot and padding word zero"""
-    out = np.zeros((recs.shape[0], dd.RW), dtype=np.uint32)
-    out[:, :dn.dyn0_word0] = recs[:, :dn.dyn0_word0]
-    out[:, dd.dyn0_word0:dd.dyn0_word0 + dn.D] = recs[:, dn.dyn0_word0:dn.dyn0_word0 + dn.D]
-    out[:, dd.dyn1_word0:dd.dyn1_word0 + dn.D] = recs[:, dn.dyn1_word0:dn.dyn1_word0 + dn.D]
-    return out
-
-
-class Outs:
-    """one-step device outputs (None for those in `skip`: the launch gets a null pointer); step() fills them with junk first"""
-
-    def __init__(self, env, skip=()):
-        n, A, F = env.num_envs, env.num_agents, env.F
-        spec = dict(obs=((n, A, F), np.float64), rew=((n, A), np.float64), term=((n, A), np.uint8), trunc=((n, A), np.uint8))
-        self.act = env.alloc((n, A), np.int32)
-        self.buf = {k: None if k in skip else env.alloc(s, t) for k, (s, t) in spec.items()}
-        self.junk = {k: junk(s, t) for k, (s, t) in spec.items()}
-
-    def fill(self):
-        for k, b in self.buf.items():
-            if b is not None:
-                b.from_host(self.junk[k])
-
-    def get(self):
-        return tuple(None if self.buf[k] is None else self.buf[k].to_host() for k in ("obs", "rew", "term", "trunc"))
-
-    def step(self, env, acts):
-        self.fill()
-        self.act.from_host(acts)
-        b = self.buf
-        env.step_device(self.act, b["obs"], b["rew"], b["term"], b["trunc"])
-        return self.get()
-
-
-def check_step(ctx, got, want):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if g is None:
-            continue
-        if k < 2:
-            bad = np.argwhere(bits(g) != bits(w))
-            assert not len(bad), f"{ctx}: {('observation', 'reward')[k]} differs at {bad[:6].tolist()}"
-        else:
-            assert np.array_equal(g, w), f"{ctx}: {('terminations', 'truncations')[k - 2]}"
+make = functools.partial(make_env, max_steps=40)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # one world on every instance
 # ---------------------------------------------------------------------------------------------------------------------------
-
-PADDED = [(None, 0), (64, 0), (65, 1), (128, 1), (129, 2), (255, 2)]       # (max_dyn, instance); None: the level's own D = 12
-
 
 def run_step_device(env, acts, want, dn):
     o = Outs(env)
@@ -146,45 +57,6 @@ def run_rollout_actions(env, acts, want, dn, chunks=2):
             check_step(f"D={env.dims.D} cz_rollout_actions chunk {c} step {t}", [x[t] for x in outs], want[c * Tc + t])
         assert np.array_equal(strip(env.get_state()), widen(want[(c + 1) * Tc - 1][4], dn, env.dims)), f"D={env.dims.D} chunk {c}: records"
     return env.stats()
-
-
-def run_compact(env, acts, want, dn):
-    n, A, F, Fp = env.num_envs, env.num_agents, env.F, env.codes_pitch
-    table = env.obs_table()
-    o = Outs(env, skip=("obs",))
-    d_codes = env.alloc((n, A, Fp), np.uint8)
-    for t, a in enumerate(acts):
-        ctx = f"D={env.dims.D} cz_step_device_compact step {t}"
-        o.fill()
-        d_codes.from_host(np.full((n, A, Fp), 7, np.uint8))             # (a real code: 255 would read as 0.0, the padding value)
-        o.act.from_host(a)
-        b = o.buf
-        env.step_device_compact(o.act, d_codes, b["rew"], b["term"], b["trunc"])
-        codes = d_codes.to_host()
-        assert (codes[:, :, F:] == 255).all(), f"{ctx}: padding bytes"
-        check_step(ctx, (table[codes[:, :, :F]],) + o.get()[1:], want[t])
-        assert np.array_equal(strip(env.get_state()), widen(want[t][4], dn, env.dims)), f"{ctx}: records"
-    return env.stats()
-
-
-def one_world_trajectory(scheme, n, T):
-    """the coop_test world at its natural D = 12 under the state-aware policy, auto-resets included (max_steps 40): the dims, the
-    reset observation and records, the actions [T][n][A], per step (observation, rewards, terminations, truncations, records),
-    and the fewest episodes an env has finished"""
-    base = make(n, scheme=scheme)
-    dn = base.dims
-    assert dn.D == 12
-    orc = VecOracle.from_vec_env(base)
-    obs0 = orc.reset()
-    rec0 = strip(orc.records)
-    pol = policy(base, 31 if scheme == "scheme3" else 37)
-    acts, want = [], []
-    for t in range(T):
-        acts.append(pol.act(orc.records))
-        want.append(tuple(x.copy() for x in orc.step(acts[-1])) + (strip(orc.records),))
-        pol.observe_result(orc.records)
-    base.close()
-    return dn, obs0, rec0, np.stack(acts), want, int(orc.records[:, soa.W_EPISODE].min())
 
 
 @pytest.mark.parametrize("scheme", ["scheme3", "scheme1"])

@@ -32,9 +32,9 @@ import pytest
 from cooking_zoo_amd import soa
 from fuzz_policy import BumperActions
 from oracle_binding import VecOracle
-from test_gpu_f32_obs import SENTINEL, GuardedRows, want32
-from test_gpu_instance_edges import Outs, _diag, bits, check_step, instance, junk, last_lean, make, strip, widen
-from test_gpu_lean_step import lean
+from host_common import register_fixture_recipes
+from vec_common import (SENTINEL, GuardedRows, Outs, bits, check_step, instance, junk, last_lean, last_mode, lean, make_env as make, strip,
+                        want32, widen)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,10 +59,6 @@ PASS_B = dict(name="B", recipes=["FruitFeast", "PickyBanana", "BreadSnack", "Fru
 
 LEDGER = {}               # (instance, agents, scheme) -> {(mode, lean)} over both passes; a cell enters when it starts
 TERMINATIONS = {}         # (instance, agents, scheme) -> terminations of the oracle's pass A
-
-
-def last_mode(env):
-    return _diag(env, "cz_diag_last_step_mode")
 
 
 def rotated(k):
@@ -380,7 +376,6 @@ def run_pass(ps, cell, seen):
 @pytest.mark.parametrize("cell", range(len(CELLS)), ids=[f"inst{i}-{a}agents-{s}" for i, a, s in CELLS])
 def test_every_variant_of_the_cell_matches_the_oracle(cell):
     from cooking_zoo_amd.cooking_book import recipe_drawer as rd
-    from test_custom_recipes import register_fixture_recipes
     inst = CELLS[cell][0]
     all_modes = {(mode, 0) for _, mode in VARIANTS}
     LEDGER[CELLS[cell]] = set()

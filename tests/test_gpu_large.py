@@ -5,12 +5,14 @@
   small-batch tests never reach that branch, so it is pinned here twice: by forcing either flavour on small batches of
   every level family (CZ_WT=0/1/2, read at cz_create) and by running configs 3, 4 (one rank's shard) and 5 at full size.
 * The oracle runs threaded (tests/oracle_binding.ShardedOracle); every comparison is bit for bit."""
+import functools
 import os
 
 import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from vec_common import bits, make_env, strip
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +20,7 @@ BOOK = ["TomatoSalad", "TomatoLettuceSalad", "TomatoLettuceOnionSalad", "CarrotB
         "CucumberOnion", "AppleWatermelon", "no_recipe"]
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def make(n, level, meta, agents, recipes, scheme="scheme3", **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(max_steps=30, num_layouts=16, auto_reset=True)
-    args.update(kw)
-    ms = args.pop("max_steps")
-    return CookingVecEnv(n, level, meta, agents, ms, recipes, action_scheme=scheme, **args)
+make = functools.partial(make_env, num_layouts=16)          # 30 steps; 16 layouts
 
 
 FAMILIES = [

@@ -15,11 +15,10 @@ import pytest
 from cooking_zoo_amd import _native, soa
 from cooking_zoo_amd.cooking_world.engine import level_program as lp
 from cooking_zoo_amd.cooking_world.engine import load_level as ll
-from layout_keyed_common import CASES, CASE_IDS, assert_matches_reference, case_tables
+from layout_keyed_common import CASES, CASE_IDS, FOUR, assert_matches_reference, case_tables, host_update, read_pool
+from vec_common import CallerStream, bits, buffers, strip
 
 pytestmark = pytest.mark.gpu
-
-FOUR = ["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"]
 
 
 @pytest.fixture(autouse=True)
@@ -30,16 +29,6 @@ def time_limit():
     faulthandler.cancel_dump_traceback_later()
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0          # running returns: device-side statistics only
-    return r
-
-
 def prefilled(n, level, meta, agents, *, pool, max_dyn=None, max_steps=30, **kw):
     """a batch whose whole pool holds ONE fixed, valid, recognisable layout per level: the host loader's draw under Random(99)"""
     from cooking_zoo_amd.vec_env import CookingVecEnv
@@ -48,19 +37,6 @@ def prefilled(n, level, meta, agents, *, pool, max_dyn=None, max_steps=30, **kw)
     fixed = [[ll.instantiate(ll.load_level_file(l), m, agents, random.Random(99))] * pool for l in levels]
     return CookingVecEnv(n, level, meta, agents, max_steps, FOUR[:max(agents, 1)], action_scheme="scheme3", layouts=fixed,
                          max_dyn=max_dyn, auto_reset=True, **kw)
-
-
-def read_pool(env, slots):
-    """(records, observations) of the env's first len(slots) worlds reset onto pool slots `slots`"""
-    slots = np.asarray(slots, dtype=np.int32)
-    obs = env.reset(layout_ids=slots, env_begin=0, env_count=len(slots))
-    return env.get_state()[:len(slots)], np.array(obs)
-
-
-def host_update(twin, first, layouts):
-    """the model's layouts over the host path; the switch makes the staged copy land before the next call (cz_set_layout_group)"""
-    twin.update_layouts(first, layouts)
-    twin.set_layout_group(1, 0)
 
 
 def check_pool(env, twin, expected):
@@ -283,8 +259,6 @@ def test_device_rotation_is_bit_exact_and_needs_no_process():
 def test_generate_steps_and_switch_captured_in_one_graph():
     """[cz_generate_layouts of the retired part, K steps, cz_set_layout_group] twice - once per part of the pool - captured on a
     stream of the caller and replayed: state, outputs and pool equal the same calls issued directly"""
-    from test_gpu_capture import Hip, buffers
-    hip = Hip()
     n, A, K, K2, period, R = 256, 2, 10, 30, 40, 5                      # K2 >= max_steps + 2: a part is retired before it is redrawn
 
     def make():
@@ -296,13 +270,11 @@ def test_generate_steps_and_switch_captured_in_one_graph():
     ring = np.random.default_rng(5).integers(0, 5, size=(period, n, A), dtype=np.int32)
     de, dr = env.alloc((period, n, A), np.int32), ref.alloc((period, n, A), np.int32)
     de.from_host(ring); dr.from_host(ring)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
     for e in (env, ref):
         e.reset(return_obs=False)
         e.load_level_programs()
         e.set_layout_group(2, 0)
-    env.set_stream(stream)
+    cs = CallerStream(env)
 
     def round_trip(e, d, b):
         for part in (1, 0):
@@ -310,27 +282,22 @@ def test_generate_steps_and_switch_captured_in_one_graph():
             e.step_device_ring(K, d, n * A, period, 0, b["obs"], b["rew"], b["term"], b["trunc"])
             e.set_layout_group(2, part)
             e.step_device_ring(K2, d, n * A, period, K, b["obs"], b["rew"], b["term"], b["trunc"])
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    round_trip(env, de, be)
-    with pytest.raises(_native.NativeError, match="not inside a stream capture"):
-        env.set_layout_group(4, 0)                                        # a new cut is not a pure launch
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    with cs.capture():
+        round_trip(env, de, be)
+        with pytest.raises(_native.NativeError, match="not inside a stream capture"):
+            env.set_layout_group(4, 0)                                    # a new cut is not a pure launch
     assert np.array_equal(env.get_state()[:, soa.W_T], ref.get_state()[:, soa.W_T]), "capturing must not have stepped anything"
     for _ in range(R):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
+        cs.replay()
         round_trip(ref, dr, br)
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.sync()
     ref.sync()
     assert np.array_equal(env.get_state(), ref.get_state())
     assert env.stats() == ref.stats() and env.stats()["episodes"] > n
     for k in ("obs", "rew", "term", "trunc"):
         assert np.array_equal(be[k].to_host().view(np.uint8), br[k].to_host().view(np.uint8)), k
     assert env.generate_failures() == ref.generate_failures() == 0
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     # the pools: equal, and what the model says
     want, _ = env.keyed_layouts(0, 8, 4, 1)
     want += env.keyed_layouts(8, 8, 4, 2)[0]

@@ -26,9 +26,9 @@ import pytest
 from cooking_zoo_amd import _native, soa
 from cooking_zoo_amd.cooking_world.engine import level_program as lp
 from cooking_zoo_amd.cooking_world.engine import load_level as ll
-from layout_keyed_common import (KINDS, STRESS_CASES, STRESS_IDS, assert_matches_reference, case_files, case_tables, failure_kind,
-                                 reference_misfit)
-from test_gpu_layout_generate import FOUR, bits, host_update, read_pool
+from layout_keyed_common import (FOUR, KINDS, SHIPPED, STRESS, STRESS_CASES, STRESS_IDS, assert_matches_reference, case_files, case_tables,
+                                 failure_kind, host_update, read_pool, reference_misfit)
+from vec_common import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -290,7 +290,6 @@ MIXED_FLOOR = (17, 78)                                                     # (fa
 def test_zz_the_floors_cover_every_level_agent_count_and_failure_kind():
     """the coverage table the cases above assert: every case of the fixture is one of them, every shipped level at every agent
     count, every stress level at 1 .. 3 agents, and each of the six failure kinds with floors above zero on both sides"""
-    from test_layout_keyed import SHIPPED, STRESS
     cases = {(c["level"], c["num_agents"]) for c in STRESS_CASES}
     assert cases == {(l, a) for l, n in SHIPPED.items() for a in range(1, n + 1)} | {(l, a) for l in STRESS for a in (1, 2, 3)}
     assert set(FLOORS) <= cases

@@ -6,24 +6,13 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from vec_common import bits, make_env, strip
 
 pytestmark = pytest.mark.gpu
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0          # running returns: device-side statistics only
-    return r
-
-
 def make(n, max_steps, num_layouts):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    return CookingVecEnv(n, "coop_test", "example", 2, max_steps, ["TomatoLettuceSalad", "CarrotBanana"], action_scheme="scheme3",
-                         num_layouts=num_layouts, layout_seed=11, auto_reset=True)
+    return make_env(n, max_steps=max_steps, num_layouts=num_layouts, layout_seed=11)
 
 
 def test_rotating_pool_is_bit_exact_and_uses_new_layouts():

@@ -8,8 +8,8 @@ Observations, rewards, flags, records and statistics are compared bit for bit; c
 -1 not a lean kernel, 0 k_step_lean, 0x100 | R | end_all << 4 | walk_touches << 5 a k_step_lean_cfg.  The golden episodes of
 BASELINE configs 1 and 2 - dishes are delivered and terminate episodes there, so the reward of a changed recipe mark runs with R
 fixed - are replayed through the same kernels.  The last test counts the rows that ran."""
-import contextlib
 import ctypes as C
+import functools
 import os
 import re
 
@@ -18,10 +18,12 @@ import pytest
 
 from cooking_zoo_amd import _native, soa
 from golden_io import GoldenSet
-from gpu_common import handle_for_set
-from test_gpu_rollout import bits, make, oracle_for, strip
+from gpu_common import handle_for_set, strip_golden
+from vec_common import bits, lean, make_env, oracle_for, strip
 
 pytestmark = pytest.mark.gpu
+
+make = functools.partial(make_env, num_layouts=16)          # coop_test, two agents, 30 steps; 16 layouts
 
 HEADER = os.path.join(os.path.dirname(os.path.abspath(_native.__file__)), "csrc", "cz_kernels.h")
 
@@ -40,20 +42,6 @@ BOOK = ["TomatoLettuceSalad", "CarrotBanana", "TomatoSalad", "MashedCarrotBanana
 LEVEL = {1: ("coop_test", "example"), 2: ("coop_test", "example"), 3: ("edge_8x8", "edge"), 4: ("crowded_6x5", "crowded_6x5")}
 
 
-@contextlib.contextmanager
-def lean(enabled):
-    """CZ_LEAN is read by cz_create: the handles made inside take (or never take) a lean kernel"""
-    old = os.environ.get("CZ_LEAN")
-    os.environ["CZ_LEAN"] = "1" if enabled else "0"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["CZ_LEAN"]
-        else:
-            os.environ["CZ_LEAN"] = old
-
-
 def variant(h):
     L = _native.lib()
     L.cz_diag_last_step_variant.restype = C.c_int32
@@ -68,7 +56,7 @@ def code(R, end_all, walk_touches):
 def run_against_oracle(n, agents, scheme, R, end_all, expect, T=12, max_steps=3):
     """T steps of one handle with a lean kernel, one with CZ_LEAN=0 and the oracle; -> the variants the lean handle reported"""
     level, meta = LEVEL[agents]
-    kw = dict(level=level, meta_file=meta, num_agents=agents, recipes=BOOK[:R], action_scheme="scheme%d" % scheme, max_steps=max_steps,
+    kw = dict(level=level, meta=meta, agents=agents, recipes=BOOK[:R], scheme="scheme%d" % scheme, max_steps=max_steps,
               num_layouts=2, end_condition_all_dishes=bool(end_all))
     with lean(True):
         ea = make(n, **kw)
@@ -176,14 +164,6 @@ def replay(gs, enabled):
     st = h.stats()
     h.close()
     return out, st, seen
-
-
-def strip_golden(rec):
-    r = rec.copy()
-    for w in (soa.W_STATUS, soa.W_LAYOUT, soa.W_EPISODE, soa.W_POOL):
-        r[..., w] = 0
-    r[..., soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
 
 
 # (under "all dishes" no golden episode delivers both dishes: its deliveries are rewarded, nothing terminates)

@@ -4,48 +4,26 @@ launch_step picks the lean kernel when the handle's settings allow it (narrow re
 observations of at most 384 features with write-through stores, no compact output, no marks buffer).  Both kernels must give
 the same observations, rewards, flags, records and statistics bit for bit: every golden set replayed through cz_step_device by
 both, and a few hundred steps of the state-aware fuzz policy on the small-instance levels, also checked against the oracle."""
-import contextlib
 import ctypes as C
-import os
+import functools
 
 import numpy as np
 import pytest
 
-from cooking_zoo_amd import _native, soa
 from fuzz_policy import BumperActions
 from golden_io import GoldenSet, golden_sets
-from gpu_common import handle_for_set
-from test_gpu_rollout import bits, make, oracle_for, strip
+from gpu_common import handle_for_set, strip_golden
+from vec_common import bits, last_lean, lean, make_env, oracle_for, strip
 
 pytestmark = pytest.mark.gpu
 
-
-@contextlib.contextmanager
-def lean(enabled):
-    """CZ_LEAN is read by cz_create: the handles made inside take (or never take) the lean kernel"""
-    old = os.environ.get("CZ_LEAN")
-    os.environ["CZ_LEAN"] = "1" if enabled else "0"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["CZ_LEAN"]
-        else:
-            os.environ["CZ_LEAN"] = old
+make = functools.partial(make_env, num_layouts=16)          # coop_test, two agents, 30 steps; 16 layouts
 
 
-def last_lean(L, h):
+def handle_last_lean(L, h):
     L.cz_diag_last_step_lean.restype = C.c_int32
     L.cz_diag_last_step_lean.argtypes = [C.c_void_p]
     return int(L.cz_diag_last_step_lean(h))
-
-
-def strip_golden(rec):
-    r = rec.copy()
-    for w in (soa.W_STATUS, soa.W_LAYOUT, soa.W_EPISODE, soa.W_POOL):
-        r[..., w] = 0
-    r[..., soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
 
 
 def replay_device(gs, enabled):
@@ -65,7 +43,7 @@ def replay_device(gs, enabled):
                 acts[i] = ep.actions[t]
         h.h2d(d_act, acts)
         h.ck(h.L.cz_step_device(h.h, C.c_void_p(d_act), C.c_void_p(d_obs), C.c_void_p(d_rew), C.c_void_p(d_term), C.c_void_p(d_trunc)))
-        flags.add(last_lean(h.L, h.h))
+        flags.add(handle_last_lean(h.L, h.h))
         out.append((h.get_state(), h.d2h(d_obs, (n, A, F), np.float64), h.d2h(d_rew, (n, A), np.float64),
                     h.d2h(d_term, (n, A), np.uint8), h.d2h(d_trunc, (n, A), np.uint8)))
     st = h.stats()
@@ -115,7 +93,7 @@ FUZZ = [
 def test_fuzz_lean_and_generic(scheme, level, agents, recipes, meta, max_steps):
     """300 steps of the biased fuzz policy with next-step auto-reset; lean vs generic byte for byte, lean vs the oracle"""
     n, T = 64, 300
-    kw = dict(level=level, meta_file=meta, num_agents=agents, recipes=recipes, action_scheme=scheme, max_steps=max_steps,
+    kw = dict(level=level, meta=meta, agents=agents, recipes=recipes, scheme=scheme, max_steps=max_steps,
               num_layouts=24, end_condition_all_dishes=level == "crowded_6x5")
     with lean(True):
         ea = make(n, **kw)
@@ -134,7 +112,7 @@ def test_fuzz_lean_and_generic(scheme, level, agents, recipes, meta, max_steps):
             d_act.from_host(acts)
             e.step_device(d_act, *o)
             outs.append([b.to_host() for b in o] + [e.get_state()])
-        assert last_lean(_native.lib(), ea._h) == 1
+        assert last_lean(ea) == 1
         for k, (u, v) in enumerate(zip(*outs)):
             assert u.tobytes() == v.tobytes(), f"step {t}: output {k} differs between the lean and the generic kernel"
         oo, ro, to, uo = orc.step(acts)
@@ -165,7 +143,7 @@ def test_bench_workload_takes_lean_kernel():
         env.rollout(300, 3, 0)                       # (worlds a few hundred steps old, like the bench's timed regions)
         env.step_device_ring(K, d_ring, N * A, P, 0, *outs)
         env.sync()
-        assert last_lean(_native.lib(), env._h) == (1 if enabled else 0)
+        assert last_lean(env) == (1 if enabled else 0)
         res.append(([o.to_host().tobytes() for o in outs], env.get_state().tobytes(), env.stats()))
         env.close()
     assert res[0] == res[1]

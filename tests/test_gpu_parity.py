@@ -6,23 +6,10 @@ import pytest
 
 from cooking_zoo_amd import soa
 from golden_io import GoldenSet, golden_sets
-from gpu_common import Handle, handle_for_set, oracle_for_set
+from gpu_common import Handle, handle_for_set, oracle_for_set, strip_golden
+from vec_common import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(rec):
-    r = rec.copy()
-    r[..., soa.W_STATUS] = 0
-    r[..., soa.W_LAYOUT] = 0
-    r[..., soa.W_EPISODE] = 0
-    r[..., soa.W_POOL] = 0
-    r[..., soa.RET_WORD0:soa.RET_WORD0 + 8] = 0        # running returns: device-side statistics only
-    return r
 
 
 @pytest.mark.parametrize("name", golden_sets())
@@ -34,7 +21,7 @@ def test_hip_replays_golden(name):
     obs0 = h.reset(np.arange(n), rids)
     st = h.get_state()
     for i, ep in enumerate(eps):
-        assert np.array_equal(strip(st[i]), strip(ep.states[0])), f"{name} ep{i}: reset state"
+        assert np.array_equal(strip_golden(st[i]), strip_golden(ep.states[0])), f"{name} ep{i}: reset state"
         assert np.array_equal(bits(obs0[i]), bits(ep.obs[0])), f"{name} ep{i}: reset obs"
     T = max(len(ep.actions) for ep in eps)
     A = eps[0].dims.A
@@ -49,7 +36,7 @@ def test_hip_replays_golden(name):
             if t >= len(ep.actions):
                 continue
             ctx = f"{name} ep{i} (seed {ep.seed}, {ep.policy}) step {t} actions {ep.actions[t].tolist()}"
-            if not np.array_equal(strip(st[i]), strip(ep.states[t + 1])):
+            if not np.array_equal(strip_golden(st[i]), strip_golden(ep.states[t + 1])):
                 pytest.fail(f"{ctx}: state differs\n-- hip\n{soa.describe_record(ep.dims, st[i])}\n-- reference\n"
                             f"{soa.describe_record(ep.dims, ep.states[t + 1])}\n-- before\n"
                             f"{soa.describe_record(ep.dims, ep.states[t])}")
@@ -111,7 +98,7 @@ def test_hip_replays_despawn_respawn_steps(name):
             if t >= len(ep.actions):
                 continue
             ctx = f"{name} ep{i} (seed {ep.seed}) step {t} actions {ep.actions[t].tolist()}"
-            if not np.array_equal(strip(st[i]), strip(ep.pre_states[t])):
+            if not np.array_equal(strip_golden(st[i]), strip_golden(ep.pre_states[t])):
                 pytest.fail(f"{ctx}: state differs\n-- device\n{soa.describe_record(ep.dims, st[i])}\n-- reference\n"
                             f"{soa.describe_record(ep.dims, ep.pre_states[t])}")
             assert np.array_equal(bits(obs[i]), bits(ep.pre_obs[t])), ctx

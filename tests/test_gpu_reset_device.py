@@ -13,48 +13,16 @@ import pytest
 from cooking_zoo_amd import _native, soa
 from fuzz_policy import BumperActions
 from oracle_binding import VecOracle
-from test_gpu_f32_obs import SENTINEL, GuardedRows, want32
+from vec_common import (ALL_FORMS, COOP, FORM_SUBSETS, INSTANCE_CASES, SENT8, SENT64, SENTINEL, TWO, Bufs, CallerStream, check_rows, env_of,
+                        instance, oracle_reset, strip, tables_of, want32)
 
 pytestmark = pytest.mark.gpu
 
-TWO = ["TomatoLettuceSalad", "CarrotBanana"]
-DENSE_RECIPES = ["TomatoSalad", "no_recipe", "TomatoLettuceSalad", "CarrotBanana"]
-SENT64 = 0x7FF8BEEF0BADF00D         # a quiet NaN no table entry equals
-SENT8 = 199                         # no entry of the quotient table in use and not the padding value: no code equals it
-COOP = dict(level="coop_test", meta="example", agents=2, recipes=TWO, scheme="scheme3", max_steps=12, num_layouts=3)
 SEED = 3                            # the mixed run's seed: `sensitive` holds for it on the oracle alone
 
 
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def tables_of(n, level, meta, agents, recipes, scheme, max_steps, num_layouts, **kw):
-    from cooking_zoo_amd.vec_env import BatchTables
-    return BatchTables(n, level, meta, agents, max_steps, recipes, action_scheme=scheme, num_layouts=num_layouts, **kw)
-
-
 def make(n, auto_reset=False, tables=None, **cfg):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    return CookingVecEnv(n, tables=tables or tables_of(n, **cfg), auto_reset=auto_reset)
-
-
-def oracle_reset(orc, e, layout_id=-1, groups=1, active=0):
-    """the first way: bump the episode word, draw (or take) the layout, czo_reset_env -> the fresh world's float64 rows"""
-    lib = orc.oracle.lib
-    lib.czo_next_layout_group.restype = C.c_uint32
-    rec = orc.records[e]
-    rec[soa.W_EPISODE] += 1
-    if layout_id < 0:
-        layout_id = lib.czo_next_layout_group(C.c_int64(orc.env_id_base + e), C.c_uint32(int(rec[soa.W_EPISODE])), C.c_uint32(int(rec[soa.W_POOL])),
-                                              C.c_uint32(orc.n_layouts), C.c_uint32(groups), C.c_uint32(active))
-    obs = np.empty((orc.dims.A, orc.dims.F))
-    err = lib.czo_reset_env(C.byref(orc.oracle.ctx), C.c_int64(e), C.c_uint32(int(layout_id)), rec.ctypes.data_as(C.c_void_p),
-                            obs.ctypes.data_as(C.c_void_p))
-    assert err == 0
-    return obs
+    return env_of(tables or tables_of(n, **cfg), auto_reset)
 
 
 def oracle_reset_pass(orc, auto, e):
@@ -126,51 +94,6 @@ def coop_script(kind):
     if kind == "explicit":
         return Script(t, 16, SEED, p_chosen=0.6, explicit=True)
     raise KeyError(kind)
-
-
-class Bufs:
-    """whole-batch device buffers of one handle: the step's and the three observation forms, each with its sentinel"""
-
-    def __init__(self, env):
-        n, A, F = env.num_envs, env.num_agents, env.F
-        self.env, self.shape = env, (n, A, F)
-        self.act, self.rew = env.alloc((n, A), np.int32), env.alloc((n, A), np.float64)
-        self.term, self.trunc = env.alloc((n, A), np.uint8), env.alloc((n, A), np.uint8)
-        self.obs, self.codes, self.rows32 = env.alloc((n, A, F), np.uint64), env.alloc((n, A, env.codes_pitch), np.uint8), GuardedRows(env)
-        self.mask, self.ids = env.alloc((n,), np.uint8), env.alloc((n,), np.int32)
-        self.fill()
-
-    def fill(self):
-        self.obs.from_host(np.full(self.shape, SENT64, dtype=np.uint64))
-        self.codes.from_host(np.full(self.codes.shape, SENT8, dtype=np.uint8))
-        self.rows32.fill()
-
-    def read(self):
-        return self.obs.to_host(), self.codes.to_host(), self.rows32.rows()
-
-
-ALL_FORMS = ("obs", "obs32", "codes")
-FORM_SUBSETS = [tuple(f for k, f in enumerate(ALL_FORMS) if m >> k & 1) for m in range(1, 8)]      # the seven non-empty ones
-
-
-def check_rows(ctx, env, before, got, rows, forms=ALL_FORMS):
-    """the three buffers after a reset call: a buffer the call named holds what it held before with rows e of the restarted envs
-    replaced by the oracle's reset observation, a buffer it did not name is untouched"""
-    F, table = env.F, env.obs_table()
-    obs, codes, r32 = (x.copy() for x in before)
-    for e, o in rows.items():
-        if "obs" in forms:
-            obs[e] = o.view(np.uint64)
-        if "obs32" in forms:
-            r32[e] = want32(o)
-    assert np.array_equal(got[0], obs), f"{ctx}: float64 rows"
-    assert np.array_equal(got[2], r32), f"{ctx}: float32 rows"
-    for e in range(codes.shape[0]):
-        if e in rows and "codes" in forms:
-            assert np.array_equal(table[got[1][e][:, :F]].view(np.uint64), rows[e].view(np.uint64)), f"{ctx}: codes of env {e}"
-            assert (got[1][e][:, F:] == 255).all(), f"{ctx}: padding of env {e}"
-        else:
-            assert np.array_equal(got[1][e], codes[e]), f"{ctx}: codes of env {e} were touched"
 
 
 def replay(env, script, forms=ALL_FORMS, prepare=None, calls=None):
@@ -375,22 +298,10 @@ def test_statistics_equal_host_resets_of_the_same_set():
 # 6: every instance and agent count
 # ---------------------------------------------------------------------------------------------------------------------------
 
-INSTANCE_CASES = [
-    ("crowded_6x5", "crowded_6x5", 4, ["TomatoSalad", "TomatoLettuceSalad", "no_recipe", "MashedCarrotBanana"], "scheme1", 0),
-    ("dense_8x8", "dense_8x8", 1, DENSE_RECIPES[:1], "scheme3", 0),
-    ("dense_8x8", "dense_8x8", 2, DENSE_RECIPES[:2], "scheme3", 0),
-    ("dense_8x8", "dense_8x8", 3, DENSE_RECIPES[:3], "scheme3", 0),
-    ("dense_8x8", "dense_8x8", 4, DENSE_RECIPES[:4], "scheme3", 0),
-    ("dense_16x16", "dense_16x16", 2, ["TomatoLettuceOnionSalad", "MashedCarrotBanana"], "scheme1", 1),
-    ("huge_20x20", "huge_20x20", 3, ["TomatoLettuceSalad", "MashedCarrotBanana", "TomatoSalad"], "scheme1", 2),
-]
-
-
 @pytest.mark.parametrize("level,meta,agents,recipes,scheme,inst", INSTANCE_CASES)
 def test_every_instance_and_agent_count(level, meta, agents, recipes, scheme, inst):
     """the mixed run, short, on every kernel instance and agent count; the calls name all three buffers, or - by the agent count - the
     float32 rows alone (the image is then built without the float64 encode) or the codes alone"""
-    from test_gpu_instance_edges import instance
     forms = {1: ("obs32",), 3: ("codes",)}.get(agents, ALL_FORMS) if level == "dense_8x8" else ALL_FORMS
     t = tables_of(9, level, meta, agents, recipes, scheme, 6, 3)
     s = Script(t, 12, 7, p_chosen=0.4)
@@ -450,8 +361,6 @@ def test_despawn_respawn_on():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_reset_device_inside_a_callers_capture():
-    from test_gpu_capture import Hip
-    hip = Hip()
     n, K, R = 256, 4, 50
     cfg = dict(COOP, num_layouts=8)
     t = tables_of(n, **cfg)
@@ -468,19 +377,13 @@ def test_reset_device_inside_a_callers_capture():
     for e, b in ((env, be), (ref, br)):
         e.reset(return_obs=False)
         e.observe_device(b.obs)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    loop(env, be, K)                                            # K x [policy, step, reset of the finished envs]: captured, not executed
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    cs = CallerStream(env)
+    with cs.capture():
+        loop(env, be, K)                                        # K x [policy, step, reset of the finished envs]: captured, not executed
     assert env._steps == 0 and env.captured_steps == K         # (and the resets are no steps)
     assert np.array_equal(env.get_state(), ref.get_state()), "capturing must not have stepped or reset anything"
-    for _ in range(R):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.replay(R)
+    cs.sync()
     loop(ref, br, K * R)
     ref.sync()
     assert ref._steps == K * R
@@ -491,9 +394,7 @@ def test_reset_device_inside_a_callers_capture():
     st = env.stats()
     assert st == ref.stats() and st["episodes"] >= n and st["env_steps"] == n * K * R      # no env-step went to a reset pass
     assert not (env.get_state()[:, soa.W_STATUS] & 1).any()
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()
 
 

@@ -1,36 +1,16 @@
 """GPU: batched stepping, on-device auto-reset, fused rollouts, statistics and sharding against the oracle,
 plus size-independent properties at BASELINE sizes."""
+import functools
+
 import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from vec_common import bits, make_env, oracle_for, strip
 
 pytestmark = pytest.mark.gpu
 
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def make(n, **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(level="coop_test", meta_file="example", num_agents=2, max_steps=30,
-                recipes=["TomatoLettuceSalad", "CarrotBanana"], action_scheme="scheme3", num_layouts=16, auto_reset=True)
-    args.update(kw)
-    lvl, meta = args.pop("level"), args.pop("meta_file")
-    A, ms, rec = args.pop("num_agents"), args.pop("max_steps"), args.pop("recipes")
-    return CookingVecEnv(n, lvl, meta, A, ms, rec, **args)
-
-
-def oracle_for(env, **kw):
-    from oracle_binding import VecOracle
-    return VecOracle.from_vec_env(env, **kw)
+make = functools.partial(make_env, num_layouts=16)          # coop_test, two agents, 30 steps; 16 layouts
 
 
 def stats_from_oracle_run(orc, T, seed):
@@ -78,7 +58,7 @@ def stats_from_oracle_run(orc, T, seed):
 ])
 def test_step_with_autoreset_matches_oracle(scheme, level, agents, recipes, meta):
     n, T = 96, 75
-    env = make(n, level=level, meta_file=meta, num_agents=agents, recipes=recipes, action_scheme=scheme, max_steps=30,
+    env = make(n, level=level, meta=meta, agents=agents, recipes=recipes, scheme=scheme, max_steps=30,
                num_layouts=12)
     orc = oracle_for(env)
     og, oo = env.reset(), orc.reset()
@@ -244,7 +224,7 @@ def test_long_fused_rollout_matches_oracle(scheme, agents, level, meta, recipes,
     """Long horizons at scale (millions of env-steps per case): final state, last observation and statistics of a
     fused device rollout against the oracle's rollout over the same counter-based action stream."""
     seed = 2024
-    env = make(n, level=level, meta_file=meta, num_agents=agents, recipes=recipes, action_scheme=scheme, max_steps=ms,
+    env = make(n, level=level, meta=meta, agents=agents, recipes=recipes, scheme=scheme, max_steps=ms,
                num_layouts=64)
     orc = oracle_for(env)
     env.reset(return_obs=False)
@@ -268,7 +248,7 @@ def test_fused_trajectory_with_many_descriptor_chunks():
     """F = 840 needs three descriptor chunks per encode: every step of a fused rollout must still be encoded from
     chunk 0 onwards (regression test: the chunk-0 descriptors are restored after each encode)."""
     n, T, seed, A = 48, 12, 5, 4
-    env = make(n, level="large_16x16", meta_file="large_16x16", num_agents=A, max_steps=9,
+    env = make(n, level="large_16x16", meta="large_16x16", agents=A, max_steps=9,
                recipes=["TomatoLettuceSalad", "CarrotBanana", "AppleWatermelon", "CucumberOnion"], num_layouts=6)
     orc = oracle_for(env)
     env.reset(return_obs=False)

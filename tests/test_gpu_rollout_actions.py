@@ -5,25 +5,9 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
+from vec_common import bits, make_env as make, strip
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
-
-
-def make(n, level, meta, agents, recipes, scheme, max_steps=30, **kw):
-    from cooking_zoo_amd.vec_env import CookingVecEnv
-    args = dict(action_scheme=scheme, num_layouts=8, auto_reset=True)
-    args.update(kw)
-    return CookingVecEnv(n, level, meta, agents, max_steps, recipes, **args)
 
 
 def run_and_compare(env, orc, acts, chunks=1, check_every=1):

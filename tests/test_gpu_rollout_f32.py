@@ -16,7 +16,6 @@ entry, and a copy of its meta file with "Agent": 4; everything else is the shipp
 
 Shapes: 35 envs (the last workgroup is partly empty at 8 and at 4 envs per workgroup), T = 5 with max_steps = 3, so that an episode
 end, the reset pass behind it and a move to another layout fall inside one launch - the descriptor re-fetch of the kernel."""
-import ctypes as C
 import json
 import os
 
@@ -25,9 +24,9 @@ import pytest
 
 from cooking_zoo_amd import _native, soa
 from oracle_binding import VecOracle
-from test_gpu_f32_edges import CROWDED4, HUGE3, MIN_INEXACT, Sensitivity
-from test_gpu_f32_obs import SENTINEL, want32
-from test_gpu_instance_edges import TWO, _diag, instance, make, strip
+from host_common import register_fixture_recipes
+from vec_common import (CROWDED4, HUGE3, MIN_INEXACT, SENTINEL, TWO, CallerStream, Sensitivity, instance, last_mode, make_env as make, strip,
+                        want32)
 
 pytestmark = pytest.mark.gpu
 
@@ -43,10 +42,6 @@ MOVABLE = {
     "huge_20x20": ("huge_20x20", 2, {("Cutboard", 0): ([3, 7, 11], [4]), ("Blender", 0): ([0], [8, 12])},
                    {"MAX_COUNT": 1, "X_POSITION": list(range(2, 18)), "Y_POSITION": [6, 7, 11, 12]}),
 }
-
-
-def last_mode(env):
-    return _diag(env, "cz_diag_last_step_mode")
 
 
 @pytest.fixture(scope="module")
@@ -394,7 +389,6 @@ def test_null_outputs(skip):
 @pytest.mark.parametrize("max_dyn,inst,agents,scheme", [(None, 0, 4, "scheme3"), (65, 1, 3, "scheme1"), (129, 2, 4, "scheme1")])
 def test_wide_books_and_spawning(max_dyn, inst, agents, scheme):
     from cooking_zoo_amd.cooking_book import recipe_drawer as rd
-    from test_custom_recipes import register_fixture_recipes
     assert not rd.RECIPE_STORE
     register_fixture_recipes()
     try:
@@ -460,8 +454,6 @@ def test_refusals_step_nothing():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_both_launches_captured_into_a_callers_graph():
-    from test_gpu_capture import Hip
-    hip = Hip()
     env, ref = crowded(), crowded()
     orc = VecOracle.from_vec_env(env)
     start(env, orc)
@@ -473,18 +465,13 @@ def test_both_launches_captured_into_a_callers_graph():
     for x in (ta, tb):
         x.fill()
     tb.act.from_host(acts)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    env.rollout_f32(T, seed, 0, ta.buf["rows"], ta.buf["rew"], ta.buf["term"], ta.buf["trunc"])
-    env.rollout_actions_f32(tb.act, T, tb.buf["rows"], tb.buf["rew"], tb.buf["term"], tb.buf["trunc"])
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    cs = CallerStream(env)
+    with cs.capture():
+        env.rollout_f32(T, seed, 0, ta.buf["rows"], ta.buf["rew"], ta.buf["term"], ta.buf["trunc"])
+        env.rollout_actions_f32(tb.act, T, tb.buf["rows"], tb.buf["rew"], tb.buf["term"], tb.buf["trunc"])
     assert (env.get_state()[:, soa.W_T] == 0).all(), "capturing must not have stepped anything"
-    hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.replay()
+    cs.sync()
     eager_a, eager_b = ra.rollout(ref, seed, 0), rb.rollout_actions(ref, acts)
     got_a, got_b = ta.get(), tb.get()
     check("captured cz_rollout_f32", got_a, wants_a)
@@ -493,10 +480,7 @@ def test_both_launches_captured_into_a_callers_graph():
         for x, y in zip(got, eager):
             assert np.array_equal(x, y), "the replayed launch differs from the eager one"
     assert np.array_equal(env.get_state(), ref.get_state()) and env.stats() == ref.stats()
-    hip.lib.hipGraphExecDestroy(gexec)
-    hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close()
     ref.close()
 

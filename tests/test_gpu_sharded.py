@@ -8,18 +8,9 @@ import pytest
 from cooking_zoo_amd import soa
 from cooking_zoo_amd.sharded import ShardedVecEnv
 from cooking_zoo_amd.vec_env import CookingVecEnv
+from vec_common import bits
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
 
 
 def same_stats(a, b):

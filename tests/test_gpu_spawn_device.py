@@ -10,14 +10,12 @@ import pytest
 
 from cooking_zoo_amd import soa
 from cooking_zoo_amd.spawn import SpawnBook, grace_bits, status_bits
+from host_common import scalar_rule
+from vec_common import bits, strip
 
 pytestmark = pytest.mark.gpu
 KW = dict(action_scheme="scheme3", num_layouts=6, auto_reset=True, agent_despawn_rate=0.15, agent_respawn_rate=0.25, grace_period=2, spawn_seed=5)
 RECIPES = ["TomatoSalad", "TomatoLettuceSalad", "no_recipe", "MashedCarrotBanana"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
 
 
 def make(n, base=0, max_steps=40, **kw):
@@ -62,7 +60,6 @@ class Model:
         return obs, rew, term, trunc
 
     def _scalar_after_step(self, stepped):
-        from test_spawn_book import scalar_rule
         book, recs, dims = self.book, self.orc.records, self.env.dims
         book._key = (recs[:, soa.W_EPISODE].astype(np.uint64) << np.uint64(32)) | recs[:, soa.W_T].astype(np.uint64)
         moved = []
@@ -79,12 +76,6 @@ class Model:
                     moved.append(int(e))
             book.active[e], book.changed[e], book.grace[e] = st["active"], st["changed"], st["grace"]
         return sorted(set(moved))
-
-
-def strip(recs):
-    r = recs.copy()
-    r[:, soa.RET_WORD0:soa.RET_WORD0 + 8] = 0
-    return r
 
 
 def test_host_array_step_and_device_step_match_the_model():

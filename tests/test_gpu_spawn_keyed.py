@@ -13,15 +13,13 @@ import pytest
 from cooking_zoo_amd import soa
 from golden_io import GoldenSet, layout_from_episode, spawn_keyed_sets
 from gpu_common import Handle, _ptr
+from vec_common import bits
 
 pytestmark = pytest.mark.gpu
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def strip(rec):
+def strip_keyed(rec):
+    """a golden record against the device's: the status word stays (it holds the spawn bookkeeping), the episode word too"""
     r = rec.copy()
     r[..., soa.W_LAYOUT] = 0
     r[..., soa.W_POOL] = 0
@@ -74,7 +72,7 @@ def test_hip_replays_keyed_despawn_respawn(name):
             obs, rew, term, trunc = h.step(ep.actions[t][None])
             st = h.get_state()
             ctx = f"{ctx0} step {t} actions {ep.actions[t].tolist()}"
-            if not np.array_equal(strip(st[0]), strip(ep.states[t + 1])):
+            if not np.array_equal(strip_keyed(st[0]), strip_keyed(ep.states[t + 1])):
                 pytest.fail(f"{ctx}: state differs (status {st[0][soa.W_STATUS]:#x} vs {ep.states[t + 1][soa.W_STATUS]:#x})\n-- device\n"
                             f"{soa.describe_record(ep.dims, st[0])}\n-- reference\n{soa.describe_record(ep.dims, ep.states[t + 1])}")
             assert np.array_equal(bits(obs[0]), bits(ep.obs[t + 1])), f"{ctx}: observation"
@@ -98,7 +96,7 @@ def test_hip_replays_keyed_despawn_respawn(name):
             assert np.array_equal(bits(obs), bits(ep.obs[1:])), f"{ctx0}: {what} observations"
             assert np.array_equal(bits(rew), bits(ep.rewards)), f"{ctx0}: {what} rewards"
             assert np.array_equal(term, ep.terms) and np.array_equal(trunc, ep.truncs), f"{ctx0}: {what} flags"
-            assert np.array_equal(strip(h.get_state()[0]), strip(ep.states[-1])), f"{ctx0}: {what} final record"
+            assert np.array_equal(strip_keyed(h.get_state()[0]), strip_keyed(ep.states[-1])), f"{ctx0}: {what} final record"
         assert h.L.cz_spawn_exhausted(h.h) == 0
         h.close()
     assert n_gone >= 4

@@ -3,7 +3,7 @@ restore_device, fork_device).  Everything is compared exactly: records as bytes 
 those against a numpy sum of the oracle's rewards in step order), float64 rows as uint64, float32 rows as uint32 against np.float32
 of the oracle's rows, codes decoded through obs_table().  Every output buffer is pre-filled with a sentinel and the float32 buffer is
 guarded.  What a restored env must be comes from the oracle alone: its record e set to the saved row, its rows the oracle's observe
-of that record (`Twin.restore`); the statistics follow the numpy model of tests/test_state_device_host.py."""
+of that record (`Twin.restore`); the statistics follow the numpy model of tests/host_common.py."""
 import ctypes as C
 
 import numpy as np
@@ -12,15 +12,19 @@ import pytest
 from cooking_zoo_amd import _native, soa
 from fuzz_policy import BumperActions
 from oracle_binding import VecOracle
-from test_gpu_f32_obs import SENTINEL
-from test_gpu_reset_device import ALL_FORMS, COOP, FORM_SUBSETS, INSTANCE_CASES, SENT8, SENT64, TWO, Bufs, check_rows, make, strip, tables_of
-from test_state_device_host import env_steps, row_ok, steps_correction
+from host_common import env_steps, row_ok, steps_correction
+from vec_common import (ALL_FORMS, COOP, FORM_SUBSETS, INSTANCE_CASES, SENT8, SENT64, SENTINEL, TWO, Bufs, CallerStream, check_rows, env_of,
+                        instance, strip, tables_of)
 
 pytestmark = pytest.mark.gpu
 
 RET = slice(soa.RET_WORD0, soa.RET_WORD0 + 8)
 ARCH_SENT = 0xA5C3F00D              # an archive word nobody wrote (as a layout id, a recipe id or a pool word it would be refused)
 DONE = soa.STATUS_DONE
+
+
+def make(n, auto_reset, tables):
+    return env_of(tables, auto_reset)
 
 
 class Twin:
@@ -343,7 +347,6 @@ def test_refused_slots_and_rows():
 def test_every_instance_and_agent_count(level, meta, agents, recipes, scheme, inst):
     """save / step / fork / step, short, on every kernel instance and agent count; the calls name all three buffers, or - by the
     agent count - the float32 rows alone (the image is then built without the float64 encode) or the codes alone"""
-    from test_gpu_instance_edges import instance
     forms = {1: ("obs32",), 3: ("codes",)}.get(agents, ALL_FORMS) if level == "dense_8x8" else ALL_FORMS
     t, env, tw, b = start(9, False, 7, tables=tables_of(9, level, meta, agents, recipes, scheme, 6, 3))
     assert instance(env) == inst
@@ -451,8 +454,6 @@ def test_statistics_and_episode_records():
 # ---------------------------------------------------------------------------------------------------------------------------
 
 def test_save_and_restore_inside_a_callers_capture():
-    from test_gpu_capture import Hip
-    hip = Hip()
     n, K = 64, 3
     t = tables_of(n, **dict(COOP, num_layouts=8))
     env, ref = make(n, auto_reset=True, tables=t), make(n, auto_reset=True, tables=t)
@@ -472,20 +473,14 @@ def test_save_and_restore_inside_a_callers_capture():
     for e, b in ((env, be), (ref, br)):
         e.reset(return_obs=False)
         e.observe_device(b.obs)
-    stream = C.c_void_p()
-    hip.ck(hip.lib.hipStreamCreateWithFlags(C.byref(stream), 1), "hipStreamCreateWithFlags")
-    env.set_stream(stream)
-    graph, gexec = C.c_void_p(), C.c_void_p()
-    hip.ck(hip.lib.hipStreamBeginCapture(stream, 0), "hipStreamBeginCapture")
-    loop(env, be, ae)                                           # [save, K x (policy, step), restore, policy, step]: captured, not executed
-    hip.ck(hip.lib.hipStreamEndCapture(stream, C.byref(graph)), "hipStreamEndCapture (a call inside the capture invalidated it)")
-    hip.ck(hip.lib.hipGraphInstantiate(C.byref(gexec), graph, None, None, C.c_size_t(0)), "hipGraphInstantiate")
+    cs = CallerStream(env)
+    with cs.capture():
+        loop(env, be, ae)                                       # [save, K x (policy, step), restore, policy, step]: captured, not executed
     assert env._steps == 0 and env.captured_steps == K + 1     # (save and restore are no steps)
     assert np.array_equal(env.get_state(), ref.get_state()), "capturing must not have run anything"
     assert (ae.to_host() == ARCH_SENT).all()
-    for _ in range(2):
-        hip.ck(hip.lib.hipGraphLaunch(gexec, stream), "hipGraphLaunch")
-    hip.ck(hip.lib.hipStreamSynchronize(stream), "hipStreamSynchronize")
+    cs.replay(2)
+    cs.sync()
     for _ in range(2):
         loop(ref, br, ar)
     ref.sync()
@@ -499,9 +494,7 @@ def test_save_and_restore_inside_a_callers_capture():
     st = env.stats()
     assert st == ref.stats() and st["env_steps"] == n * 2 * (K + 1)
     assert env.restore_device_refused() == 0
-    hip.lib.hipGraphExecDestroy(gexec); hip.lib.hipGraphDestroy(graph)
-    env.set_stream(None)
-    hip.lib.hipStreamDestroy(stream)
+    cs.close()
     env.close(); ref.close()
 
 

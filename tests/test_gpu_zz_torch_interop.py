@@ -13,13 +13,11 @@ import sys
 import numpy as np
 import pytest
 
+from vec_common import bits
+
 CHILD_FLAG = "CZ_TORCH_INTEROP_CHILD"
 
 pytestmark = pytest.mark.gpu
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_torch_tensors_on_the_callers_stream():

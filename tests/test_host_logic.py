@@ -12,10 +12,7 @@ from cooking_zoo_amd.cooking_world.layout import feature_length
 from cooking_zoo_amd.cooking_world.engine.load_level import load_meta_file
 from golden_io import GoldenSet, golden_sets, layout_from_episode, recipe_table, RECIPE_NAMES
 from oracle_binding import Oracle
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+from vec_common import bits
 
 
 def test_feature_length_example_meta():

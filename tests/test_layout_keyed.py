@@ -10,7 +10,7 @@ import pytest
 from cooking_zoo_amd import soa, spawn
 from cooking_zoo_amd.cooking_world.engine import level_program as lp
 from cooking_zoo_amd.cooking_world.engine import load_level as ll
-from layout_keyed_common import (CASES, CASE_IDS, KINDS, STRESS_CASES, STRESS_IDS, assert_matches_reference, case_tables,
+from layout_keyed_common import (CASES, CASE_IDS, KINDS, SHIPPED, STRESS, STRESS_CASES, STRESS_IDS, assert_matches_reference, case_tables,
                                  failure_kind, reference_misfit)
 
 
@@ -133,13 +133,6 @@ def test_more_slots_than_the_batch_has_is_a_failed_draw():
 
 
 # ------------------------------------------------------------------------------------------------ every level, every failure branch
-# tests/golden/layouts_keyed_stress_ref.json.gz: the 15 shipped levels at every agent count their meta files allow, and the stress
-# levels of tests/levels/ - one per way a draw can fail - under keys the device test redraws (test_gpu_layout_generate_matrix.py)
-SHIPPED = {"coop_test": 2, "coexistence_test": 2, "switch_test": 2, "crowded_6x5": 4, "dense_8x8": 4, "edge_8x8": 3, "edge_9x8": 3,
-           "edge_empty": 3, "limit_32x8": 3, "limit_8x31": 3, "large_16x16": 4, "dense_16x16": 4, "huge_objs_16x16": 3,
-           "huge_20x20": 3, "huge_32x32": 4}                               # level -> the Agent count of its meta file
-STRESS = ["stress_object_timeout", "stress_agent_timeout", "stress_second_switch", "stress_counter_overflow", "stress_slots",
-          "stress_meta_cap"]
 
 
 @pytest.mark.parametrize("case", STRESS_CASES, ids=STRESS_IDS)

@@ -6,10 +6,7 @@ import pytest
 from cooking_zoo_amd import soa
 from golden_io import GoldenSet, golden_sets, recipe_table
 from oracle_binding import Oracle
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+from vec_common import bits
 
 
 def make_oracle(gs, ep, **kw):

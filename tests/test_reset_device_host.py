@@ -10,7 +10,7 @@ import re
 
 import pytest
 
-from test_f32_host import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
+from host_common import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
 
 NEW_SYMBOLS = ["cz_reset_device", "cz_reset_device_refused"]
 

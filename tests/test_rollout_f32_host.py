@@ -9,7 +9,7 @@ import re
 
 import pytest
 
-from test_f32_host import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
+from host_common import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
 
 NEW_SYMBOLS = ["cz_rollout_f32", "cz_rollout_actions_f32"]
 ROLLOUT_F32, ROLLOUT_ACTIONS_F32 = 7, 8                           # cz::StepMode in cz_kernels.h

@@ -5,31 +5,7 @@ import pytest
 
 from cooking_zoo_amd import soa
 from cooking_zoo_amd.spawn import SpawnBook, uniform
-
-
-def scalar_rule(book_like, rec, dims, e, step):
-    """handle_agent_spawn for ONE world, written the way the reference writes it (draw only when the `and` chain gets
-    there); state = (active[A], changed[A], grace[A]) lists; returns whether somebody was moved"""
-    active, grace, changed = book_like["active"], book_like["grace"], book_like["changed"]
-    A = len(active)
-    moved = False
-    for i in range(A):
-        changed[i] = False
-    for i in range(A):
-        if grace[i] > 0:
-            grace[i] -= 1
-            continue
-        if active.count(True) > 1 and active[i] and uniform(book_like["seed"], e, step, i, 0) < book_like["despawn"]:
-            if soa.unpack_agent(rec[soa.AGENT_WORD0 + i])[3] >= 0:
-                continue
-            active[i] = False
-            changed[i] = True
-        elif not active[i] and uniform(book_like["seed"], e, step, i, 1) < book_like["respawn"]:
-            active[i] = True
-            changed[i] = True
-            grace[i] = book_like["grace_period"]
-            moved = True
-    return moved
+from host_common import scalar_rule
 
 
 def test_vectorised_bookkeeping_equals_the_scalar_rule():

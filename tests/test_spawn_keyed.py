@@ -11,10 +11,7 @@ import pytest
 from cooking_zoo_amd import soa, spawn
 from golden_io import GoldenSet, spawn_keyed_sets
 from oracle_binding import Oracle, load_lib
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+from vec_common import bits
 
 
 def keyed_oracle(gs, ep):

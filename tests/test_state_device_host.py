@@ -4,8 +4,8 @@ ABI number stayed 10, a library built before them fails at the first call and na
 methods, k_restore_where exists for all three instance sizes and every agent count behind the unchanged Params (no vector register
 spilled, no scratch memory) and k_save_where exists once.
 
-Also here, for the GPU tests to import: the numpy models of what the device does to a restored env's statistics (`steps_correction`,
-`env_steps`: the SU_STEPS rule) and of the checks a row must pass (`row_ok`: cz_set_state's host loop).  (cz_save_device's and
+Also here: the numpy models of what the device does to a restored env's statistics (`steps_correction`, `env_steps` of
+tests/host_common.py: the SU_STEPS rule), checked against a random life of 64 envs.  (cz_save_device's and
 cz_restore_device's refusal of capacity < num_envs without slots is a host check, but a handle does not exist without a device: that
 case is in tests/test_gpu_state_device.py.)"""
 import ctypes as C
@@ -16,44 +16,9 @@ import numpy as np
 import pytest
 
 from cooking_zoo_amd import soa
-from test_f32_host import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
+from host_common import HEADER, INSTANCES, LIB, device_code, env_steps, steps_correction  # noqa: F401  (device_code: the fixture)
 
 NEW_SYMBOLS = ["cz_save_device", "cz_restore_device", "cz_restore_device_refused"]
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# the models
-# ---------------------------------------------------------------------------------------------------------------------------
-
-def steps_correction(old_status, old_t, new_status, new_t):
-    """what a restore adds to an env's signed correction word SU_STEPS: the old record's t if that episode was still running (its
-    steps stay counted: k_count_aborted's rule), minus the new record's t if this one is (steps that arrive already taken are not
-    this handle's: k_stats_clear's rule).  uint32 arithmetic, read back as int32, like the device's word."""
-    old_status, old_t, new_status, new_t = (np.asarray(x, dtype=np.uint32) for x in (old_status, old_t, new_status, new_t))
-    plus = np.where(old_status & soa.STATUS_DONE, np.uint32(0), old_t)
-    minus = np.where(new_status & soa.STATUS_DONE, np.uint32(0), new_t)
-    return (plus - minus).astype(np.uint32).view(np.int32)
-
-
-def env_steps(su_steps, length_sum, status, t):
-    """cz_get_stats' env_steps from the per-env words (k_stats_chains): the signed correction word, the lengths of the finished
-    episodes, and the steps of the episode in flight"""
-    live = (np.asarray(status) & soa.STATUS_DONE) == 0
-    return int(np.asarray(su_steps, dtype=np.int64).sum() + np.asarray(length_sum, dtype=np.int64).sum()
-               + np.asarray(t, dtype=np.int64)[live].sum())
-
-
-def row_ok(row, dims, n_layouts, n_recipes, recipes_per_env):
-    """cz_set_state's checks of one record: layout id, recipe ids, pool slice, no dead slot with a container tag"""
-    if int(row[soa.W_LAYOUT]) >= n_layouts:
-        return False
-    if any(((int(row[soa.W_RECIPES]) >> (8 * k)) & 0xFF) >= n_recipes for k in range(recipes_per_env)):
-        return False
-    base, count = int(row[soa.W_POOL]) & 0xFFFF, int(row[soa.W_POOL]) >> 16
-    if count and base + count > n_layouts:
-        return False
-    d0, d1 = row[dims.dyn0_word0:dims.dyn0_word0 + dims.D], row[dims.dyn1_word0:dims.dyn1_word0 + dims.D]
-    return not ((((d0 >> 24) & soa.DYN_ALIVE) == 0) & ((d1 & 0xFF) != 0)).any()
 
 
 def test_steps_correction_keeps_env_steps_the_steps_taken():
