@@ -1506,6 +1506,22 @@ extern "C" int cz_observe_device_f32(cz_handle h, int64_t b, int64_t c, float *d
     HIPCHK(h, h->kl.observe_f32(P, h->stream, b, (int)c, d_obs32));
     return 0;
 }
+// The grid observation of the current state into DEVICE buffers (k_observe_grid, cz_kernels.h; definition: cooking_zoo_amd/grid.py): any
+// of the three forms of the (W, H, C) tensor and the agents' locations, laid out for env_count envs.  Stream-ordered, nothing is copied,
+// waited for or queried (legal inside a stream capture of the caller).
+extern "C" int32_t cz_grid_channels(int32_t extended) { return extended == 0 ? 32 : extended == 1 ? 48 : -1; }
+extern "C" int cz_observe_grid_device(cz_handle h, int64_t b, int64_t c, int32_t extended, uint32_t *d_bits, uint8_t *d_grid8, float *d_grid32,
+                                      int32_t *d_agent_xy) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (cz_grid_channels(extended) < 0) return fail(h, "cz_observe_grid_device: extended is %d, not 0 or 1", extended);
+    if (c == 0) return 0;
+    if (!d_bits && !d_grid8 && !d_grid32 && !d_agent_xy) return fail(h, "cz_observe_grid_device: all four output pointers are null");
+    if (((uintptr_t)d_grid8 | (uintptr_t)d_grid32) & 15u || (uintptr_t)d_bits & 7u || (uintptr_t)d_agent_xy & 3u)
+        return fail(h, "cz_observe_grid_device: d_grid8 and d_grid32 must be 16-byte aligned, d_bits 8-byte, d_agent_xy 4-byte");
+    if (set_device(h)) return 1;
+    HIPCHK(h, h->kl.observe_grid(h->P, h->stream, b, (int)c, extended, d_bits, d_grid8, d_grid32, d_agent_xy));
+    return 0;
+}
 // host mirror of the table the float32 rows are gathered from: what the kernels make of the float64 table while they stage it
 // (v_cvt_f32_f64, round to nearest even) is what this conversion makes of the host copy
 extern "C" int cz_obs_table_f32(cz_handle h, float *table) {

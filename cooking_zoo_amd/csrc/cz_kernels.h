@@ -1154,6 +1154,140 @@ __global__ __launch_bounds__(64) void k_observe_f32(const Params P, int64_t env_
     write_forms(P, e, cx, lds, nullptr, lutf, nullptr, obs_out, nullptr, (size_t)i);
 }
 
+// The grid observation (cz_observe_grid_device): the (W, H, 32) state tensor the reference declares for obs_spaces=["full"]
+// (cooking_env.py:118-123, 149-150, 274-278) and never fills, from the per-object vectors of world_objects.py
+// (numeric_state_representation); cooking_zoo_amd/grid.py is the definition and the host model.  All channels are 0 / 1: one cell is
+// one word of reference channels plus, `extended`, one word of which 16 bits are used.  A pure function of the record, in the shape
+// of k_observe_f32: one wavefront per env and workgroup.
+//   1. every lane ORs its alive slots' bits into the words of the slot's cell (LDS atomics, `acc`, record order c = y * W + x),
+//      lanes a < NA the agents' bits; a slot or agent outside the grid (no valid record has one) is not drawn;
+//   2. every lane takes its own cells, adds the static bit of the cell type and the mutable cell bits and puts the words at the
+//      cell's place in the output order (`fin`, o = x * H + y; x and y from the constant block's coordinate table: no division);
+//   3. the forms that were asked for (a uniform test each) go out in output order: `bits` one word or pair per lane, `grid8` two or
+//      three 16-byte stores per lane, `grid32` with four lanes per cell - neighbouring lanes write neighbouring 16 bytes, 64 bytes per
+//      cell and store.  Every channel of every cell is written, nothing behind the last cell; plain stores.
+// Channels of a dynamic class / a cell type: 5 bits each, by class id (cooking_zoo_amd/grid.py DYN_CHANNEL, STATIC_CHANNEL)
+constexpr uint64_t GRID_DYN_CHANNEL = 26ull | 24ull << 5 | 28ull << 10 | 22ull << 15 | 14ull << 20 | 17ull << 25 | 7ull << 30 | 5ull << 35 | 30ull << 40 | 11ull << 45;
+constexpr uint64_t GRID_STATIC_CHANNEL = 21ull | 16ull << 5 | 20ull << 10 | 27ull << 15 | 10ull << 20 | 19ull << 25 | 9ull << 30;
+constexpr uint32_t GRID_N_DYN = 10u, GRID_N_STATIC = 7u, GRID_CHOPPED_CLASSES = 0x1FEu;   // Onion .. Watermelon: a `chopped` channel behind the class's
+enum : uint32_t { GX_CARROT_MASHED = 0, GX_BANANA_MASHED, GX_FRESH, GX_FREE, GX_HELD, GX_IN_PLATE, GX_CUT_READY, GX_BL_READY, GX_BL_TOGGLE,
+                  GX_SW_ACTIVE, GX_BLOCK_WALK, GX_DESPAWNED, GX_AGENT0 };                  // bits of the second word (channel 32 + bit)
+// four channel bits -> four bytes 0 / 1 (bit i of the nibble lands at bit 8 i: i + 7 i)
+__device__ __forceinline__ uint32_t grid_bytes(uint32_t nibble) { return (nibble * 0x00204081u) & 0x01010101u; }
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_observe_grid(const Params P, int64_t env_begin, int32_t extended, uint32_t *bits_out, uint8_t *grid8_out,
+                                                     float *grid32_out, int32_t *agent_xy_out) {
+    constexpr int CELLS = 64 * CPL;
+    __shared__ uint32_t acc[2][CELLS], fin[2][CELLS];
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    const uint32_t W = (uint32_t)P.W, H = (uint32_t)P.H, C = W * H;
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)lane};
+    const CoordWords<CPL> cw = load_coord_words<CPL>(P, (int)lane);
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, P.state + (size_t)(env_begin + i) * P.RW);
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) acc[0][lane + 64u * k] = acc[1][lane + 64u * k] = 0u;
+    __syncthreads();                                                  // (one wave: the LDS fence)
+    uint32_t held[NA];                                                // slot + 1 in every agent's hands, 0: empty
+#pragma unroll
+    for (int a = 0; a < NA; ++a) held[a] = rdl(e.agw, a) >> 24;
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) {
+        const uint32_t d0 = e.d0[k], d1 = e.d1[k], s1 = lane + 64u * k + 1u;
+        const uint32_t x = d0 & 0xFFu, y = (d0 >> 8) & 0xFFu, cls = (d0 >> 16) & 0xFFu;
+        if ((d0 & D_ALIVE) && cls < GRID_N_DYN && x < W && y < H) {   // (lanes past D hold zeros)
+            const uint32_t ch = (uint32_t)(GRID_DYN_CHANNEL >> (5u * cls)) & 31u;
+            const bool chopped = (d0 & D_CHOPPED) && ((GRID_CHOPPED_CLASSES >> cls) & 1u), mashed = (d0 & D_MASHED) != 0u;
+            bool in_hand = false;
+#pragma unroll
+            for (int a = 0; a < NA; ++a) in_hand = in_hand || held[a] == s1;
+            const uint32_t w0 = (1u << ch) | (chopped ? 2u << ch : 0u);
+            const uint32_t w1 = (uint32_t)(mashed && cls == CARROT) << GX_CARROT_MASHED | (uint32_t)(mashed && cls == BANANA) << GX_BANANA_MASHED |
+                                (uint32_t)(cls != PLATE && !(d0 & D_DONE)) << GX_FRESH | (uint32_t)((d0 & D_FREE) != 0u) << GX_FREE |
+                                (uint32_t)in_hand << GX_HELD | (uint32_t)((d1 & 0xFFu) != 0u) << GX_IN_PLATE;
+            const uint32_t c = y * W + x;
+            atomicOr(&acc[0][c], w0);
+            atomicOr(&acc[1][c], w1);
+        }
+    }
+    if (lane < (uint32_t)NA) {
+        const uint32_t x = e.agw & 0xFFu, y = (e.agw >> 8) & 0xFFu, orient = (e.agw >> 16) & 0xFFu;
+        if (x < W && y < H) {
+            const uint32_t c = y * W + x;
+            atomicOr(&acc[0][c], 1u | (orient - 1u < 4u ? 1u << orient : 0u));           // Agent: channels 0..4
+            atomicOr(&acc[1][c], (1u << (GX_AGENT0 + lane)) | (((e.status >> (SPAWN_GONE0 + lane)) & 1u) << GX_DESPAWNED));
+        }
+        if (agent_xy_out) {
+            int32_t *xy = agent_xy_out + ((size_t)i * NA + lane) * 2;
+            xy[0] = (int32_t)x;
+            xy[1] = (int32_t)y;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const uint32_t c = lane + 64u * k;
+        if (c < C) {
+            const uint32_t x = ((cw.w[k] & 0xFFFFu) >> 3) - (W - 1u), y = (cw.w[k] >> 19) - ((uint32_t)LUT_Y0 + H - 1u);
+            const uint32_t cv = e.cell[k], ty = cv & CELL_TYPE;
+            const uint32_t st = ty < GRID_N_STATIC ? 1u << ((uint32_t)(GRID_STATIC_CHANNEL >> (5u * ty)) & 31u) : 0u;
+            const bool ready = (cv & CELL_READY) != 0u;
+            const uint32_t w1 = (uint32_t)(ty == CUTBOARD && ready) << GX_CUT_READY | (uint32_t)(ty == BLENDER && ready) << GX_BL_READY |
+                                (uint32_t)(ty == BLENDER && (cv & CELL_TOGGLE)) << GX_BL_TOGGLE | (uint32_t)(ty == SWITCH && (cv & CELL_ACTIVE)) << GX_SW_ACTIVE |
+                                (uint32_t)(ty == BLOCK && (cv & CELL_WALK)) << GX_BLOCK_WALK;
+            const uint32_t o = x * H + y;                             // (x < W, y < H: o < C)
+            fin[0][o] = acc[0][c] | st;
+            fin[1][o] = acc[1][c] | w1;
+        }
+    }
+    __syncthreads();
+    const uint32_t CH = extended ? 48u : 32u;
+    if (bits_out) {
+        uint32_t *out = bits_out + (size_t)i * C * (extended ? 2u : 1u);
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const uint32_t o = lane + 64u * k;
+            if (o < C) {
+                if (extended) stg<uint2_t>(out, o * 8u, uint2_t{fin[0][o], fin[1][o]});
+                else stg<uint32_t>(out, o * 4u, fin[0][o]);
+            }
+        }
+    }
+    if (grid8_out) {
+        uint8_t *out = grid8_out + (size_t)i * C * CH;
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const uint32_t o = lane + 64u * k;
+            if (o < C) {
+                const uint32_t w0 = fin[0][o], w1 = fin[1][o];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    if (q == 2 && !extended) break;
+                    const uint32_t h = q == 0 ? w0 : q == 1 ? w0 >> 16 : w1;
+                    stg<uint4_t>(out, o * CH + 16u * q, uint4_t{grid_bytes(h & 0xFu), grid_bytes((h >> 4) & 0xFu), grid_bytes((h >> 8) & 0xFu),
+                                                                 grid_bytes((h >> 12) & 0xFu)});
+                }
+            }
+        }
+    }
+    if (grid32_out) {
+        float *out = grid32_out + (size_t)i * C * CH;
+        const uint32_t sub = lane & 3u;
+#pragma nounroll
+        for (uint32_t o = lane >> 2; o < C; o += 16u) {
+            const uint32_t w0 = fin[0][o], w1 = fin[1][o];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                if (q == 2 && !extended) break;
+                const uint32_t chunk = 4u * q + sub;                  // 16 bytes = four channels from 4 * chunk
+                const uint32_t n = ((q < 2 ? w0 : w1) >> ((4u * chunk) & 31u)) & 0xFu;
+                const uint32_t one = 0x3F800000u;
+                stg<uint4_t>(out, (o * CH + 4u * chunk) * 4u, uint4_t{(n & 1u) ? one : 0u, (n & 2u) ? one : 0u, (n & 4u) ? one : 0u, (n & 8u) ? one : 0u});
+            }
+        }
+    }
+}
+
 // reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
 // when mask[e] != 0 or, without a mask, when its status word has the done bit - what the auto-reset pass of step_env does to such an
 // env, without spending a step.  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load,
@@ -1317,6 +1451,8 @@ struct Launchers {
     // k_restore_where over all P.N envs: slots, archive, its rows, recipes in the table, float64 rows, float32 rows, codes, refused counter
     hipError_t (*restore_where)(const Params &, hipStream_t, const int32_t *, const uint32_t *, int64_t, uint32_t, double *, float *, uint8_t *,
                                 unsigned long long *);
+    // k_observe_grid: first env, count, extended, then bits, grid8, grid32, agent_xy (any may be null)
+    hipError_t (*observe_grid)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t *, uint8_t *, float *, int32_t *);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1406,8 +1542,12 @@ struct Inst {
                                     uint32_t n_recipes, double *obs, float *obs32, uint8_t *codes, unsigned long long *refused) {
         return CZ_LAUNCH_PER_ENV(k_restore_where, P.N, slot, records, capacity, n_recipes, obs, obs32, codes, refused);
     }
+    static hipError_t observe_grid(const Params &P, hipStream_t st, int64_t b, int n, int32_t extended, uint32_t *bits, uint8_t *grid8,
+                                   float *grid32, int32_t *agent_xy) {
+        return CZ_LAUNCH_PER_ENV(k_observe_grid, n, b, extended, bits, grid8, grid32, agent_xy);
+    }
 #undef CZ_LAUNCH_PER_ENV
-    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where}; }
+    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid}; }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

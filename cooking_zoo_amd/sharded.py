@@ -320,6 +320,15 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.observe_device(P(d_obs, i), P(d_codes, i), d_obs32=P(d_obs32, i)))
 
+    def grid_shape(self, extended=False):
+        return self.shards[0].grid_shape(extended)
+
+    def observe_grid_device(self, d_bits=None, d_grid8=None, d_grid32=None, d_agent_xy=None, extended=False):
+        """`CookingVecEnv.observe_grid_device` on every shard over its part of the ShardedBuffers (per env: bits uint32 [W, H, C / 32],
+        grid8 uint8 [W, H, C], grid32 float32 [W, H, C], agent_xy int32 [A, 2])"""
+        P = self._part
+        self._each(lambda i, env: env.observe_grid_device(P(d_bits, i), P(d_grid8, i), P(d_grid32, i), P(d_agent_xy, i), extended=extended))
+
     def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
         """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids
         int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""

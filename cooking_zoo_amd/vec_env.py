@@ -12,7 +12,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, rotation as _rotation, soa
+from cooking_zoo_amd import _native, grid as _grid, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -584,6 +584,34 @@ class CookingVecEnv:
             _native.check(self._h, _native.lib().cz_observe_device(self._h, env_begin, n, _dev_ptr(d_obs), _dev_ptr(d_codes)))
         if d_obs32 is not None:
             _native.check(self._h, _native.lib().cz_observe_device_f32(self._h, env_begin, n, _dev_ptr(d_obs32)))
+
+    def grid_shape(self, extended=False):
+        """(W, H, C) of one env's grid observation: C = 32 reference channels, 48 when `extended` (cooking_zoo_amd/grid.py)"""
+        return (self.dims.W, self.dims.H, _grid.n_channels(extended))
+
+    def observe_grid_device(self, d_bits=None, d_grid8=None, d_grid32=None, d_agent_xy=None, extended=False, env_begin=0, env_count=None):
+        """the grid observation of the current state - the reference's (W, H, 32) `full` tensor, cell (x, y) at x * H + y - into
+        device buffers, stream-ordered and capturable: `d_bits` uint32 [n, W, H, C / 32], `d_grid8` uint8 [n, W, H, C], `d_grid32`
+        float32 [n, W, H, C] (a torch tensor's `permute(0, 3, 1, 2)` is the channels_last image), `d_agent_xy` int32 [n, A, 2];
+        at least one of them"""
+        n = self.num_envs if env_count is None else int(env_count)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_observe_grid_device(self._h, env_begin, n, int(extended), p(d_bits), p(d_grid8), p(d_grid32),
+                                                                    p(d_agent_xy)))
+
+    def observe_grid(self, extended=False, env_begin=0, env_count=None):
+        """host convenience: (uint8 [n, W, H, C], int32 [n, A, 2]) of envs [env_begin, env_begin + n)"""
+        n = self.num_envs if env_count is None else int(env_count)
+        shape = (n,) + self.grid_shape(extended)
+        if n == 0:
+            return np.zeros(shape, np.uint8), np.zeros((0, self.num_agents, 2), np.int32)
+        d_grid, d_xy = DeviceBuffer(self, shape, np.uint8), DeviceBuffer(self, (n, self.num_agents, 2), np.int32)
+        try:
+            self.observe_grid_device(d_grid8=d_grid, d_agent_xy=d_xy, extended=extended, env_begin=env_begin, env_count=n)
+            return d_grid.to_host(), d_xy.to_host()
+        finally:
+            d_grid.free()
+            d_xy.free()
 
     # ------------------------------------------------------------------ device-resident API
     def alloc(self, shape, dtype):

@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -312,6 +312,24 @@ int cz_observe_device(cz_handle h, int64_t env_begin, int64_t env_count, double 
 /* ... and as FLOAT32 rows (cooking_env.py:271,352-373 in the dtype of cz_step_device_f32): device buffer float [env_count][A][F],
  * dense.  Stream-ordered, nothing is synchronised. */
 int cz_observe_device_f32(cz_handle h, int64_t env_begin, int64_t env_count, float *d_obs32);
+
+/* The GRID observation: the spatial state tensor the reference declares for obs_spaces=["full"] - a (width, height,
+ * graph_representation_length) tensor next to agent_location and goal_vector (cooking_env.py:118-123, 274-278), allocated at
+ * cooking_env.py:149-150 and never written upstream - filled from the per-object vectors every class of world_objects.py carries
+ * (numeric_state_representation(), state_length(); 32 channels in GAME_CLASSES order, all 0 / 1, the maximum where objects of a
+ * class share a cell).  extended = 1 appends 16 channels the reference vectors leave out (mashed food, free / held / in-plate,
+ * appliance and switch state, which agent stands where); cooking_zoo_amd/grid.py names every channel and is the host model.
+ * Cell (x, y) is at index x * H + y - the reference's (W, H, C) per env - in every form, C = cz_grid_channels(extended):
+ *   d_bits    uint32 [env_count][W][H][C / 32]   channel c = bit c & 31 of word c >> 5           (8-byte aligned)
+ *   d_grid8   uint8  [env_count][W][H][C]        0 / 1                                           (16-byte aligned)
+ *   d_grid32  float  [env_count][W][H][C]        exactly 0.0f / 1.0f                             (16-byte aligned)
+ *   d_agent_xy int32 [env_count][A][2]           the agent_location entry
+ * Any of the four may be NULL (not all); every channel of every cell of a named form is written.  env_count == 0 returns 0.
+ * Refused: all four NULL, extended other than 0 / 1, a range outside the batch.  Stream-ordered on the handle's stream: no copy, no
+ * wait, no query - legal inside a stream capture of the caller. */
+int cz_observe_grid_device(cz_handle h, int64_t env_begin, int64_t env_count, int32_t extended,
+                           uint32_t *d_bits, uint8_t *d_grid8, float *d_grid32, int32_t *d_agent_xy);
+int32_t cz_grid_channels(int32_t extended);     /* 32 or 48; -1 for any other argument */
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
