@@ -1522,6 +1522,24 @@ extern "C" int cz_observe_grid_device(cz_handle h, int64_t b, int64_t c, int32_t
     HIPCHK(h, h->kl.observe_grid(h->P, h->stream, b, (int)c, extended, d_bits, d_grid8, d_grid32, d_agent_xy));
     return 0;
 }
+// Shortest-path navigation on the current state into DEVICE buffers (k_navigate, cz_kernels.h; definition: cooking_zoo_amd/nav.py):
+// first move, path length and / or the whole distance field for every agent and T candidate goals each.  Stream-ordered, nothing is
+// copied, waited for or queried (legal inside a stream capture of the caller); the records are only read.
+extern "C" int32_t cz_nav_max_targets(void) { return NAV_MAX_TARGETS; }
+extern "C" int cz_navigate_device(cz_handle h, int64_t b, int64_t c, int32_t T, uint32_t flags, const int32_t *d_target, int32_t *d_action,
+                                  int32_t *d_steps, uint16_t *d_field) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (T < 1 || T > NAV_MAX_TARGETS) return fail(h, "cz_navigate_device: T is %d, not in 1..%d targets per agent", T, NAV_MAX_TARGETS);
+    if (flags & ~NAV_KNOWN_FLAGS) return fail(h, "cz_navigate_device: unknown flags bits 0x%x", flags & ~NAV_KNOWN_FLAGS);
+    if (c == 0) return 0;
+    if (!d_target) return fail(h, "cz_navigate_device: d_target is null");
+    if (!d_action && !d_steps && !d_field) return fail(h, "cz_navigate_device: all three output pointers are null");
+    if (((uintptr_t)d_target | (uintptr_t)d_action | (uintptr_t)d_steps) & 3u || (uintptr_t)d_field & 1u)
+        return fail(h, "cz_navigate_device: d_target, d_action and d_steps must be 4-byte aligned, d_field 2-byte");
+    if (set_device(h)) return 1;
+    HIPCHK(h, h->kl.navigate(h->P, h->stream, b, (int)c, T, flags, d_target, d_action, d_steps, d_field));
+    return 0;
+}
 // host mirror of the table the float32 rows are gathered from: what the kernels make of the float64 table while they stage it
 // (v_cvt_f32_f64, round to nearest even) is what this conversion makes of the host copy
 extern "C" int cz_obs_table_f32(cz_handle h, float *table) {

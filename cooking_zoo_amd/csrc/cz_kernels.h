@@ -1288,6 +1288,138 @@ __global__ __launch_bounds__(64) void k_observe_grid(const Params P, int64_t env
     }
 }
 
+// Shortest-path navigation (cz_navigate_device): BaseAgent.walk_to_location and reachable of the reference's scripted partner
+// (cooking_agents/base_agent.py:62-126) for every agent of every env and up to NAV_MAX_TARGETS candidate goals each;
+// cooking_zoo_amd/nav.py is the definition and the host model.  The reference searches breadth first from the agent over the Floor
+// tiles, the goal admitted whatever it is, neighbours in the order of the walk codes 1:(-1,0) 2:(+1,0) 3:(0,+1) 4:(0,-1), and
+// returns the first move of the first path found: the lexicographically smallest shortest path.  So no queue order is
+// reproduced: a flood fill from the GOAL over the Floor set gives field[c], and the answer for a start s is the neighbour of s
+// with the smallest field, the first code on ties (steps = field + 1; no finite neighbour: action 0, steps -1; s == g: 0, 0).
+// A pure function of the record, one wavefront per env and workgroup:
+//   1. the Floor set (with NAV_WALKABLE_BLOCKS: and the Blocks whose walkable bit is set) and the "not the first / last column"
+//      sets are wave-uniform, a ballot per 64 cells over the cell lanes (record order c = y * W + x), as agents_walk builds
+//      walk_set; the column comes from the constant block's coordinate table (no division);
+//   2. lane q < NA * T owns query q = (agent q / T, candidate q % T) and runs the whole fill in its own registers on bit sets of
+//      CPL 64-bit words: frontier -> (west | east | south | north of it) & floor & ~visited, the shifts by 1 masked by the column
+//      sets, the shifts by W carried across words.  The lane looks at every frontier for the neighbours of its start (`nb`):
+//      the first frontier that holds one answers action and steps without a distance array, and the lane's fill ends there;
+//   3. with a field output (the second, slower instantiation of the body) the fill runs until its frontier is empty and the
+//      lane stores the distance of every cell of every frontier, then 0xFFFF for the cells it never reached: every cell of the
+//      field is written exactly once, at x * H + y (a transposition table in LDS).
+// The fill loop runs at most W * H times whatever the record holds (no path is longer), and ends early once every lane's
+// frontier is empty.  Plain stores; a target outside the grid is "no target" (action 0, steps -1, field all 0xFFFF), and so is
+// an agent whose stored location is outside the grid (no valid record has one) - nothing is indexed unchecked.
+constexpr int NAV_MAX_TARGETS = 8;
+constexpr uint32_t NAV_WALKABLE_BLOCKS = 1u, NAV_KNOWN_FLAGS = NAV_WALKABLE_BLOCKS;
+// the cells next to the cells of `s`
+template <int CPL>
+__device__ __forceinline__ Mask<CPL> nav_spread(const Mask<CPL> &s, const Mask<CPL> &not_first, const Mask<CPL> &not_last, uint32_t W) {
+    Mask<CPL> east, west, r;                                          // who may step to x + 1 / x - 1
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        east.w[k] = s.w[k] & not_last.w[k];
+        west.w[k] = s.w[k] & not_first.w[k];
+    }
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        uint64_t v = (east.w[k] << 1) | (west.w[k] >> 1) | (s.w[k] << W) | (s.w[k] >> W);           // (1 <= W <= 32)
+        if (k > 0) v |= (east.w[k - 1] >> 63) | (s.w[k - 1] >> (64u - W));
+        if (k + 1 < CPL) v |= (west.w[k + 1] << 63) | (s.w[k + 1] << (64u - W));
+        r.w[k] = v;
+    }
+    return r;
+}
+template <int CPL, int NA, bool FIELD>
+__device__ __forceinline__ void navigate_env(const Params &P, int64_t env, uint32_t i, uint32_t T, uint32_t flags, const int32_t *target,
+                                             int32_t *action_out, int32_t *steps_out, uint16_t *field_out, uint16_t *tr) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t W = (uint32_t)P.W, H = (uint32_t)P.H, C = W * H;
+    const uint32_t *rec = P.state + (size_t)env * P.RW;
+    const uint32_t aw = ldg<uint32_t>(rec, (AGENT_WORD0 + (lane & 3u)) * 4u);                     // lane a = agent a
+    const uint64_t blocks_too = (flags & NAV_WALKABLE_BLOCKS) ? ~0ull : 0ull;
+    Mask<CPL> floor, not_first, not_last;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const uint32_t c = lane + 64u * k;
+        const uint32_t cv = ldg<uint8_t>(rec, CELL_WORD0 * 4u + min(c, C - 1u));                   // (clamped: inside the record)
+        const uint32_t cw = ldg<uint32_t>(P.lut, COORD_TABLE_OFFSET + c * 4u);
+        const uint32_t x = ((cw & 0xFFFFu) >> 3) - (W - 1u), y = (cw >> 19) - ((uint32_t)LUT_Y0 + H - 1u);
+        const uint64_t inside = ballot(c < C);
+        floor.w[k] = (ballot((cv & CELL_TYPE) == FLOOR) | (ballot((cv & (CELL_TYPE | CELL_WALK)) == (BLOCK | CELL_WALK)) & blocks_too)) & inside;
+        not_first.w[k] = ballot(x != 0u);
+        not_last.w[k] = ballot(x != W - 1u);
+        if (FIELD) tr[c] = (uint16_t)(c < C ? x * H + y : 0u);                                    // (c < C: x < W, y < H, below C)
+    }
+    if (FIELD) __syncthreads();                                                                    // (one wave: the LDS fence)
+    const uint32_t nq = (uint32_t)NA * T;                                                          // (T <= 8: at most 32 queries)
+    const bool mine = lane < nq;
+    const uint32_t q = mine ? lane : 0u, a = q / T;
+    uint32_t sw = 0u;
+#pragma unroll
+    for (int b = 0; b < NA; ++b) sw = a == (uint32_t)b ? rdl(aw, b) : sw;
+    const uint32_t sx = sw & 0xFFu, sy = (sw >> 8) & 0xFFu;
+    const size_t q0 = (size_t)i * nq + q;
+    int32_t gx = -1, gy = -1;
+    if (mine) {
+        gx = target[q0 * 2];
+        gy = target[q0 * 2 + 1];
+    }
+    const bool goal_in = (uint32_t)gx < W && (uint32_t)gy < H, start_in = sx < W && sy < H;
+    const uint32_t g = goal_in ? (uint32_t)gy * W + (uint32_t)gx : 0u, s = start_in ? sy * W + sx : 0u;   // both below C
+    Mask<CPL> vis = Mask<CPL>::zero(), nb = Mask<CPL>::zero();
+    if (goal_in) vis.set((int)g);
+    bool open = goal_in && start_in && s != g;                                                     // still looking for the first move
+    if (open) {
+        if (sx > 0u) nb.set((int)(s - 1u));
+        if (sx + 1u < W) nb.set((int)(s + 1u));
+        if (sy + 1u < H) nb.set((int)(s + W));
+        if (sy > 0u) nb.set((int)(s - W));
+    }
+    int32_t act = 0, steps = goal_in && start_in && s == g ? 0 : -1;
+    uint16_t *field = FIELD && mine ? field_out + q0 * C : nullptr;
+    if (FIELD && mine && goal_in) field[tr[g]] = (uint16_t)0;
+    Mask<CPL> fr = vis;                                                                            // the cells whose field is d
+#pragma nounroll
+    for (uint32_t d = 0; d < C; ++d) {                                                             // the hard trip limit
+        if (open && (fr & nb).any()) {
+            steps = (int32_t)d + 1;
+            act = (sx > 0u && fr.test((int)(s - 1u))) ? 1 : (sx + 1u < W && fr.test((int)(s + 1u))) ? 2 : (sy + 1u < H && fr.test((int)(s + W))) ? 3 : 4;
+            open = false;
+        }
+        if (!FIELD && !open) fr = Mask<CPL>::zero();
+        if (ballot(fr.any()) == 0ull) break;
+        fr = nav_spread(fr, not_first, not_last, W) & floor;
+        fr = fr.andnot(vis);
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) vis.w[k] |= fr.w[k];
+        if (FIELD && mine) {
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                for (uint64_t u = fr.w[k]; u; u &= u - 1ull) field[tr[64u * k + (uint32_t)__builtin_ctzll(u)]] = (uint16_t)(d + 1u);
+            }
+        }
+    }
+    if (mine) {
+        if (action_out) action_out[q0] = act;
+        if (steps_out) steps_out[q0] = steps;
+        if (FIELD) {
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                const uint64_t cells = 64u * (k + 1) <= C ? ~0ull : 64u * k < C ? (1ull << (C - 64u * k)) - 1ull : 0ull;
+                for (uint64_t u = cells & ~vis.w[k]; u; u &= u - 1ull) field[tr[64u * k + (uint32_t)__builtin_ctzll(u)]] = (uint16_t)0xFFFFu;
+            }
+        }
+    }
+}
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_navigate(const Params P, int64_t env_begin, int32_t T, uint32_t flags, const int32_t *target,
+                                                 int32_t *action_out, int32_t *steps_out, uint16_t *field_out) {
+    __shared__ uint16_t tr[64 * CPL];
+    const uint32_t i = blockIdx.x;
+    if (field_out) navigate_env<CPL, NA, true>(P, env_begin + i, i, (uint32_t)T, flags, target, action_out, steps_out, field_out, tr);
+    else navigate_env<CPL, NA, false>(P, env_begin + i, i, (uint32_t)T, flags, target, action_out, steps_out, nullptr, tr);
+}
+
 // reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
 // when mask[e] != 0 or, without a mask, when its status word has the done bit - what the auto-reset pass of step_env does to such an
 // env, without spending a step.  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load,
@@ -1453,6 +1585,8 @@ struct Launchers {
                                 unsigned long long *);
     // k_observe_grid: first env, count, extended, then bits, grid8, grid32, agent_xy (any may be null)
     hipError_t (*observe_grid)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t *, uint8_t *, float *, int32_t *);
+    // k_navigate: first env, count, T, flags, targets, then actions, steps, field (any may be null)
+    hipError_t (*navigate)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t, const int32_t *, int32_t *, int32_t *, uint16_t *);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1546,8 +1680,14 @@ struct Inst {
                                    float *grid32, int32_t *agent_xy) {
         return CZ_LAUNCH_PER_ENV(k_observe_grid, n, b, extended, bits, grid8, grid32, agent_xy);
     }
+    static hipError_t navigate(const Params &P, hipStream_t st, int64_t b, int n, int32_t T, uint32_t flags, const int32_t *target,
+                               int32_t *action, int32_t *steps, uint16_t *field) {
+        return CZ_LAUNCH_PER_ENV(k_navigate, n, b, T, flags, target, action, steps, field);
+    }
 #undef CZ_LAUNCH_PER_ENV
-    static Launchers launchers() { return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid}; }
+    static Launchers launchers() {
+        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate};
+    }
 };
 
 Launchers launchers_small();   // D <= 64 slots, W*H <= 64 cells

@@ -329,6 +329,12 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.observe_grid_device(P(d_bits, i), P(d_grid8, i), P(d_grid32, i), P(d_agent_xy, i), extended=extended))
 
+    def navigate_device(self, d_target, d_action=None, d_steps=None, d_field=None, walkable_blocks=False):
+        """`CookingVecEnv.navigate_device` on every shard over its part of the ShardedBuffers (per env: target int32 [A, T, 2],
+        action and steps int32 [A, T], field uint16 [A, T, W * H])"""
+        P = self._part
+        self._each(lambda i, env: env.navigate_device(P(d_target, i), P(d_action, i), P(d_steps, i), P(d_field, i), walkable_blocks=walkable_blocks))
+
     def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
         """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids
         int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""

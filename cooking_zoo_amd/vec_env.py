@@ -12,7 +12,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, grid as _grid, rotation as _rotation, soa
+from cooking_zoo_amd import _native, grid as _grid, nav as _nav, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -612,6 +612,44 @@ class CookingVecEnv:
         finally:
             d_grid.free()
             d_xy.free()
+
+    def navigate_device(self, d_target, d_action=None, d_steps=None, d_field=None, walkable_blocks=False, env_begin=0, env_count=None,
+                        T=None):
+        """shortest-path navigation on the current state - the reference's `BaseAgent.walk_to_location` / `reachable` for every
+        agent and T candidate goals each (cooking_zoo_amd/nav.py) - into device buffers, stream-ordered and capturable:
+        `d_target` int32 [n, A, T, 2] (x, y; (-1, -1) or any off-grid value: no target), `d_action` int32 [n, A, T] (walk codes
+        0..4; with T = 1 the array `step_device` takes), `d_steps` int32 [n, A, T] (0 at the goal, -1 unreachable), `d_field`
+        uint16 [n, A, T, W * H] (cell (x, y) at x * H + y, 0xFFFF unreachable); at least one output.  T is read from the target
+        buffer's shape ([n, A, T, 2], or [n, A, 2] for T = 1) unless given."""
+        n = self.num_envs if env_count is None else int(env_count)
+        if T is None:
+            shape = tuple(getattr(d_target, "shape", ()))
+            if len(shape) not in (3, 4) or shape[-1] != 2 or shape[-3 if len(shape) == 4 else -2] != self.num_agents:
+                raise ValueError(f"navigate_device: the target buffer's shape is {shape}, not [n, A, T, 2] (or [n, A, 2]); pass T")
+            T = shape[2] if len(shape) == 4 else 1
+        flags = _nav.WALKABLE_BLOCKS if walkable_blocks else 0
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_navigate_device(self._h, env_begin, n, int(T), flags, p(d_target), p(d_action), p(d_steps),
+                                                                p(d_field)))
+
+    def navigate(self, targets, walkable_blocks=False, env_begin=0, env_count=None):
+        """host convenience: targets int [n, A, T, 2] (or [n, A, 2]) -> (actions int32 [n, A, T], steps int32 [n, A, T]) of envs
+        [env_begin, env_begin + n)"""
+        n = self.num_envs if env_count is None else int(env_count)
+        tg = np.ascontiguousarray(targets, dtype=np.int32)
+        T = tg.shape[2] if tg.ndim == 4 else 1
+        if n == 0:
+            return np.zeros((0, self.num_agents, T), np.int32), np.zeros((0, self.num_agents, T), np.int32)
+        tg = tg.reshape(n, self.num_agents, T, 2)
+        shape = (n, self.num_agents, T)
+        d_t, d_a, d_s = DeviceBuffer(self, tg.shape, np.int32), DeviceBuffer(self, shape, np.int32), DeviceBuffer(self, shape, np.int32)
+        try:
+            d_t.from_host(tg)
+            self.navigate_device(d_t, d_a, d_s, walkable_blocks=walkable_blocks, env_begin=env_begin, env_count=n)
+            return d_a.to_host(), d_s.to_host()
+        finally:
+            for b in (d_t, d_a, d_s):
+                b.free()
 
     # ------------------------------------------------------------------ device-resident API
     def alloc(self, shape, dtype):

@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -330,6 +330,31 @@ int cz_observe_device_f32(cz_handle h, int64_t env_begin, int64_t env_count, flo
 int cz_observe_grid_device(cz_handle h, int64_t env_begin, int64_t env_count, int32_t extended,
                            uint32_t *d_bits, uint8_t *d_grid8, float *d_grid32, int32_t *d_agent_xy);
 int32_t cz_grid_channels(int32_t extended);     /* 32 or 48; -1 for any other argument */
+
+/* Shortest-path NAVIGATION: walk_to_location and reachable of the reference's scripted partner (cooking_agents/base_agent.py:62-126)
+ * for every agent of every env and T candidate goals each, from the current records.  The reference searches breadth first from the
+ * agent's cell over the observation's Floor tiles, the goal cell admitted whatever it is, neighbours in the order of the walk codes
+ * 1:(-1,0) 2:(+1,0) 3:(0,+1) 4:(0,-1), and returns the first move of the first path found - the lexicographically smallest shortest
+ * path.  Here one flood fill from the goal gives field[c] (0 at the goal; for a Floor cell the length of the shortest path from the
+ * goal that enters Floor cells only; 0xFFFF everywhere else), and for the agent's cell s: s == goal gives action 0, steps 0;
+ * otherwise the neighbour of s with the smallest finite field wins, the first code on ties: action = its code, steps = field + 1;
+ * no such neighbour: action 0, steps -1.  reachable(a, b) of the reference is steps >= 0.  cooking_zoo_amd/nav.py is the host model.
+ *   d_target int32  [env_count][A][T][2]    x, y per agent and candidate                              (4-byte aligned)
+ *   d_action int32  [env_count][A][T]       0..4, the walk codes both action schemes share; with T = 1 the [N][A] array cz_step_device takes
+ *   d_steps  int32  [env_count][A][T]       path length, 0 at the goal, -1 unreachable / no target
+ *   d_field  uint16 [env_count][A][T][W*H]  cell (x, y) at x * H + y as in the grid observation; 0xFFFF unreachable (2-byte aligned)
+ * Any of the three outputs may be NULL (not all).  T in 1..cz_nav_max_targets(); flags: known bits only.  env_count == 0 returns 0.
+ * Deviations from the reference: a target with a coordinate outside [0, W) x [0, H) is "no target" - action 0, steps -1, field all
+ * 0xFFFF; (-1, -1) is the padding value (the reference would walk towards an off-grid goal next to a floor tile); a despawned agent is
+ * routed from its stored location; the reference's reachable() cache can answer from a stale world, there is no cache here.
+ * Refused: all three outputs NULL, d_target NULL, T outside 1..8, unknown flag bits, a range outside the batch.  Stream-ordered on
+ * the handle's stream: no copy, no wait, no query, no allocation - legal inside a stream capture of the caller; the records are
+ * only read. */
+#define CZ_NAV_WALKABLE_BLOCKS 1u  /* a Block whose walkable bit is set counts as floor too (what world_step lets an agent enter);
+                                      default: Floor cells only, what BaseAgent sees */
+int32_t cz_nav_max_targets(void);  /* 8 */
+int cz_navigate_device(cz_handle h, int64_t env_begin, int64_t env_count, int32_t T, uint32_t flags,
+                       const int32_t *d_target, int32_t *d_action, int32_t *d_steps, uint16_t *d_field);
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
