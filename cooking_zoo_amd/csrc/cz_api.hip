@@ -276,6 +276,15 @@ struct cz_handle_s {
     int n_layouts = 0, n_recipes = 0;
     uint32_t *d_state = nullptr, *d_lay_init = nullptr, *d_lay_desc = nullptr, *d_recipes = nullptr;
     uint32_t *d_lay_block = nullptr;       // the allocation behind d_lay_init: LAY_CTL_WORDS control words, then the records
+    uint16_t *d_lay_rank = nullptr;        // [L][W * H]: the position of a cell's static object in world_objects[class] (cz_load_layout_ranks, cz_generate_layouts)
+    std::vector<uint8_t> rank_ok;          // per pool slot: its rank row belongs to its layout
+    int rank_missing = 0;                  // how many do not
+    uint16_t *h_rank_stage = nullptr;      // pinned staging of cz_load_layout_ranks, a place per slot
+    hipStream_t rank_stream = nullptr;     // its copies run here; the handle's stream waits for them on the device
+    hipEvent_t ev_rank_done = nullptr;
+    uint32_t *d_partner = nullptr;         // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
+    int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
+    int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
     char *h_lay_stage = nullptr;           // pinned staging of cz_update_layouts: [L] records, then [L] descriptors
     hipStream_t copy_stream = nullptr;     // cz_update_layouts copies run here, beside the steps
     hipEvent_t ev_copy_done = nullptr, ev_steps_issued = nullptr;
@@ -364,6 +373,7 @@ struct cz_handle_s {
 static thread_local std::string g_err;
 static int ready(cz_handle h);
 static int set_device(cz_handle h);
+static void mark_ranks(cz_handle h, int32_t first, int32_t count, int ok);
 static int flush_updates(cz_handle h, bool force);
 
 static int fail(cz_handle h, const char *fmt, ...) {
@@ -618,7 +628,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -629,6 +639,9 @@ extern "C" int cz_destroy(cz_handle h) {
     if (h->ev_steps_issued) (void)hipEventDestroy(h->ev_steps_issued);
     if (h->ev_main_copy_done) (void)hipEventDestroy(h->ev_main_copy_done);
     if (h->h_lay_stage) (void)hipHostFree(h->h_lay_stage);
+    if (h->rank_stream) { (void)hipStreamSynchronize(h->rank_stream); (void)hipStreamDestroy(h->rank_stream); }
+    if (h->ev_rank_done) (void)hipEventDestroy(h->ev_rank_done);
+    if (h->h_rank_stage) (void)hipHostFree(h->h_rank_stage);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_small) (void)hipHostFree(h->h_small);
     if (h->h_marks) (void)hipHostFree(h->h_marks);
@@ -792,6 +805,7 @@ extern "C" int cz_load_recipes(cz_handle h, const uint32_t *table, int32_t n, in
     h->n_recipes = n;
     h->P.recipes = h->d_recipes;
     h->tables_version++;
+    h->n_partner = 0;                      // the partner table was built from the book this call replaces: cz_load_partner_table again
     // Carrying an object from cell to cell changes no co-location (hence no recipe mark) when at most two agents
     // exist (they can never share a cell, cooking_world.py:206-221) and no recipe relates a dynamic-class node to a
     // node of a walkable static class (Floor, Switch, Block) -- the only statics a carried object can be "at".
@@ -863,6 +877,9 @@ extern "C" int cz_load_layouts(cz_handle h, const uint32_t *init_records, const 
     }
     if (h->d_lay_block) { HIPCHK(h, hipFree(h->d_lay_block)); h->d_lay_block = nullptr; h->d_lay_init = nullptr; h->P.lay_init = nullptr; }
     if (h->d_lay_desc) { HIPCHK(h, hipFree(h->d_lay_desc)); h->d_lay_desc = nullptr; h->P.lay_desc = nullptr; }
+    if (h->rank_stream) HIPCHK(h, hipStreamSynchronize(h->rank_stream));
+    if (h->d_lay_rank) { HIPCHK(h, hipFree(h->d_lay_rank)); h->d_lay_rank = nullptr; }
+    if (h->h_rank_stage) { HIPCHK(h, hipHostFree(h->h_rank_stage)); h->h_rank_stage = nullptr; }
     if (h->h_lay_stage) { HIPCHK(h, hipHostFree(h->h_lay_stage)); h->h_lay_stage = nullptr; }
     size_t b0 = (size_t)n * h->P.RW * 4, b1 = (size_t)n * h->P.F * 4;
     // the records, behind LAY_CTL_WORDS control words (which part of their pool slices the envs draw from: all of it)
@@ -872,6 +889,11 @@ extern "C" int cz_load_layouts(cz_handle h, const uint32_t *init_records, const 
     HIPCHK(h, hipMemsetAsync(h->d_lay_block, 0, LAY_CTL_WORDS * 4, h->stream));
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->d_lay_block + LC_GROUPS), 1, 1, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_lay_desc, 0, b1 + 16, h->stream));
+    const size_t b2 = (size_t)n * h->P.W * h->P.H * sizeof(uint16_t);
+    HIPCHK(h, hipMalloc(&h->d_lay_rank, b2));
+    HIPCHK(h, hipMemsetAsync(h->d_lay_rank, 0, b2, h->stream));
+    h->rank_ok.assign((size_t)n, 0);
+    h->rank_missing = n;
     HIPCHK(h, hipMemcpyAsync(h->d_lay_init, init_records, b0, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_lay_desc, obs_desc, b1, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -963,6 +985,7 @@ extern "C" int cz_update_layouts(cz_handle h, int32_t first, int32_t count, cons
     // LATER, by whichever call of this handle first finds that those steps have completed (flush_updates), with nothing to
     // wait for on the device.
     HIPCHK(h, hipEventRecord(h->ev_steps_issued, h->stream));
+    mark_ranks(h, first, count, 0);       // (cz_load_layout_ranks follows)
     h->upd_ranges.push_back({first, count});
     h->n_layout_updates += count;
     return flush_updates(h, false);
@@ -1116,11 +1139,12 @@ extern "C" int cz_generate_layouts(cz_handle h, int32_t first, int32_t count, ui
     }
     if (h->P.RW > (CELL_WORD0 + 256 + 2 * 255 + 15) / 16 * 16) return fail(h, "cz_generate_layouts: record longer than the generator's staging");
     GenParams G = h->gen;
-    G.lay_init = h->d_lay_init; G.lay_desc = h->d_lay_desc;
+    G.lay_init = h->d_lay_init; G.lay_desc = h->d_lay_desc; G.lay_rank = h->d_lay_rank;
     G.seed = seed; G.generation = generation; G.first = first;
     hipLaunchKernelGGL(k_generate_layouts, dim3((unsigned)count), dim3(64), 0, h->stream, G);
     HIPCHK(h, hipGetLastError());
     h->n_layout_updates += count;
+    mark_ranks(h, first, count, 1);       // (a failed draw keeps the slot's row as well)
     return 0;
 }
 // draws that failed since cz_load_level_programs (the reference raises ValueError there; the slot kept its content); -1 on error
@@ -1141,6 +1165,13 @@ static int copy_back_and_wait(cz_handle h, hipError_t rc, void *dst, const void 
     return 0;
 }
 
+// pool slots [first, first + count) have (ok = 1) / have lost (0) the rank rows of their layouts
+static void mark_ranks(cz_handle h, int32_t first, int32_t count, int ok) {
+    for (int32_t l = first; l < first + count; ++l) {
+        h->rank_missing += (int)h->rank_ok[(size_t)l] - ok;
+        h->rank_ok[(size_t)l] = (uint8_t)ok;
+    }
+}
 static int check_range(cz_handle h, int64_t b, int64_t c) {
     if (!h) return fail(nullptr, "null handle");
     if (b < 0 || c < 0 || b + c > h->P.N) return fail(h, "env range [%lld, %lld) outside [0, %d)", (long long)b, (long long)(b + c), h->P.N);
@@ -1539,6 +1570,96 @@ extern "C" int cz_navigate_device(cz_handle h, int64_t b, int64_t c, int32_t T, 
     if (set_device(h)) return 1;
     HIPCHK(h, h->kl.navigate(h->P, h->stream, b, (int)c, T, flags, d_target, d_action, d_steps, d_field));
     return 0;
+}
+// The rank rows of pool slots [first, first + count): uint16 [count][W * H], the position of every cell's static object in
+// world_objects[class] (Layout.static_lists) - the list order the scripted partner breaks ties by, which the records do not hold.
+// The caller's array is free again when this returns; in place before anything issued later on the handle's stream runs.  Like
+// cz_update_layouts only for slots that no env plays on, and not inside a stream capture.
+extern "C" int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, const uint16_t *ranks) {
+    if (ready(h)) return 1;
+    if (first < 0 || count < 0 || (int64_t)first + count > h->n_layouts || (count > 0 && !ranks))
+        return fail(h, "cz_load_layout_ranks: slots [%d, %d) outside the resident pool of %d layouts", first, first + count, h->n_layouts);
+    if (count == 0) return 0;
+    const size_t C = (size_t)h->P.W * h->P.H;
+    for (size_t k = 0; k < (size_t)count * C; ++k)
+        if (ranks[k] >= C) return fail(h, "cz_load_layout_ranks: rank %u at %zu is not below the %zu cells", (unsigned)ranks[k], k, C);
+    if (set_device(h)) return 1;
+    if (caller_capturing(h)) return fail(h, "cz_load_layout_ranks: not inside a stream capture of the caller (it copies from the host)");
+    // through a pinned staging block of the library, on a stream of its own: the caller's thread does not wait for the steps it has
+    // issued (a refill under a stepping batch), and what it issues next on the handle's stream waits for the copy on the device
+    if (!h->rank_stream) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->rank_stream, hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ev_rank_done, hipEventDisableTiming));
+    }
+    if (!h->h_rank_stage) HIPCHK(h, hipHostMalloc((void **)&h->h_rank_stage, (size_t)h->n_layouts * C * sizeof(uint16_t), hipHostMallocDefault));
+    else HIPCHK(h, hipEventSynchronize(h->ev_rank_done));             // (the last copy out of the staging block: over long ago)
+    uint16_t *const stage = h->h_rank_stage + (size_t)first * C;
+    memcpy(stage, ranks, (size_t)count * C * sizeof(uint16_t));
+    HIPCHK(h, hipMemcpyAsync(h->d_lay_rank + (size_t)first * C, stage, (size_t)count * C * sizeof(uint16_t), hipMemcpyHostToDevice, h->rank_stream));
+    HIPCHK(h, hipEventRecord(h->ev_rank_done, h->rank_stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_rank_done, 0));
+    mark_ranks(h, first, count, 1);
+    return 0;
+}
+// The partner table: one row of PARTNER_ROW_WORDS words per recipe of the loaded recipe table, built by the host from the same
+// graphs (cooking_zoo_amd/partner.py partner_rows) - the node words the step kernels use keep an accept mask, which loses the
+// ORDER of a node's conditions.  Checks everything k_partner relies on.
+extern "C" int32_t cz_partner_row_words(void) { return PARTNER_ROW_WORDS; }
+extern "C" int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t n) {
+    if (!h || !rows) return fail(h, "cz_load_partner_table: bad arguments");
+    if (n != h->n_recipes) return fail(h, "cz_load_partner_table: %d rows for the %d recipes of the loaded table (cz_load_recipes first)", n, h->n_recipes);
+    for (int i = 0; i < n; ++i) {
+        const uint32_t *row = rows + (size_t)i * PARTNER_ROW_WORDS, nn = row[0];
+        if (nn < 1 || nn > (uint32_t)WIDE_NODES) return fail(h, "cz_load_partner_table: recipe %d has %u nodes, not 1..%d", i, nn, WIDE_NODES);
+        for (uint32_t j = 0; j < nn; ++j) {
+            const uint32_t a = row[1 + 2 * j], nc = (a >> 8) & 0xFFu, kids = a >> 16;
+            if (nc > (uint32_t)PARTNER_MAX_CONDS) return fail(h, "cz_load_partner_table: recipe %d node %u has %u conditions, more than %d", i, j, nc, PARTNER_MAX_CONDS);
+            if (kids >> nn || (kids >> j) & 1u) return fail(h, "cz_load_partner_table: recipe %d node %u: bad child mask %#x", i, j, kids);
+            for (uint32_t q = 0; q < nc; ++q) {
+                const uint32_t cond = (row[2 + 2 * j] >> (4 * q)) & 0xFu, attr = cond & 1u, value = (cond >> 1) & 3u;
+                if ((cond >> 3) || value > (attr ? 2u : 1u)) return fail(h, "cz_load_partner_table: recipe %d node %u: bad condition %#x", i, j, cond);
+            }
+        }
+    }
+    if (set_device(h)) return 1;
+    if (caller_capturing(h)) return fail(h, "cz_load_partner_table: not inside a stream capture of the caller (it allocates and copies)");
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_partner) { HIPCHK(h, hipFree(h->d_partner)); h->d_partner = nullptr; h->n_partner = h->partner_rows_alloc = 0; }
+    const size_t bytes = (size_t)n * PARTNER_ROW_WORDS * 4, counter = (bytes + 7) / 8 * 8;
+    HIPCHK(h, hipMalloc(&h->d_partner, counter + 8));
+    HIPCHK(h, hipMemsetAsync(h->d_partner, 0, counter + 8, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_partner, rows, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->n_partner = h->partner_rows_alloc = n;
+    return 0;
+}
+static unsigned long long *partner_counter(cz_handle h) {
+    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_partner) + ((size_t)h->partner_rows_alloc * PARTNER_ROW_WORDS * 4 + 7) / 8 * 8);
+}
+// The scripted partner on the current state into DEVICE buffers (k_partner, cz_kernels.h; definition: cooking_zoo_amd/partner.py): the
+// action the reference's CookingAgent would return for every chosen agent of every env.  Stream-ordered, nothing is copied, waited
+// for, queried or allocated (legal inside a stream capture of the caller); the records are only read.
+extern "C" int cz_partner_device(cz_handle h, int64_t b, int64_t c, uint32_t agents, uint32_t flags, const int32_t *d_recipe, int32_t *d_action,
+                                 int32_t *d_target, uint8_t *d_status) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (agents == 0 || agents >> h->P.A) return fail(h, "cz_partner_device: agents is 0x%x, not a non-empty set of the %d agents", agents, h->P.A);
+    if (flags) return fail(h, "cz_partner_device: unknown flags bits 0x%x", flags);
+    if (!h->d_partner || h->n_partner == 0 || h->n_partner != h->n_recipes) return fail(h, "cz_partner_device: no partner table for the loaded recipes (cz_load_partner_table)");
+    if (h->rank_missing)
+        return fail(h, "cz_partner_device: %d pool slot(s) have no rank row (cz_load_layout_ranks after cz_load_layouts / cz_update_layouts)", h->rank_missing);
+    if (c == 0) return 0;
+    if (!d_action && !d_target && !d_status) return fail(h, "cz_partner_device: all three output pointers are null");
+    if (((uintptr_t)d_recipe | (uintptr_t)d_action | (uintptr_t)d_target) & 3u)
+        return fail(h, "cz_partner_device: d_recipe, d_action and d_target must be 4-byte aligned");
+    if (set_device(h)) return 1;
+    PartnerArgs G{b, agents, h->n_partner, d_recipe, h->d_partner, h->d_lay_rank, partner_counter(h), d_action, d_target, d_status};
+    HIPCHK(h, h->kl.partner(h->P, h->stream, (int)c, G));
+    return 0;
+}
+// agents that were asked for a recipe index outside the table (they got IDLE) since cz_load_partner_table; -1 on error.  Waits.
+extern "C" int64_t cz_partner_bad_recipes(cz_handle h) {
+    if (!h || !h->d_partner) return h ? 0 : -1;
+    return read_counter<unsigned long long>(h, partner_counter(h), "cz_partner_bad_recipes");
 }
 // host mirror of the table the float32 rows are gathered from: what the kernels make of the float64 table while they stage it
 // (v_cvt_f32_f64, round to nearest even) is what this conversion makes of the host copy

@@ -31,6 +31,7 @@ enum : uint32_t { GEN_AGENT = 0x20, GEN_EXCLUDED = 0x40, GEN_OCCUPIED = 0x80 };
 struct GenParams {
     uint32_t *lay_init;                 // [L][RW]
     uint32_t *lay_desc;                 // [L][F]
+    uint16_t *lay_rank;                 // [L][W * H] the position of a cell's static object in world_objects[class]
     const uint32_t *programs;           // every level's program, one after the other
     const uint32_t *prog_off;           // [n_levels] word offset of a level's program
     const uint8_t *level_of_slot;       // [L]
@@ -189,6 +190,24 @@ __global__ __launch_bounds__(64) void k_generate_layouts(const GenParams G) {
     __syncthreads();
     uint32_t *const out_rec = G.lay_init + (size_t)slot * RW;
     for (uint32_t i = lane; i < RW; i += 64u) out_rec[i] = rec[i];
+
+    // ---- the rank table (the scripted partner's list order): Floor and Counter are what is left of the base grid, row-major; the
+    // other classes in placement order - one store per static
+    {
+        uint16_t *const rk = G.lay_rank + (size_t)slot * C;
+        for (uint32_t code = FLOOR; code <= BLENDER; ++code) {
+            const bool base = code <= COUNTER;
+            const uint32_t total = base ? C : n_static;
+            uint32_t seen = 0;
+            for (uint32_t j0 = 0; j0 < total; j0 += 64u) {
+                const uint32_t j = j0 + lane;
+                const bool mine = j < total && (base ? (grid[j] & CELL_TYPE) == code : st_cls[j] == code);
+                const uint64_t m = ballot(mine);
+                if (mine) rk[base ? j : st_cell[j]] = (uint16_t)(seen + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
+                seen += (uint32_t)__popcll(m);
+            }
+        }
+    }
 
     // ---- Layout.obs_descriptor: meta-file class order, list order inside a class, zero padding up to the meta count
     uint32_t *const out = G.lay_desc + (size_t)slot * (uint32_t)G.F;

@@ -1329,6 +1329,42 @@ __device__ __forceinline__ Mask<CPL> nav_spread(const Mask<CPL> &s, const Mask<C
     }
     return r;
 }
+// the x / y of a cell from its word of the constant block's coordinate table (no division)
+__device__ __forceinline__ uint32_t coord_x(uint32_t cw, uint32_t W) { return ((cw & 0xFFFFu) >> 3) - (W - 1u); }
+__device__ __forceinline__ uint32_t coord_y(uint32_t cw, uint32_t H) { return (cw >> 19) - ((uint32_t)LUT_Y0 + H - 1u); }
+// word k of the wave-uniform sets of a fill, from the cell lanes (lane l: cell c = l + 64 k, its byte `cv`, its coordinate word
+// `cw`): the cells a path may cross - Floor, with `blocks_too` = ~0 the Blocks whose walkable bit is set as well - and the cells that
+// are not in the first / last column
+__device__ __forceinline__ void nav_sets_word(uint32_t c, uint32_t cv, uint32_t cw, uint32_t W, uint32_t C, uint64_t blocks_too,
+                                              uint64_t &floor, uint64_t &not_first, uint64_t &not_last) {
+    const uint32_t x = coord_x(cw, W);
+    const uint64_t inside = ballot(c < C);
+    floor = (ballot((cv & CELL_TYPE) == FLOOR) | (ballot((cv & (CELL_TYPE | CELL_WALK)) == (BLOCK | CELL_WALK)) & blocks_too)) & inside;
+    not_first = ballot(x != 0u);
+    not_last = ballot(x != W - 1u);
+}
+// one round of a fill: the frontier becomes the cells of `floor` next to it that were not visited, and they are visited
+template <int CPL>
+__device__ __forceinline__ void nav_advance(Mask<CPL> &fr, Mask<CPL> &vis, const Mask<CPL> &floor, const Mask<CPL> &not_first,
+                                            const Mask<CPL> &not_last, uint32_t W) {
+    fr = nav_spread(fr, not_first, not_last, W) & floor;
+    fr = fr.andnot(vis);
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) vis.w[k] |= fr.w[k];
+}
+// the four neighbours of the start s = (sx, sy) that lie in the grid, as a set ...
+template <int CPL>
+__device__ __forceinline__ void nav_neighbours(Mask<CPL> &nb, uint32_t s, uint32_t sx, uint32_t sy, uint32_t W, uint32_t H) {
+    if (sx > 0u) nb.set((int)(s - 1u));
+    if (sx + 1u < W) nb.set((int)(s + 1u));
+    if (sy + 1u < H) nb.set((int)(s + W));
+    if (sy > 0u) nb.set((int)(s - W));
+}
+// ... and the first move when the frontier `fr` holds one of them: the first walk code in the order 1:(-1,0) 2:(+1,0) 3:(0,+1) 4:(0,-1)
+template <int CPL>
+__device__ __forceinline__ int32_t nav_first_code(const Mask<CPL> &fr, uint32_t s, uint32_t sx, uint32_t sy, uint32_t W, uint32_t H) {
+    return (sx > 0u && fr.test((int)(s - 1u))) ? 1 : (sx + 1u < W && fr.test((int)(s + 1u))) ? 2 : (sy + 1u < H && fr.test((int)(s + W))) ? 3 : 4;
+}
 template <int CPL, int NA, bool FIELD>
 __device__ __forceinline__ void navigate_env(const Params &P, int64_t env, uint32_t i, uint32_t T, uint32_t flags, const int32_t *target,
                                              int32_t *action_out, int32_t *steps_out, uint16_t *field_out, uint16_t *tr) {
@@ -1343,12 +1379,8 @@ __device__ __forceinline__ void navigate_env(const Params &P, int64_t env, uint3
         const uint32_t c = lane + 64u * k;
         const uint32_t cv = ldg<uint8_t>(rec, CELL_WORD0 * 4u + min(c, C - 1u));                   // (clamped: inside the record)
         const uint32_t cw = ldg<uint32_t>(P.lut, COORD_TABLE_OFFSET + c * 4u);
-        const uint32_t x = ((cw & 0xFFFFu) >> 3) - (W - 1u), y = (cw >> 19) - ((uint32_t)LUT_Y0 + H - 1u);
-        const uint64_t inside = ballot(c < C);
-        floor.w[k] = (ballot((cv & CELL_TYPE) == FLOOR) | (ballot((cv & (CELL_TYPE | CELL_WALK)) == (BLOCK | CELL_WALK)) & blocks_too)) & inside;
-        not_first.w[k] = ballot(x != 0u);
-        not_last.w[k] = ballot(x != W - 1u);
-        if (FIELD) tr[c] = (uint16_t)(c < C ? x * H + y : 0u);                                    // (c < C: x < W, y < H, below C)
+        nav_sets_word(c, cv, cw, W, C, blocks_too, floor.w[k], not_first.w[k], not_last.w[k]);
+        if (FIELD) tr[c] = (uint16_t)(c < C ? coord_x(cw, W) * H + coord_y(cw, H) : 0u);           // (c < C: x < W, y < H, below C)
     }
     if (FIELD) __syncthreads();                                                                    // (one wave: the LDS fence)
     const uint32_t nq = (uint32_t)NA * T;                                                          // (T <= 8: at most 32 queries)
@@ -1370,10 +1402,7 @@ __device__ __forceinline__ void navigate_env(const Params &P, int64_t env, uint3
     if (goal_in) vis.set((int)g);
     bool open = goal_in && start_in && s != g;                                                     // still looking for the first move
     if (open) {
-        if (sx > 0u) nb.set((int)(s - 1u));
-        if (sx + 1u < W) nb.set((int)(s + 1u));
-        if (sy + 1u < H) nb.set((int)(s + W));
-        if (sy > 0u) nb.set((int)(s - W));
+        nav_neighbours(nb, s, sx, sy, W, H);
     }
     int32_t act = 0, steps = goal_in && start_in && s == g ? 0 : -1;
     uint16_t *field = FIELD && mine ? field_out + q0 * C : nullptr;
@@ -1383,15 +1412,12 @@ __device__ __forceinline__ void navigate_env(const Params &P, int64_t env, uint3
     for (uint32_t d = 0; d < C; ++d) {                                                             // the hard trip limit
         if (open && (fr & nb).any()) {
             steps = (int32_t)d + 1;
-            act = (sx > 0u && fr.test((int)(s - 1u))) ? 1 : (sx + 1u < W && fr.test((int)(s + 1u))) ? 2 : (sy + 1u < H && fr.test((int)(s + W))) ? 3 : 4;
+            act = nav_first_code(fr, s, sx, sy, W, H);
             open = false;
         }
         if (!FIELD && !open) fr = Mask<CPL>::zero();
         if (ballot(fr.any()) == 0ull) break;
-        fr = nav_spread(fr, not_first, not_last, W) & floor;
-        fr = fr.andnot(vis);
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) vis.w[k] |= fr.w[k];
+        nav_advance(fr, vis, floor, not_first, not_last, W);
         if (FIELD && mine) {
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {
@@ -1418,6 +1444,413 @@ __global__ __launch_bounds__(64) void k_navigate(const Params P, int64_t env_beg
     const uint32_t i = blockIdx.x;
     if (field_out) navigate_env<CPL, NA, true>(P, env_begin + i, i, (uint32_t)T, flags, target, action_out, steps_out, field_out, tr);
     else navigate_env<CPL, NA, false>(P, env_begin + i, i, (uint32_t)T, flags, target, action_out, steps_out, nullptr, tr);
+}
+
+// The scripted partner (cz_partner_device): CookingAgent.step of the reference (cooking_agents/cooking_agent.py:9-119,
+// base_agent.py:128-198) for the chosen agents of every env - which object to walk to, and the first move of the walk;
+// cooking_zoo_amd/partner.py is the definition and the host model.  A pure function of the record, one wavefront per env and
+// workgroup:
+//   1. the off-step kernels' shared load puts cells and slots on the lanes; the wave stages them in LDS with, per cell, its
+//      coordinates and its static object's rank in world_objects[class] (the layout pool's rank table), and builds the wave-uniform
+//      sets: the cells of every static type and the Floor / column sets of the fill (ballots), the cells an object lies on directly
+//      (LDS atomics);
+//   2. lane a < NA is agent a.  One fill from the agent's cell over the Floor set, in the lane's registers (nav_advance), gives what
+//      is reachable: the fill, its 4-neighbours and the agent's cell;
+//   3. the lane evaluates update_recipe_state of the asked recipe from the partner table (matched-location sets per node in LDS),
+//      takes the unmarked node with the highest index and runs the condition branch: candidates in list order, the first minimum of
+//      (unmet conditions, squared distance, list rank), the first unmet condition in the node's order, generic_sequence - the
+//      statics by sets, `closest` as the first minimum of (squared distance, list rank);
+//   4. every lane with a goal walks (nav_route: the fill from the goal of k_navigate, all lanes together); a result of 0 falls
+//      through to the contains branch: counts of matching child objects per cell, the main object, the nearest child object that is
+//      not at its cell; and a second walk.
+// Every loop is bounded by D, W * H, the node count (16) or the conditions of a node (8) whatever the record and the tables hold;
+// a slot outside the grid or of no class (no valid record has one) is not an object, an agent outside the grid is IDLE.  The
+// records are only read; plain stores; the entries of agents that are not driven are not written.
+enum : uint32_t { PS_DONE = 0, PS_WALK, PS_IDLE, PS_RAISES, PS_ABSENT };
+// partner table, one row per recipe: the node count, then per node  class | conditions << 8 | child mask << 16  and the conditions,
+// 4 bits each in the node's order: attribute (0 chop_state, 1 blend_state) | wanted value << 1 (0 fresh, 1 chopped / in progress, 2 mashed)
+constexpr int PARTNER_ROW_WORDS = 1 + 2 * WIDE_NODES, PARTNER_MAX_CONDS = 8;
+struct PartnerArgs {
+    int64_t env_begin;
+    uint32_t agents;                   // bit a: agent a is driven
+    int32_t n_recipes;
+    const int32_t *recipe;             // [count][A] indices into the table, or null: the env's own
+    const uint32_t *table;             // [n_recipes][PARTNER_ROW_WORDS]
+    const uint16_t *lay_rank;          // [L][W * H]
+    unsigned long long *bad_recipe;    // agents asked for a recipe outside the table
+    int32_t *action, *target;
+    uint8_t *status;
+};
+template <int OPL, int CPL, int NA>
+struct PartnerLds {
+    uint32_t d0[64 * OPL], d1[64 * OPL];
+    uint32_t row[NA][PARTNER_ROW_WORDS + 3];
+    uint64_t type[8][CPL];             // the cells of every static type
+    uint64_t direct[CPL];              // the cells an object lies on directly (not held, not in a plate)
+    uint64_t reach[NA][CPL];
+    uint64_t locs[NA][WIDE_NODES][CPL];
+    uint16_t xy[64 * CPL], rank[64 * CPL];
+    uint8_t cnt[NA][64 * CPL];
+};
+// getattr(obj, attr) == value for a dynamic object (an attribute the class lacks meets nothing)
+__device__ __forceinline__ bool partner_meets(uint32_t d0, uint32_t cond) {
+    const uint32_t cls = (d0 >> 16) & 0xFFu, attr = cond & 1u, value = (cond >> 1) & 3u;
+    if (cls == PLATE) return false;
+    if (attr == 0u) return value == ((d0 & D_CHOPPED) ? 1u : 0u);
+    if (cls != CARROT && cls != BANANA) return false;
+    return value == ((d0 & D_MASHED) ? 2u : 0u);
+}
+__device__ __forceinline__ uint32_t partner_unmet(uint32_t d0, uint32_t nc, uint32_t conds) {
+    uint32_t n = 0;
+#pragma nounroll
+    for (uint32_t q = 0; q < nc && q < (uint32_t)PARTNER_MAX_CONDS; ++q) n += partner_meets(d0, (conds >> (4u * q)) & 0xFu) ? 0u : 1u;
+    return n;
+}
+// first move towards (gx, gy) for every lane with `go`, all lanes together: action 0 at the goal or when it is unreachable
+template <int CPL>
+__device__ __forceinline__ int32_t nav_route(const Mask<CPL> &floor, const Mask<CPL> &not_first, const Mask<CPL> &not_last, uint32_t W, uint32_t H,
+                                             bool go, uint32_t sx, uint32_t sy, uint32_t gx, uint32_t gy) {
+    const uint32_t C = W * H;
+    const bool ok = go && gx < W && gy < H && sx < W && sy < H;
+    const uint32_t g = ok ? gy * W + gx : 0u, s = ok ? sy * W + sx : 0u;
+    Mask<CPL> vis = Mask<CPL>::zero(), nb = Mask<CPL>::zero();
+    bool open = ok && s != g;
+    if (open) {
+        vis.set((int)g);
+        nav_neighbours(nb, s, sx, sy, W, H);
+    }
+    int32_t act = 0;
+    Mask<CPL> fr = vis;
+#pragma nounroll
+    for (uint32_t d = 0; d < C; ++d) {                                                             // the hard trip limit
+        if (open && (fr & nb).any()) {
+            act = nav_first_code(fr, s, sx, sy, W, H);
+            open = false;
+        }
+        if (!open) fr = Mask<CPL>::zero();
+        if (ballot(fr.any()) == 0ull) break;
+        nav_advance(fr, vis, floor, not_first, not_last, W);
+    }
+    return act;
+}
+template <int OPL, int CPL, int NA>
+struct Partner {
+    using L = PartnerLds<OPL, CPL, NA>;
+    L &s;
+    uint32_t a, W, H, C, D, sx, sy, s0, held;          // this lane's agent, its cell, slot + 1 in its hands
+    uint32_t held_all[NA];
+    __device__ __forceinline__ static bool bit(const uint64_t *m, uint32_t c) { return (m[c >> 6] >> (c & 63u)) & 1ull; }
+    __device__ __forceinline__ uint32_t d2(uint32_t c) const {
+        const int32_t dx = (int32_t)(s.xy[c] & 0xFFu) - (int32_t)sx, dy = (int32_t)(s.xy[c] >> 8) - (int32_t)sy;
+        return (uint32_t)(dx * dx + dy * dy);
+    }
+    // slot sl holds a live object of class `cls` inside the grid: its cell, else -1
+    __device__ __forceinline__ int32_t object_cell(uint32_t sl, uint32_t cls) const {
+        const uint32_t w = s.d0[sl], x = w & 0xFFu, y = (w >> 8) & 0xFFu;
+        return ((w & D_ALIVE) && ((w >> 16) & 0xFFu) == cls && x < W && y < H) ? (int32_t)(y * W + x) : -1;
+    }
+    // the first minimum of (squared distance, list rank) over the reachable cells of a static type, `empty`: nothing lies on them
+    __device__ __forceinline__ int32_t closest(uint32_t type, bool empty) const {
+        uint32_t best = ~0u;
+        int32_t at = -1;
+#pragma nounroll
+        for (int k = 0; k < CPL; ++k) {
+            for (uint64_t u = s.type[type][k] & s.reach[a][k] & (empty ? ~s.direct[k] : ~0ull); u; u &= u - 1ull) {
+                const uint32_t c = 64u * k + (uint32_t)__builtin_ctzll(u), key = d2(c) << 16 | s.rank[c];
+                if (key < best) { best = key; at = (int32_t)c; }
+            }
+        }
+        return at;
+    }
+    // update_recipe_state (recipe.py:77-104): the marks, and every node's matched locations in s.locs[a]
+    __device__ __forceinline__ uint32_t marks(uint32_t n) {
+        uint32_t m = 0;
+#pragma nounroll
+        for (int32_t j = (int32_t)n - 1; j >= 0; --j) {
+            const uint32_t A = s.row[a][1 + 2 * j], conds = s.row[a][2 + 2 * j], cls = A & 0xFFu, nc = (A >> 8) & 0xFu, kids = (A >> 16) & ((1u << n) - 1u);
+            uint64_t *mine = s.locs[a][j];
+#pragma nounroll
+            for (int k = 0; k < CPL; ++k) mine[k] = 0ull;
+            if (kids & ~m) continue;
+            bool any = false;
+            if (cls < 7u && nc == 0u) {
+#pragma nounroll
+                for (int k = 0; k < CPL; ++k) {
+                    uint64_t w = s.type[cls][k];
+#pragma nounroll
+                    for (uint32_t q = kids; q; q &= q - 1u) w &= s.locs[a][__builtin_ctz(q)][k];
+                    mine[k] = w;
+                    any = any || w != 0ull;
+                }
+            } else if (cls >= 16u && cls < 26u) {
+#pragma nounroll
+                for (uint32_t sl = 0; sl < D; ++sl) {
+                    const int32_t c = object_cell(sl, cls - 16u);
+                    if (c < 0 || partner_unmet(s.d0[sl], nc, conds)) continue;
+                    bool ok = true;
+#pragma nounroll
+                    for (uint32_t q = kids; q; q &= q - 1u) ok = ok && bit(s.locs[a][__builtin_ctz(q)], (uint32_t)c);
+                    if (ok) { mine[c >> 6] |= 1ull << (c & 63); any = true; }
+                }
+            }
+            if (any) m |= 1u << j;
+        }
+        return m;
+    }
+    // the condition branch (cooking_agent.py:41-53, base_agent.py:140-190): PS_WALK with a goal cell, PS_RAISES, or PS_IDLE for
+    // "0 without a walk" (the contains branch follows)
+    __device__ __forceinline__ uint32_t condition(uint32_t j, int32_t &goal) const {
+        const uint32_t A = s.row[a][1 + 2 * j], conds = s.row[a][2 + 2 * j], cls = A & 0xFFu, nc = (A >> 8) & 0xFu;
+        int32_t bs = -1, bc = -1;                                       // the best object's slot (dynamic) and cell
+        if (cls >= 16u && cls < 26u) {
+            uint32_t best = ~0u;
+#pragma nounroll
+            for (uint32_t sl = 0; sl < D; ++sl) {
+                const int32_t c = object_cell(sl, cls - 16u);
+                if (c < 0) continue;
+                const uint32_t key = partner_unmet(s.d0[sl], nc, conds) << 16 | d2((uint32_t)c);
+                if (key < best) { best = key; bs = (int32_t)sl; bc = c; }
+            }
+        } else if (cls < 7u) {
+            uint32_t best = ~0u;
+#pragma nounroll
+            for (int k = 0; k < CPL; ++k) {
+                for (uint64_t u = s.type[cls][k]; u; u &= u - 1ull) {
+                    const uint32_t c = 64u * k + (uint32_t)__builtin_ctzll(u), key = d2(c) << 16 | s.rank[c];
+                    if (key < best) { best = key; bc = (int32_t)c; }
+                }
+            }
+        }
+        if (bc < 0) return PS_RAISES;                                   // IndexError, cooking_agent.py:48
+        uint32_t appliance = 7u;
+        bool unmet = false;
+#pragma nounroll
+        for (uint32_t q = 0; q < nc && q < (uint32_t)PARTNER_MAX_CONDS && !unmet; ++q) {
+            const uint32_t cond = (conds >> (4u * q)) & 0xFu;
+            if (bs >= 0 && partner_meets(s.d0[bs], cond)) continue;
+            unmet = true;
+            appliance = cond == (0u | 1u << 1) ? (uint32_t)CUTBOARD : cond == (1u | 2u << 1) ? (uint32_t)BLENDER : 7u;
+        }
+        if (!unmet || appliance == 7u) return PS_IDLE;
+        // generic_sequence
+        bool in_hands = false;
+#pragma unroll
+        for (int b = 0; b < NA; ++b) in_hands = in_hands || (bs >= 0 && held_all[b] == (uint32_t)bs + 1u);
+        const bool lies = bs >= 0 && !in_hands && (s.d1[bs] & 0xFFu) == 0u;
+        bool some_empty = false;
+#pragma nounroll
+        for (int k = 0; k < CPL; ++k) some_empty = some_empty || (s.type[appliance][k] & s.reach[a][k] & ~s.direct[k]) != 0ull;
+        if (lies && bit(s.type[appliance], (uint32_t)bc) && bit(s.reach[a], (uint32_t)bc)) goal = bc;
+        else if (bs >= 0 && held == (uint32_t)bs + 1u) goal = some_empty ? closest(appliance, true) : closest(COUNTER, false);
+        else if (some_empty) goal = held ? closest(COUNTER, true) : bc;
+        else goal = closest(appliance, false);
+        return goal < 0 ? PS_RAISES : PS_WALK;                          // TypeError, base_agent.py:64
+    }
+    // the contains branch (cooking_agent.py:26-39, 55-119)
+    __device__ __forceinline__ uint32_t contains(uint32_t j, uint32_t n, int32_t &goal) {
+        const uint32_t A = s.row[a][1 + 2 * j], cls = A & 0xFFu, kids = (A >> 16) & ((1u << n) - 1u);
+        uint8_t *cnt = s.cnt[a];
+#pragma nounroll
+        for (uint32_t q = kids; q; q &= q - 1u) {
+            const uint32_t kj = (uint32_t)__builtin_ctz(q), KA = s.row[a][1 + 2 * kj], kconds = s.row[a][2 + 2 * kj], kcls = KA & 0xFFu, knc = (KA >> 8) & 0xFu;
+            if (kcls >= 16u && kcls < 26u) {
+#pragma nounroll
+                for (uint32_t sl = 0; sl < D; ++sl) {
+                    const int32_t c = object_cell(sl, kcls - 16u);
+                    if (c >= 0 && bit(s.reach[a], (uint32_t)c) && !partner_unmet(s.d0[sl], knc, kconds) && cnt[c] < 255u) cnt[c]++;
+                }
+            } else if (kcls < 7u && knc == 0u) {
+#pragma nounroll
+                for (int k = 0; k < CPL; ++k)
+                    for (uint64_t u = s.type[kcls][k] & s.reach[a][k]; u; u &= u - 1ull) {
+                        const uint32_t c = 64u * k + (uint32_t)__builtin_ctzll(u);
+                        if (cnt[c] < 255u) cnt[c]++;
+                    }
+            }
+        }
+        int32_t main = -1;
+        uint64_t best = ~0ull;                                          // most objects, then nearest, then first in the list
+        if (cls >= 16u && cls < 26u) {
+#pragma nounroll
+            for (uint32_t sl = 0; sl < D; ++sl) {
+                const int32_t c = object_cell(sl, cls - 16u);
+                if (c < 0 || !bit(s.reach[a], (uint32_t)c)) continue;
+                const uint64_t key = (uint64_t)(255u - cnt[c]) << 32 | (uint64_t)d2((uint32_t)c) << 16;
+                if (key < best) { best = key; main = c; }
+            }
+        } else if (cls < 7u) {
+#pragma nounroll
+            for (int k = 0; k < CPL; ++k)
+                for (uint64_t u = s.type[cls][k] & s.reach[a][k]; u; u &= u - 1ull) {
+                    const uint32_t c = 64u * k + (uint32_t)__builtin_ctzll(u);
+                    const uint64_t key = (uint64_t)(255u - cnt[c]) << 32 | (uint64_t)d2(c) << 16 | s.rank[c];
+                    if (key < best) { best = key; main = (int32_t)c; }
+                }
+        }
+        int32_t child = -1;
+        uint32_t bd = ~0u;
+        bool orphan = false;                                            // a reachable child object while there is no main object
+#pragma nounroll
+        for (uint32_t q = kids; q; q &= q - 1u) {
+            const uint32_t kcls = s.row[a][1 + 2 * __builtin_ctz(q)] & 0xFFu;
+            if (kcls >= 16u && kcls < 26u) {
+#pragma nounroll
+                for (uint32_t sl = 0; sl < D; ++sl) {
+                    const int32_t c = object_cell(sl, kcls - 16u);
+                    if (c < 0 || !bit(s.reach[a], (uint32_t)c)) continue;
+                    orphan = orphan || main < 0;
+                    if (c != main && d2((uint32_t)c) < bd) { bd = d2((uint32_t)c); child = c; }
+                }
+            } else if (kcls < 7u) {
+                uint32_t kb = ~0u;
+                int32_t kc = -1;
+#pragma nounroll
+                for (int k = 0; k < CPL; ++k)
+                    for (uint64_t u = s.type[kcls][k] & s.reach[a][k]; u; u &= u - 1ull) {
+                        const uint32_t c = 64u * k + (uint32_t)__builtin_ctzll(u), key = d2(c) << 16 | s.rank[c];
+                        orphan = orphan || main < 0;
+                        if ((int32_t)c != main && key < kb) { kb = key; kc = (int32_t)c; }
+                    }
+                if (kc >= 0 && (kb >> 16) < bd) { bd = kb >> 16; child = kc; }
+            }
+        }
+        if (orphan) return PS_RAISES;                                   // AttributeError, cooking_agent.py:63
+        if (child < 0) return PS_IDLE;
+        goal = (uint32_t)child == s0 ? main : child;
+        return PS_WALK;
+    }
+};
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_partner(const Params P, const PartnerArgs G) {
+    __shared__ PartnerLds<OPL, CPL, NA> s;
+    const uint32_t i = blockIdx.x, lane = threadIdx.x;
+    const uint32_t W = (uint32_t)P.W, H = (uint32_t)P.H, C = W * H, D = (uint32_t)P.D;
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)lane};
+    const CoordWords<CPL> cw = load_coord_words<CPL>(P, (int)lane);
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, P.state + (size_t)(G.env_begin + i) * P.RW);
+    Mask<CPL> floor, not_first, not_last;
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) nav_sets_word(lane + 64u * k, e.cell[k], cw.w[k], W, C, 0ull, floor.w[k], not_first.w[k], not_last.w[k]);
+    const uint16_t *ranks = G.lay_rank + (size_t)min(e.layout, (uint32_t)P.L - 1u) * C;            // (clamped: inside the table)
+#pragma unroll
+    for (int k = 0; k < CPL; ++k) {
+        const uint32_t c = lane + 64u * k, ty = e.cell[k] & CELL_TYPE;
+        s.xy[c] = (uint16_t)(c < C ? coord_x(cw.w[k], W) | coord_y(cw.w[k], H) << 8 : 0xFFFFu);
+        s.rank[c] = c < C ? ldg<uint16_t>(ranks, c * 2u) : (uint16_t)0;
+        s.cnt[0][c] = 0;
+        if (NA > 1) s.cnt[1 % NA][c] = 0;
+        if (NA > 2) s.cnt[2 % NA][c] = 0;
+        if (NA > 3) s.cnt[3 % NA][c] = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 8u; ++t) {
+            const uint64_t m = ballot(c < C && ty == t);
+            if (lane == 0u) s.type[t][k] = m;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) {
+        s.d0[lane + 64u * k] = e.d0[k];                                // (lanes past D hold zeros: not alive)
+        s.d1[lane + 64u * k] = e.d1[k];
+    }
+    if (lane < (uint32_t)CPL) s.direct[lane] = 0ull;
+    __syncthreads();                                                   // (one wave: the LDS fence)
+    uint32_t held_all[NA];
+#pragma unroll
+    for (int b = 0; b < NA; ++b) held_all[b] = rdl(e.agw, b) >> 24;
+#pragma unroll
+    for (int k = 0; k < OPL; ++k) {
+        const uint32_t d0 = e.d0[k], x = d0 & 0xFFu, y = (d0 >> 8) & 0xFFu, s1 = lane + 64u * k + 1u;
+        bool in_hands = false;
+#pragma unroll
+        for (int b = 0; b < NA; ++b) in_hands = in_hands || held_all[b] == s1;
+        if ((d0 & D_ALIVE) && ((d0 >> 16) & 0xFFu) < 10u && x < W && y < H && !in_hands && (e.d1[k] & 0xFFu) == 0u) {
+            const uint32_t c = y * W + x;
+            atomicOr(reinterpret_cast<unsigned long long *>(&s.direct[c >> 6]), 1ull << (c & 63u));
+        }
+    }
+    // who is asked for what
+    const bool agent = lane < (uint32_t)NA && ((G.agents >> lane) & 1u);
+    const size_t out = (size_t)i * NA + (agent ? lane : 0u);
+    const uint32_t sx = e.agw & 0xFFu, sy = (e.agw >> 8) & 0xFFu;
+    uint32_t status = PS_IDLE;
+    int32_t recipe = -1;
+    if (agent) {
+        if ((e.status >> (SPAWN_GONE0 + lane)) & 1u) status = PS_ABSENT;
+        else if (G.recipe) {
+            recipe = G.recipe[out];
+            if (recipe < 0 || recipe >= G.n_recipes) { recipe = -1; atomicAdd(G.bad_recipe, 1ull); }
+        } else {
+            recipe = (int32_t)((e.recipes >> (8u * lane)) & 0xFFu);
+            if (recipe == 0xFF) { recipe = -1; status = PS_DONE; }
+            else if (recipe >= G.n_recipes) { recipe = -1; atomicAdd(G.bad_recipe, 1ull); }
+        }
+    }
+    bool busy = agent && recipe >= 0 && sx < W && sy < H;              // still deciding
+#pragma unroll
+    for (int b = 0; b < NA; ++b) {                                     // the rows of the asked recipes, one agent after the other
+        const int32_t r = (int32_t)rdl((uint32_t)recipe, b);
+        if (r >= 0 && lane < (uint32_t)PARTNER_ROW_WORDS) s.row[b][lane] = ldg<uint32_t>(G.table, ((uint32_t)r * PARTNER_ROW_WORDS + lane) * 4u);
+    }
+    // the agent's reachability: one fill from its cell
+    const uint32_t s0 = busy ? sy * W + sx : 0u;
+    {
+        Mask<CPL> vis = Mask<CPL>::zero();
+        if (busy) vis.set((int)s0);
+        Mask<CPL> fr = vis;
+#pragma nounroll
+        for (uint32_t d = 0; d < C; ++d) {                             // the hard trip limit
+            if (ballot(fr.any()) == 0ull) break;
+            nav_advance(fr, vis, floor, not_first, not_last, W);
+        }
+        const Mask<CPL> near = nav_spread(vis, not_first, not_last, W);
+        if (lane < (uint32_t)NA) {
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) {
+                const uint64_t inside = 64u * (k + 1) <= C ? ~0ull : 64u * k < C ? (1ull << (C - 64u * k)) - 1ull : 0ull;
+                s.reach[lane][k] = (vis.w[k] | near.w[k]) & inside;
+            }
+        }
+    }
+    __syncthreads();
+    Partner<OPL, CPL, NA> p{s, lane < (uint32_t)NA ? lane : 0u, W, H, C, D, sx, sy, s0, e.agw >> 24, {}};
+#pragma unroll
+    for (int b = 0; b < NA; ++b) p.held_all[b] = held_all[b];
+    uint32_t node = 0, n = 0;
+    int32_t goal = -1;
+    bool go = false;
+    if (busy) {
+        n = min(s.row[p.a][0], (uint32_t)WIDE_NODES);
+        const uint32_t left = ~p.marks(n) & ((1u << n) - 1u);
+        if (!left) { status = PS_DONE; busy = false; }
+        else {
+            node = 31u - (uint32_t)__builtin_clz(left);
+            const uint32_t r = p.condition(node, goal);
+            if (r == PS_RAISES) { status = PS_RAISES; busy = false; }
+            go = r == PS_WALK;
+        }
+    }
+    int32_t act = nav_route<CPL>(floor, not_first, not_last, W, H, go, sx, sy, go ? s.xy[goal] & 0xFFu : 0u, go ? s.xy[goal] >> 8 : 0u);
+    if (busy && go && act) { status = PS_WALK; busy = false; }
+    go = false;
+    if (busy) {                                                        // 0 from the condition branch: the contains branch
+        goal = -1;
+        const uint32_t r = p.contains(node, n, goal);
+        status = r;
+        go = r == PS_WALK && goal >= 0;
+        if (r == PS_WALK && goal < 0) status = PS_IDLE;
+    }
+    const int32_t act2 = nav_route<CPL>(floor, not_first, not_last, W, H, go, sx, sy, go ? s.xy[goal] & 0xFFu : 0u, go ? s.xy[goal] >> 8 : 0u);
+    if (go) act = act2;
+    if (agent) {
+        const bool walked = status == PS_WALK;
+        if (G.action) G.action[out] = walked ? act : 0;
+        if (G.target) {
+            G.target[out * 2] = walked ? (int32_t)(s.xy[goal] & 0xFFu) : -1;
+            G.target[out * 2 + 1] = walked ? (int32_t)(s.xy[goal] >> 8) : -1;
+        }
+        if (G.status) G.status[out] = (uint8_t)status;
+    }
 }
 
 // reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
@@ -1587,6 +2020,8 @@ struct Launchers {
     hipError_t (*observe_grid)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t *, uint8_t *, float *, int32_t *);
     // k_navigate: first env, count, T, flags, targets, then actions, steps, field (any may be null)
     hipError_t (*navigate)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t, const int32_t *, int32_t *, int32_t *, uint16_t *);
+    // k_partner: count, then its argument block
+    hipError_t (*partner)(const Params &, hipStream_t, int, const PartnerArgs &);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -1684,9 +2119,10 @@ struct Inst {
                                int32_t *action, int32_t *steps, uint16_t *field) {
         return CZ_LAUNCH_PER_ENV(k_navigate, n, b, T, flags, target, action, steps, field);
     }
+    static hipError_t partner(const Params &P, hipStream_t st, int n, const PartnerArgs &G) { return CZ_LAUNCH_PER_ENV(k_partner, n, G); }
 #undef CZ_LAUNCH_PER_ENV
     static Launchers launchers() {
-        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate};
+        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate, &partner};
     }
 };
 

@@ -12,7 +12,7 @@ import threading as _threading
 
 import numpy as np
 
-from cooking_zoo_amd import soa
+from cooking_zoo_amd import partner as _partner, soa
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
 
 
@@ -33,7 +33,8 @@ def produce_layouts(q, stop, level_objects, meta, num_agents, dims_tuple, pool_s
             first = base + g * sub
             recs = np.stack([l.init_record(dims, first + k) for k, l in enumerate(lays)])
             desc = np.stack([l.obs_descriptor(meta, dims) for l in lays])
-            batch.append((first, lays, recs, desc))
+            ranks = np.stack([_partner.rank_table(l) for l in lays])
+            batch.append((first, lays, recs, desc, ranks))
         while not stop.is_set():
             try:
                 q.put(batch, timeout=0.1)
@@ -155,8 +156,8 @@ class ProcessRefill:
                                        f"the envs keep drawing from part {env._lay_active} of {env._lay_groups}")
                 if not self.blocking:
                     return False
-        for first, lays, recs, desc in batch:
-            env._update_layout_arrays(first, lays, recs, desc)
+        for first, lays, recs, desc, *ranks in batch:                  # (ranks: the producer's, else the env computes them)
+            env._update_layout_arrays(first, lays, recs, desc, *ranks)
         return True
 
     def stop(self):

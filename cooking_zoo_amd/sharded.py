@@ -335,6 +335,22 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.navigate_device(P(d_target, i), P(d_action, i), P(d_steps, i), P(d_field, i), walkable_blocks=walkable_blocks))
 
+    def partner_device(self, d_action=None, d_target=None, d_status=None, agents=None, d_recipe=None):
+        """`CookingVecEnv.partner_device` on every shard over its part of the ShardedBuffers (per env: action int32 [A], target
+        int32 [A, 2], status uint8 [A], recipe int32 [A])"""
+        P = self._part
+        self._each(lambda i, env: env.partner_device(P(d_action, i), P(d_target, i), P(d_status, i), agents=agents, d_recipe=P(d_recipe, i)))
+
+    def partner(self, agents=None, recipes=None):
+        """`CookingVecEnv.partner` of every shard, concatenated: (actions [N, A], targets [N, A, 2], status [N, A]); `recipes`:
+        names or table indices, one per agent or [N, A] (every shard gets the rows of its envs)"""
+        per_env = recipes is not None and np.asarray(recipes, dtype=object).ndim == 2
+        if per_env and len(recipes) != int(self._local_cuts[-1]):
+            raise ValueError(f"partner: recipes has {len(recipes)} rows, the local shards hold {int(self._local_cuts[-1])} envs")
+        cut = (lambda i: list(np.asarray(recipes, dtype=object)[self._local_cuts[i]:self._local_cuts[i + 1]])) if per_env else (lambda i: recipes)
+        parts = self._each(lambda i, env: env.partner(agents=agents, recipes=cut(i)))
+        return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+
     def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
         """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids
         int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""

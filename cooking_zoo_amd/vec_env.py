@@ -12,7 +12,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, grid as _grid, nav as _nav, rotation as _rotation, soa
+from cooking_zoo_amd import _native, grid as _grid, nav as _nav, partner as _partner, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -130,6 +130,8 @@ class BatchTables:
         # compact tables while every graph of the book has at most 8 nodes, wide ones (16) otherwise
         self.recipe_nodes = soa.NARROW_NODES if max(len(g.node_list) for g in graphs) <= soa.NARROW_NODES else soa.MAX_NODES
         self.recipe_table = np.stack([g.flatten(self.recipe_nodes) for g in graphs])
+        self.recipe_graphs = graphs                                      # the book as it stood when the tables were made
+        self.partner_rows = _partner.partner_rows(graphs)               # the scripted partner's view of the same graphs
         if isinstance(recipes, np.ndarray):
             rid = np.asarray(recipes, dtype=np.int64)
             assert rid.shape[0] == self.num_envs
@@ -236,6 +238,7 @@ class CookingVecEnv:
         self.device_id = int(device_id)
         assert L.cz_record_words(self._h) == self.dims.RW
         _native.check(self._h, L.cz_load_recipes(self._h, _ptr(self.recipe_table), len(self.book_names), self.recipe_nodes))
+        _native.check(self._h, L.cz_load_partner_table(self._h, _ptr(self.partner_rows), len(self.book_names)))
         self._upload_layouts()
         self._buffers = []
         self._ep_bufs = None                  # finished_episodes: the packed list and the count
@@ -292,6 +295,14 @@ class CookingVecEnv:
         desc = np.stack([l.obs_descriptor(self.meta, self.dims) for l in self.layouts])
         self._lay_records, self._lay_desc = recs, desc
         _native.check(self._h, _native.lib().cz_load_layouts(self._h, _ptr(recs), _ptr(desc), len(self.layouts)))
+        self._upload_ranks(0, self.layouts)
+
+    def _upload_ranks(self, first, layouts, ranks=None):
+        """the rank rows of pool slots [first, first + len(layouts)): the list order of the static objects (partner_device)"""
+        if ranks is None:
+            ranks = np.stack([_partner.rank_table(l) for l in layouts])
+        ranks = np.ascontiguousarray(ranks, dtype=np.uint16)
+        _native.check(self._h, _native.lib().cz_load_layout_ranks(self._h, int(first), len(layouts), _ptr(ranks)))
 
     def set_layouts(self, layouts):
         """Replace the whole pool (single-level batches; used by the single-env facade at reset)."""
@@ -314,8 +325,9 @@ class CookingVecEnv:
         desc = np.stack([l.obs_descriptor(self.meta, self.dims) for l in layouts])
         self._update_layout_arrays(first, layouts, recs, desc)
 
-    def _update_layout_arrays(self, first, layouts, recs, desc):
+    def _update_layout_arrays(self, first, layouts, recs, desc, ranks=None):
         _native.check(self._h, _native.lib().cz_update_layouts(self._h, int(first), len(layouts), _ptr(recs), _ptr(desc)))
+        self._upload_ranks(first, layouts, ranks)
         self.layouts[first:first + len(layouts)] = list(layouts)
         self._lay_records[first:first + len(layouts)] = recs
         self._lay_desc[first:first + len(layouts)] = desc
@@ -649,6 +661,53 @@ class CookingVecEnv:
             return d_a.to_host(), d_s.to_host()
         finally:
             for b in (d_t, d_a, d_s):
+                b.free()
+
+    def _recipe_indices(self, recipes, n):
+        """recipe names or table indices, one per agent or [n, A] -> int32 [n, A] indices into the loaded recipe table"""
+        flat = [self.book_names.index(r) if isinstance(r, str) else int(r) for r in np.asarray(recipes, dtype=object).reshape(-1)]
+        idx = np.asarray(flat, dtype=np.int32)
+        if idx.size == self.num_agents:
+            idx = np.tile(idx, (n, 1))
+        return np.ascontiguousarray(idx.reshape(n, self.num_agents))
+
+    def partner_device(self, d_action=None, d_target=None, d_status=None, agents=None, d_recipe=None, env_begin=0, env_count=None):
+        """the scripted partner on the current state - the action the reference's heuristic `CookingAgent` returns
+        (cooking_zoo_amd/partner.py) - into device buffers, stream-ordered and capturable: `d_action` int32 [n, A] (walk codes 0..4:
+        the array `step_device` takes), `d_target` int32 [n, A, 2] (where the walk goes, (-1, -1) without one: a T = 1 target array
+        of `navigate_device`), `d_status` uint8 [n, A] (partner.DONE / WALK / IDLE / RAISES / ABSENT); at least one output.
+        `agents`: bit a = agent a is driven (None: all); the entries of the other agents are left untouched in every output.
+        `d_recipe` int32 [n, A]: indices into the recipe table (`book_names`); None: every env's own recipes."""
+        n = self.num_envs if env_count is None else int(env_count)
+        mask = (1 << self.num_agents) - 1 if agents is None else int(agents)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_partner_device(self._h, env_begin, n, mask, 0, p(d_recipe), p(d_action), p(d_target), p(d_status)))
+
+    def partner_bad_recipes(self):
+        """agents that `partner_device` was asked to drive with a recipe index outside the table (they got IDLE); waits"""
+        return int(_native.lib().cz_partner_bad_recipes(self._h))
+
+    def partner(self, agents=None, recipes=None, env_begin=0, env_count=None):
+        """host convenience: (actions int32 [n, A], targets int32 [n, A, 2], status uint8 [n, A]) of envs [env_begin, env_begin + n);
+        `recipes`: names or table indices, one per agent or [n, A] (None: the envs' own).  An agent that is not driven reads
+        0, (-1, -1), partner.IDLE."""
+        n = self.num_envs if env_count is None else int(env_count)
+        A = self.num_agents
+        if n == 0:
+            return np.zeros((0, A), np.int32), np.zeros((0, A, 2), np.int32), np.zeros((0, A), np.uint8)
+        bufs = [DeviceBuffer(self, (n, A), np.int32), DeviceBuffer(self, (n, A, 2), np.int32), DeviceBuffer(self, (n, A), np.uint8)]
+        try:
+            bufs[0].from_host(np.zeros((n, A), np.int32))
+            bufs[1].from_host(np.full((n, A, 2), -1, np.int32))
+            bufs[2].from_host(np.full((n, A), _partner.IDLE, np.uint8))
+            if recipes is not None:
+                bufs.append(DeviceBuffer(self, (n, A), np.int32))
+                bufs[3].from_host(self._recipe_indices(recipes, n))
+            self.partner_device(bufs[0], bufs[1], bufs[2], agents=agents, d_recipe=bufs[3] if recipes is not None else None,
+                                env_begin=env_begin, env_count=n)
+            return bufs[0].to_host(), bufs[1].to_host(), bufs[2].to_host()
+        finally:
+            for b in bufs:
                 b.free()
 
     # ------------------------------------------------------------------ device-resident API

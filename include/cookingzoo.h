@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -355,6 +355,51 @@ int32_t cz_grid_channels(int32_t extended);     /* 32 or 48; -1 for any other ar
 int32_t cz_nav_max_targets(void);  /* 8 */
 int cz_navigate_device(cz_handle h, int64_t env_begin, int64_t env_count, int32_t T, uint32_t flags,
                        const int32_t *d_target, int32_t *d_action, int32_t *d_steps, uint16_t *d_field);
+
+/* The SCRIPTED PARTNER: the action the reference's heuristic CookingAgent (cooking_agents/cooking_agent.py:9-119,
+ * base_agent.py:128-198) returns, for the chosen agents of every env, from the current records - which object to walk to (recipe
+ * marks of the asked recipe, the unmarked node with the highest index, the condition branch with generic_sequence, the contains
+ * branch) and the first move of that walk (cz_navigate_device's).  cooking_zoo_amd/partner.py is the definition and the host model.
+ *   agents   bit a set: agent a is driven; the entries of every other agent are left untouched in ALL outputs, so a learner's actions
+ *            and the partner's can share the one [N][A] array cz_step_device takes.  0, or a bit at or above A, is refused.
+ *   d_recipe int32 [env_count][A]     indices into the loaded recipe table; NULL: the env's own recipe of slot a (record word 5; 0xFF:
+ *                                     DONE).  An index outside the table gives that agent IDLE and adds one to cz_partner_bad_recipes.
+ *   d_action int32 [env_count][A]     0..4, the walk codes both action schemes share
+ *   d_target int32 [env_count][A][2]  the location handed to the walk whose result is the action, (-1, -1) when no walk produced
+ *                                     it: directly a T = 1 target array of cz_navigate_device
+ *   d_status uint8 [env_count][A]     CZ_PARTNER_DONE every node marked, or the recipe slot unused (action 0); _WALK the action is the
+ *                                     result of a walk to the target (0 at the goal or when it is unreachable); _IDLE the reference
+ *                                     returns 0 without a walk; _RAISES the reference raises here (action 0); _ABSENT the agent's
+ *                                     despawn bit is set (action 0; the reference's demo does not ask such an agent)
+ * Any output may be NULL (not all).  flags must be 0.  env_count == 0 returns 0.  Needs the partner table (cz_load_partner_table:
+ * the ordered conditions of every node, which the step kernels' accept masks lose) and the rank rows of the layout pool
+ * (cz_load_layout_ranks; cz_generate_layouts writes them itself): the list order of the static objects, which decides ties between
+ * equidistant Counters and appliances and which the records do not hold.  Deviations from the reference: those of
+ * cz_navigate_device; a condition on an attribute the object's class lacks counts as unmet (the reference raises AttributeError);
+ * a slot outside the grid or of no class is not an object, an agent outside the grid is IDLE (no valid record has either).
+ * Refused: all three outputs NULL, agents 0 or a bit >= A, flags != 0, a range outside the batch, no partner table, a pool slot
+ * without its rank row.  Stream-ordered on the handle's stream: no copy, no wait, no query, no allocation - legal inside a stream
+ * capture of the caller; the records are only read. */
+#define CZ_PARTNER_DONE 0
+#define CZ_PARTNER_WALK 1
+#define CZ_PARTNER_IDLE 2
+#define CZ_PARTNER_RAISES 3
+#define CZ_PARTNER_ABSENT 4
+int cz_partner_device(cz_handle h, int64_t env_begin, int64_t env_count, uint32_t agents, uint32_t flags,
+                      const int32_t *d_recipe, int32_t *d_action, int32_t *d_target, uint8_t *d_status);
+int64_t cz_partner_bad_recipes(cz_handle h);   /* agents asked for a recipe outside the table since cz_load_partner_table; waits */
+/* one row of cz_partner_row_words() (33) words per recipe of the table cz_load_recipes loaded, from the same graphs: the node count;
+ * then per node  class | number of conditions << 8 | child mask << 16  and the conditions in the node's own order, 4 bits each:
+ * attribute (0 chop_state, 1 blend_state) | wanted value << 1 (0 fresh, 1 chopped / in progress, 2 mashed); at most 8 per node */
+int32_t cz_partner_row_words(void);
+int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t n_recipes);   /* after every cz_load_recipes, which drops the table */
+/* rank rows of pool slots [first, first + count): uint16 [count][W*H], the position of every cell's static object in the reference's
+ * world_objects[class] list.  After cz_load_layouts / cz_update_layouts of those slots; the array is free again on return and the
+ * rows are in place before anything issued later on the handle's stream runs (the caller's thread does not wait); not inside a capture.
+ * The copy starts at once, on a stream of the library's own: it is NOT ordered behind cz_partner_device launches already issued, so -
+ * as for cz_update_layouts - only for slots that no env plays on or can draw (nothing checks this).  The wait is put on the stream
+ * the handle has at the time of the call: after a later cz_set_stream, cz_sync (or a wait of your own) before the next cz_partner_device. */
+int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, const uint16_t *ranks);
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
