@@ -1661,6 +1661,21 @@ extern "C" int64_t cz_partner_bad_recipes(cz_handle h) {
     if (!h || !h->d_partner) return h ? 0 : -1;
     return read_counter<unsigned long long>(h, partner_counter(h), "cz_partner_bad_recipes");
 }
+// Action effects and masks on the current state into DEVICE buffers (k_action_effects, cz_kernels.h; definition:
+// cooking_zoo_amd/effects.py): for every chosen agent of every env and every action code, what the action would change if the agent
+// played it alone.  Stream-ordered, nothing is copied, waited for, queried or allocated (legal inside a stream capture of the caller);
+// the records are only read; not a step: counts nothing.
+extern "C" int32_t cz_num_actions(cz_handle h) { return h ? (h->P.scheme == 3 ? 5 : 8) : -1; }   // actions.py:17,50
+extern "C" int cz_action_effects_device(cz_handle h, int64_t b, int64_t c, uint32_t agents, uint32_t ignore, uint8_t *d_mask, uint8_t *d_effects) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (agents == 0 || agents >> h->P.A) return fail(h, "cz_action_effects_device: agents is 0x%x, not a non-empty set of the %d agents", agents, h->P.A);
+    if (ignore & ~FX_ALL) return fail(h, "cz_action_effects_device: unknown ignore bits 0x%x", ignore & ~FX_ALL);
+    if (!d_mask && !d_effects) return fail(h, "cz_action_effects_device: both output pointers are null");
+    if (c == 0) return 0;
+    if (set_device(h)) return 1;
+    HIPCHK(h, h->kl.action_effects(h->P, h->stream, (int)c, EffectsArgs{b, agents, ignore, d_mask, d_effects}));
+    return 0;
+}
 // host mirror of the table the float32 rows are gathered from: what the kernels make of the float64 table while they stage it
 // (v_cvt_f32_f64, round to nearest even) is what this conversion makes of the host copy
 extern "C" int cz_obs_table_f32(cz_handle h, float *table) {

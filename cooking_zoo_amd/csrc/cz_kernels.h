@@ -1853,6 +1853,80 @@ __global__ __launch_bounds__(64) void k_partner(const Params P, const PartnerArg
     }
 }
 
+// Action effects and masks (cz_action_effects_device): which of an agent's actions would do anything at all;
+// cooking_zoo_amd/effects.py is the definition and the host model.  For an env whose done bit is clear, a present agent a and a code
+// c of the env's scheme (0 .. n_actions - 1; 5 codes in scheme3, 8 in scheme1): S0 is the record after world_step with every present
+// agent playing 0, Sc the record after world_step with agent a playing c and every other present agent playing 0 - world_step being
+// perform_agent_actions + progress_world + the linked interactions + the free-flag normalisation (cooking_world.py:104-108), without
+// handle_agent_spawn, t, recipe marks, rewards or flags; a despawned agent takes no part (action -1).  S0 is not S: a running Blender
+// progresses by itself.  effects[a][c] has one bit per difference between Sc and S0, in the words store_env would write:
+// MOVED agent a's (x, y), TURNED its orientation, HAND its held-slot field, OBJECTS any dyn0 / dyn1 word, CELLS any cell byte.
+// effects[a][0] = 0; mask[a][c] = 1 if c == 0 or (effects[a][c] & ~ignore) != 0.  A despawned agent and every agent of a finished
+// env get mask [1, 0, ...] and effects 0.  The mask speaks about one agent acting alone.
+// One wavefront per (env, agent) and workgroup, no wave talks to another; the records are only read.  A wave whose agent is not in
+// `agents` leaves at once and writes nothing; one whose agent is despawned or whose env is done leaves behind one load and writes the
+// noop-only row.  The others load the env once and run the trials c = 0 .. n_actions - 1 serially on copies of it, in one loop that
+// is not unrolled - the dynamics stand once in the kernel's code, the code c is a run-time value of lane a -, trial 0 being S0.
+// Every trial runs the free-flag normalisation (Dirty::interacted set): the step kernels skip it on steps without an interaction,
+// where it changes nothing on a record the step kernels made; here both sides of the comparison are normalised whatever the record.
+// Nothing of Dirty is taken for the answer: the bits are per-lane compares of the slots below D and the cells below W * H, reduced
+// by ballots, and three field compares of lane a's agent word.  Lane c keeps trial c's byte; lanes c < n_actions store one byte per
+// form that was asked for (plain stores): rows uint8 [count][A][n_actions], dense, every element of a written row exactly once.
+enum : uint32_t { FX_MOVED = 1, FX_TURNED = 2, FX_HAND = 4, FX_OBJECTS = 8, FX_CELLS = 16, FX_ALL = 31 };
+struct EffectsArgs {
+    int64_t env_begin;
+    uint32_t agents;                   // bit a: agent a is asked for
+    uint32_t ignore;                   // FX_ bits that do not make an action count
+    uint8_t *mask, *effects;           // [count][A][n_actions], either may be null
+};
+template <int OPL, int CPL, int NA, int SCHEME>
+__global__ __launch_bounds__(64) void k_action_effects(const Params P, const EffectsArgs G) {
+    constexpr uint32_t N_ACT = SCHEME == 3 ? 5u : 8u;
+    using O = Ops<OPL, CPL, NA, SCHEME>;
+    const uint32_t i = blockIdx.x / (uint32_t)NA, a = blockIdx.x % (uint32_t)NA, lane = threadIdx.x;
+    if (!((G.agents >> a) & 1u)) return;
+    const uint32_t *rec = P.state + (size_t)(G.env_begin + i) * P.RW;
+    const uint32_t st = rfl(rec[W_STATUS]);
+    uint32_t fx = 0u;                                                  // lane c: the byte of trial c
+    if (!(st & ST_DONE) && !((st >> ((uint32_t)SPAWN_GONE0 + a)) & 1u)) {
+        Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)lane};
+        Env<OPL, CPL, NA> e, s0;
+        load_env(P, e, cx, rec);
+        uint64_t slots[OPL], cells[CPL];                               // what a record holds: the lanes' slots below D, cells below W * H
+#pragma unroll
+        for (int k = 0; k < OPL; ++k) slots[k] = ballot(lane + 64u * k < (uint32_t)cx.D);
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) cells[k] = ballot(lane + 64u * k < (uint32_t)cx.C);
+        s0 = e;
+#pragma nounroll
+        for (uint32_t c = 0; c < N_ACT; ++c) {
+            Env<OPL, CPL, NA> t = e;
+            Dirty dt{};
+            dt.interacted = 1;
+            O::perform_agent_actions(t, cx, lane == a ? c : 0u, dt);
+            O::progress_and_link(t, cx, dt);
+            if (c == 0u) {
+                s0 = t;
+            } else {
+                uint64_t objs = 0ull, cellb = 0ull;
+#pragma unroll
+                for (int k = 0; k < OPL; ++k) objs |= (ballot(t.d0[k] != s0.d0[k]) | ballot(t.d1[k] != s0.d1[k])) & slots[k];
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) cellb |= ballot(((t.cell[k] ^ s0.cell[k]) & 0xFFu) != 0u) & cells[k];
+                const uint32_t x = rdl(t.agw ^ s0.agw, (int)a);
+                const uint32_t byte = ((x & 0xFFFFu) ? FX_MOVED : 0u) | ((x & 0xFF0000u) ? FX_TURNED : 0u) | ((x >> 24) ? FX_HAND : 0u) |
+                                      (objs ? FX_OBJECTS : 0u) | (cellb ? FX_CELLS : 0u);
+                fx = lane == c ? byte : fx;
+            }
+        }
+    }
+    if (lane < N_ACT) {
+        const size_t row = ((size_t)i * NA + a) * N_ACT;
+        if (G.effects) stg<uint8_t>(G.effects + row, lane, (uint8_t)fx);
+        if (G.mask) stg<uint8_t>(G.mask + row, lane, (uint8_t)((lane == 0u || (fx & ~G.ignore) != 0u) ? 1u : 0u));
+    }
+}
+
 // reset() of cooking_env.py:178-210 for CHOSEN envs of the whole batch, everything in device memory (cz_reset_device): env e is chosen
 // when mask[e] != 0 or, without a mask, when its status word has the done bit - what the auto-reset pass of step_env does to such an
 // env, without spending a step.  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load,
@@ -2022,6 +2096,8 @@ struct Launchers {
     hipError_t (*navigate)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t, const int32_t *, int32_t *, int32_t *, uint16_t *);
     // k_partner: count, then its argument block
     hipError_t (*partner)(const Params &, hipStream_t, int, const PartnerArgs &);
+    // k_action_effects: count envs (one workgroup per env and agent), then its argument block; by agent count and action scheme
+    hipError_t (*action_effects)(const Params &, hipStream_t, int, const EffectsArgs &);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -2120,9 +2196,18 @@ struct Inst {
         return CZ_LAUNCH_PER_ENV(k_navigate, n, b, T, flags, target, action, steps, field);
     }
     static hipError_t partner(const Params &P, hipStream_t st, int n, const PartnerArgs &G) { return CZ_LAUNCH_PER_ENV(k_partner, n, G); }
+    static hipError_t action_effects(const Params &P, hipStream_t st, int n, const EffectsArgs &G) {
+        return with_agents(P.A, [&](auto na) {
+            return with_scheme(P.scheme, [&](auto scheme) {
+                constexpr int NA = decltype(na)::value, S = decltype(scheme)::value;
+                hipLaunchKernelGGL((k_action_effects<OPL, CPL, NA, S>), dim3((unsigned)n * (unsigned)NA), dim3(64), 0, st, P, G);
+                return hipGetLastError();
+            });
+        });
+    }
 #undef CZ_LAUNCH_PER_ENV
     static Launchers launchers() {
-        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate, &partner};
+        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate, &partner, &action_effects};
     }
 };
 

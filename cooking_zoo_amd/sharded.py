@@ -31,7 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from cooking_zoo_amd import _native
+from cooking_zoo_amd import _native, effects as _effects
 from cooking_zoo_amd import distributed as czd
 from cooking_zoo_amd.vec_env import BatchTables, CookingVecEnv
 
@@ -350,6 +350,23 @@ class ShardedVecEnv:
         cut = (lambda i: list(np.asarray(recipes, dtype=object)[self._local_cuts[i]:self._local_cuts[i + 1]])) if per_env else (lambda i: recipes)
         parts = self._each(lambda i, env: env.partner(agents=agents, recipes=cut(i)))
         return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+
+    @property
+    def num_actions(self):
+        """action codes per agent: 5 (scheme3) or 8 (scheme1)"""
+        return _effects.num_actions(self.scheme_class.CODE)
+
+    def action_effects_device(self, d_mask=None, d_effects=None, agents=None, ignore=0):
+        """`CookingVecEnv.action_effects_device` on every shard over its part of the ShardedBuffers (per env: mask and effects
+        uint8 [A, num_actions])"""
+        P = self._part
+        self._each(lambda i, env: env.action_effects_device(P(d_mask, i), P(d_effects, i), agents=agents, ignore=ignore))
+
+    def action_mask(self, agents=None, ignore=0):
+        """`CookingVecEnv.action_mask` of every shard, concatenated in global env order: (mask [N, A, num_actions], effects
+        [N, A, num_actions])"""
+        parts = self._each(lambda i, env: env.action_mask(agents=agents, ignore=ignore))
+        return tuple(np.concatenate([p[k] for p in parts]) for k in range(2))
 
     def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
         """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids

@@ -12,7 +12,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, grid as _grid, nav as _nav, partner as _partner, rotation as _rotation, soa
+from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -709,6 +709,43 @@ class CookingVecEnv:
         finally:
             for b in bufs:
                 b.free()
+
+    @property
+    def num_actions(self):
+        """action codes per agent: 5 (scheme3) or 8 (scheme1)"""
+        return _effects.num_actions(self.scheme_class.CODE)
+
+    def action_effects_device(self, d_mask=None, d_effects=None, agents=None, ignore=0, env_begin=0, env_count=None):
+        """action masks of the current state - which of an agent's actions would change anything if it played them alone
+        (cooking_zoo_amd/effects.py) - into device buffers, stream-ordered and capturable: `d_mask` uint8 [n, A, num_actions]
+        (1: code 0, or the action has an effect outside `ignore`; `logits.masked_fill(~mask.bool(), -inf)`), `d_effects` uint8
+        [n, A, num_actions] (effects.MOVED | TURNED | HAND | OBJECTS | CELLS); at least one output.  `agents`: bit a = agent a is
+        asked for (None: all); the rows of the other agents are left untouched in both outputs.  `ignore`: effect bits that do not
+        make an action count (effects.TURNED: turning on the spot is a no-op).  A despawned agent and every agent of a finished env
+        get the noop-only row.  The records are only read; not a step."""
+        n = self.num_envs if env_count is None else int(env_count)
+        chosen = (1 << self.num_agents) - 1 if agents is None else int(agents)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_action_effects_device(self._h, env_begin, n, chosen, int(ignore), p(d_mask), p(d_effects)))
+
+    def action_mask(self, agents=None, ignore=0, env_begin=0, env_count=None):
+        """host convenience: (mask uint8 [n, A, num_actions], effects uint8 [n, A, num_actions]) of envs [env_begin, env_begin + n).
+        An agent that is not asked for reads the noop-only row and effects 0."""
+        n = self.num_envs if env_count is None else int(env_count)
+        shape = (n, self.num_agents, self.num_actions)
+        noop = np.zeros(shape, np.uint8)
+        noop[..., 0] = 1
+        if n == 0:
+            return noop, np.zeros(shape, np.uint8)
+        d_m, d_e = DeviceBuffer(self, shape, np.uint8), DeviceBuffer(self, shape, np.uint8)
+        try:
+            d_m.from_host(noop)
+            d_e.from_host(np.zeros(shape, np.uint8))
+            self.action_effects_device(d_m, d_e, agents=agents, ignore=ignore, env_begin=env_begin, env_count=n)
+            return d_m.to_host(), d_e.to_host()
+        finally:
+            d_m.free()
+            d_e.free()
 
     # ------------------------------------------------------------------ device-resident API
     def alloc(self, shape, dtype):

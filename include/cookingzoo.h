@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_action_effects_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -400,6 +400,52 @@ int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t n_recipes);
  * as for cz_update_layouts - only for slots that no env plays on or can draw (nothing checks this).  The wait is put on the stream
  * the handle has at the time of the call: after a later cz_set_stream, cz_sync (or a wait of your own) before the next cz_partner_device. */
 int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, const uint16_t *ranks);
+
+/* ACTION EFFECTS AND MASKS: which of an agent's actions would do anything at all, from the current records (the PettingZoo
+ * `action_mask` convention; the reference offers none).  cooking_zoo_amd/effects.py is the definition and the host model.
+ * For an env whose done bit is clear, an agent a that is present, and an action code c of the env's scheme:
+ *   - Codes are 0 .. n_actions - 1.  n_actions is 5 for scheme3 and 8 for scheme1 (cz_num_actions; action_scheme3.py:4-43,
+ *     action_scheme1.py:4-40).
+ *   - S0 is the record after world_step with every present agent playing 0.
+ *   - Sc is the record after world_step with agent a playing c and every other present agent playing 0.
+ *   - world_step means perform_agent_actions + progress_world + the linked interactions + the free-flag normalisation
+ *     (cooking_world.py:104-108).
+ *   - world_step here does NOT include handle_agent_spawn (cooking_world.py:109-112), t, recipe marks, rewards or flags.
+ *   - A despawned agent takes no part, as in the step kernels (action -1).
+ *   - S0 is not S: a running Blender progresses by itself.
+ * effects[a][c] is a byte of five bits.  Each bit is a difference between Sc and S0, in the words a step would write:
+ *   bit 0 CZ_EFFECT_MOVED    agent a's (x, y) differs
+ *   bit 1 CZ_EFFECT_TURNED   agent a's orientation differs
+ *   bit 2 CZ_EFFECT_HAND     agent a's held-slot field differs (picked up, put down, swapped)
+ *   bit 3 CZ_EFFECT_OBJECTS  any dyn0 / dyn1 word differs (an object moved, changed state, was created, deleted, plated, delivered)
+ *   bit 4 CZ_EFFECT_CELLS    any cell byte differs (appliance READY / TOGGLE, Switch, Block)
+ * Other agents' words cannot differ while they play 0, so there is no bit for them.
+ *   - effects[a][0] = 0.
+ *   - mask[a][c] = 1 if c == 0 or (effects[a][c] & ~ignore) != 0, else 0.
+ *   - ignore is a caller's bit set.  For example, CZ_EFFECT_TURNED makes "only turns on the spot" count as a no-op.
+ * Special cases: a despawned agent gets mask = [1, 0, ...] and effects 0.  A finished env (done bit set) gets the same for every
+ * agent: the next step resets or freezes it whatever is played.  Where the reference raises and the build has a defined no-op, the
+ * effect is 0 like any no-op: EXECUTE on a READY Cutboard with empty content, and a scheme1 interaction aimed off-grid (DESIGN.md
+ * section 2).
+ * The one caveat: the mask speaks about one agent acting alone.  With several agents acting at once, the collision filter and the
+ * serial interaction order can change what happens; that is what every per-agent action mask means.
+ *   agents    bit a set: agent a is asked for; the rows of every other agent are left untouched in both outputs.  0, or a bit at
+ *             or above A, is refused.
+ *   ignore    CZ_EFFECT_ bits; a bit outside the five is refused.
+ *   d_mask    uint8 [env_count][A][n_actions]   0 / 1
+ *   d_effects uint8 [env_count][A][n_actions]   the bytes
+ * Either output may be NULL; both NULL is refused, and so is a range outside [0, N].  env_count == 0 returns 0.  Rows are dense:
+ * every element of a written row is written exactly once, nothing behind the last row.  One launch on the handle's stream: no copy,
+ * no wait, no query, no allocation - legal inside a stream capture of the caller; the records are only read, and the launch is not
+ * a step: no counter or statistic moves. */
+#define CZ_EFFECT_MOVED 1
+#define CZ_EFFECT_TURNED 2
+#define CZ_EFFECT_HAND 4
+#define CZ_EFFECT_OBJECTS 8
+#define CZ_EFFECT_CELLS 16
+int32_t cz_num_actions(cz_handle h);          /* 5 (scheme3) or 8 (scheme1); -1 for a null handle */
+int cz_action_effects_device(cz_handle h, int64_t env_begin, int64_t env_count, uint32_t agents, uint32_t ignore,
+                             uint8_t *d_mask, uint8_t *d_effects);
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
