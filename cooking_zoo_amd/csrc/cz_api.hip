@@ -309,6 +309,8 @@ struct cz_handle_s {
     cz_stats *d_stats_out = nullptr;
     unsigned long long *d_stats_part = nullptr;   // [256 chains][16 columns] between the two stages of the reduction
     double *d_lut = nullptr;
+    void *d_sprites = nullptr;         // cz_load_sprites: float table [256] | sheet [RENDER_SPRITES][M][M] RGBA
+    int32_t sprites_M = 0;             // 0: no sheet loaded
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
     unsigned long long *d_reset_refused = nullptr;   // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
@@ -628,7 +630,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1551,6 +1553,62 @@ extern "C" int cz_observe_grid_device(cz_handle h, int64_t b, int64_t c, int32_t
         return fail(h, "cz_observe_grid_device: d_grid8 and d_grid32 must be 16-byte aligned, d_bits 8-byte, d_agent_xy 4-byte");
     if (set_device(h)) return 1;
     HIPCHK(h, h->kl.observe_grid(h->P, h->stream, b, (int)c, extended, d_bits, d_grid8, d_grid32, d_agent_xy));
+    return 0;
+}
+// Frames of the current state into DEVICE buffers (k_render, cz_kernels.h; definition: cooking_zoo_amd/render.py).  cz_load_sprites
+// takes the sheet uint8 [cz_render_sprites()][M][M][4] RGBA from HOST memory, uploads it with the table v * (1 / 255) and replaces an earlier
+// sheet; it allocates, copies and waits for the stream (not capturable).  cz_render_device is one launch on the env's stream: nothing
+// is copied, waited for, queried or allocated (legal inside a stream capture of the caller); the records are only read.
+extern "C" int32_t cz_render_sprites(void) { return RENDER_SPRITES; }
+extern "C" int cz_load_sprites(cz_handle h, const uint8_t *rgba, int32_t n_sprites, int32_t M) {
+    if (ready(h)) return 1;
+    if (!rgba) return fail(h, "cz_load_sprites: the sheet pointer is null");
+    if (n_sprites != RENDER_SPRITES) return fail(h, "cz_load_sprites: %d sprites, the sheet has %d (cz_render_sprites)", n_sprites, RENDER_SPRITES);
+    if (M < 1 || M > RENDER_M_MAX) return fail(h, "cz_load_sprites: M = %d is outside [1, %d]", M, RENDER_M_MAX);
+    if (set_device(h)) return 1;
+    HIPCHK(h, hipStreamSynchronize(h->stream));                        // (a launch in flight may still read the old sheet)
+    if (h->d_sprites) { HIPCHK(h, hipFree(h->d_sprites)); h->d_sprites = nullptr; h->sprites_M = 0; }
+    const size_t bytes = (size_t)RENDER_SPRITES * M * M * 4;
+    float ftab[256];
+    const volatile float inv = 1.0f / 255.0f;                          // render.py: v * (1 / 255) in float32, torch's `x / 255` on the device
+    for (int v = 0; v < 256; ++v) ftab[v] = (float)v * inv;
+    HIPCHK(h, hipMalloc(&h->d_sprites, sizeof ftab + bytes));
+    HIPCHK(h, hipMemcpy(h->d_sprites, ftab, sizeof ftab, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_sprites + sizeof ftab, rgba, bytes, hipMemcpyHostToDevice));
+    h->sprites_M = M;
+    return 0;
+}
+extern "C" int cz_render_device(cz_handle h, int64_t b, int64_t c, int32_t P, uint32_t vis, uint8_t *d_rgb8, float *d_chw32) {
+    if (ready(h) || check_range(h, b, c)) return 1;
+    if (P < RENDER_P_MIN || P > RENDER_P_MAX) return fail(h, "cz_render_device: P = %d is outside [%d, %d]", P, RENDER_P_MIN, RENDER_P_MAX);
+    if (!h->sprites_M) return fail(h, "cz_render_device: no sprite sheet is loaded (cz_load_sprites)");
+    if (c == 0) return 0;
+    if (!d_rgb8 && !d_chw32) return fail(h, "cz_render_device: both output pointers are null");
+    if ((uintptr_t)d_rgb8 & 3u || (uintptr_t)d_chw32 & 15u) return fail(h, "cz_render_device: d_rgb8 must be 4-byte aligned, d_chw32 16-byte");
+    if (set_device(h)) return 1;
+    RenderArgs G{};
+    G.env_begin = b;
+    G.ftab = (const float *)h->d_sprites;
+    G.sheet = (const uint32_t *)((const char *)h->d_sprites + 256 * sizeof(float));
+    G.rgb8 = d_rgb8; G.chw32 = d_chw32;
+    G.P = (uint32_t)P; G.M = (uint32_t)h->sprites_M; G.vis = vis;
+    // the reference's own float expressions in its own order (graphic_pipeline.py:46-55, 197-220; render.geometry), every product
+    // rounded to double before the next (volatile: nothing is folded or fused)
+    const volatile double tile = (double)P, hs = 0.5, cs = 0.7;
+    volatile double v;
+    v = tile * hs; G.holding = (uint32_t)(int)v;
+    v = tile * cs; G.container = (uint32_t)(int)v;
+    v = tile * cs; v = v * hs; G.holding_container = (uint32_t)(int)v;
+    G.arrow = (uint32_t)P / 4u;
+    volatile double one_h = 1.0 - hs, one_c = 1.0 - cs;
+    v = tile * one_h; G.holding_off = (uint32_t)(int)v;
+    v = tile * one_c; v = v / 2.0; G.container_off = (uint32_t)(int)v;
+    volatile double f = one_c / 2.0; f = f * hs; f = one_h + f;
+    v = tile * f; G.holding_container_off = (uint32_t)(int)v;
+    const uint32_t WP = (uint32_t)h->P.W * (uint32_t)P, per_row = (WP & 3u) ? WP : WP >> 2;
+    G.mul_p = (1u << 20) / (uint32_t)P + 1u;
+    G.mul_row = (1u << RENDER_ROW_SHIFT) / per_row + 1u;
+    HIPCHK(h, h->kl.render(h->P, h->stream, (int)c, G));
     return 0;
 }
 // Shortest-path navigation on the current state into DEVICE buffers (k_navigate, cz_kernels.h; definition: cooking_zoo_amd/nav.py):

@@ -1288,6 +1288,222 @@ __global__ __launch_bounds__(64) void k_observe_grid(const Params P, int64_t env
     }
 }
 
+// Frames (cz_render_device): the reference's GraphicPipeline.render (environment/game/graphic_pipeline.py) as a display list per
+// cell composited per pixel; cooking_zoo_amd/render.py is the definition (display list, sampling, blend, deviations) and the host
+// model.  A pure function of the record plus the sprite sheet; records are only read.  One workgroup of four wavefronts per
+// (env, row of cells, band of RENDER_BAND pixel rows):
+//   A. the first wave runs load_env and puts the slot words, the row's cell bytes, the agent words and the status word into LDS;
+//      thread x < W owns cell (x, row): it counts the cell's draws (static 2, agents 2 each, the alive slots of the cell in slot
+//      order), the W counts are summed into list starts, and the thread writes its cell's commands - sprite | x0 << 8 | y0 << 16
+//      | size << 24 relative to the tile, and the multiplier that replaces the division by the size - at its start.  The list
+//      holds every command of every record: a row has at most 2 W static, 2 NA agent and D slot commands (RENDER_CMDS), so
+//      nothing is clipped whatever the record holds;
+//   B. all threads share the band's (up to RENDER_BAND) x (W P) pixels.  A pixel finds its cell (a multiply and a shift: the API passes the
+//      multipliers), starts from Color.FLOOR and walks the cell's commands in order, since every draw stays inside its tile.
+//      Where the row pitch W * P * 3 is a multiple of 4 a thread owns 4 neighbouring pixels: three dword stores of rgb8, one
+//      16-byte store per plane of chw32; otherwise one pixel: three byte stores, three float stores.  Every output byte is
+//      written exactly once, nothing behind the last frame; plain stores.  chw32 goes through the 256-entry table v * (1 / 255).
+constexpr int RENDER_BAND = 16;       // pixel rows per workgroup: a tile above 16 pixels is drawn by several workgroups (each repeats A)
+constexpr int RENDER_THREADS = 256, RENDER_SPRITES = 40, RENDER_RECT = 255, RENDER_MAX_W = 32, RENDER_ROW_SHIFT = 31;
+constexpr int RENDER_P_MIN = 4, RENDER_P_MAX = 128, RENDER_M_MAX = 128, RENDER_DIV_SHIFT = 21;
+constexpr uint32_t RENDER_FLOOR_RGB = 245u | 230u << 8 | 210u << 16, RENDER_DELIVERY_RGB = 96u | 96u << 8 | 96u << 16;
+// sprite numbers (cooking_zoo_amd/render.py SPRITES), 5 bits per dynamic class: fresh, chopped (mashed is the chopped one, for a
+// Carrot the one behind it); 4 bits per cell type: plain, and with TOGGLE, ACTIVE or WALK set
+constexpr uint64_t RENDER_DYN_FRESH = 9ull | 10ull << 5 | 12ull << 10 | 14ull << 15 | 16ull << 20 | 19ull << 25 | 20ull << 30 | 22ull << 35 | 24ull << 40 | 26ull << 45;
+constexpr uint64_t RENDER_DYN_CHOPPED = 9ull | 11ull << 5 | 13ull << 10 | 15ull << 15 | 17ull << 20 | 19ull << 25 | 21ull << 30 | 23ull << 35 | 25ull << 40 | 27ull << 45;
+constexpr uint32_t RENDER_CELL_PLAIN = 0u | 1u << 4 | 2u << 8 | 4u << 12 | 5u << 16 | 6u << 20 | 8u << 24, RENDER_CELL_SET = 0u | 1u << 4 | 2u << 8 | 3u << 12 | 0u << 16 | 6u << 20 | 7u << 24;
+constexpr uint32_t RENDER_SPR_COUNTER = 1u, RENDER_SPR_HUMAN0 = 28u, RENDER_SPR_ROBOT0 = 32u, RENDER_SPR_ARROW0 = 36u;
+struct RenderArgs {
+    int64_t env_begin;
+    const uint32_t *sheet;          // [RENDER_SPRITES][M][M] RGBA, one word per texel (r in the low byte)
+    const float *ftab;              // [256]: v * (1 / 255)
+    uint8_t *rgb8;                  // [count][H P][W P][3] or null
+    float *chw32;                   // [count][3][H P][W P] or null
+    uint32_t P, M, vis;
+    uint32_t holding, container, holding_container, arrow, holding_off, container_off, holding_container_off;   // render.geometry(P)
+    uint32_t mul_p;                 // floor(2^20 / P) + 1: px / P = px * mul_p >> 20 for px < 4096
+    uint32_t mul_row;               // floor(2^31 / units per pixel row) + 1: u / units = u * mul_row >> 31 (64-bit product), u < 2^19
+};
+// floor(n / s) = n * render_mul(s) >> RENDER_DIV_SHIFT for n < s * RENDER_M_MAX, 1 <= s <= 128
+__host__ __device__ inline uint32_t render_mul(uint32_t s) { return s ? (1u << RENDER_DIV_SHIFT) / s + 1u : 0u; }
+__device__ __forceinline__ uint32_t render_tiles(uint32_t n) {        // floor(sqrt(n - 1)) + 1: the smallest t with t * t >= n
+    uint32_t t = 1u;
+    while (t * t < n) ++t;
+    return t;
+}
+// one channel: round-half-up of (src a + dst (255 - a)) / 255
+__device__ __forceinline__ uint32_t render_blend(uint32_t dst, uint32_t src, uint32_t a) {
+    const uint32_t t = src * a + dst * (255u - a) + 128u;
+    return (t + (t >> 8)) >> 8;
+}
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(RENDER_THREADS) void k_render(const Params P, const RenderArgs G) {
+    constexpr int SLOTS = 64 * OPL, MAX_W = RENDER_MAX_W, RENDER_CMDS = 2 * MAX_W + 2 * NA + SLOTS;
+    static_assert(MAX_W <= 64, "one thread of the first wave per cell of a row");
+    __shared__ uint32_t d0s[SLOTS], rowcell[MAX_W], ag[MAX_AGENTS], status_s, cnt[MAX_W], start[MAX_W];
+    __shared__ uint32_t cmd[RENDER_CMDS], cmdmul[RENDER_CMDS];
+    __shared__ float ftab[256];
+    const uint32_t tid = threadIdx.x, W = (uint32_t)P.W, H = (uint32_t)P.H, D = (uint32_t)P.D;
+    const uint32_t i = blockIdx.x / H, row = blockIdx.x - i * H;      // (uniform: one scalar division per workgroup)
+    const uint32_t TP = G.P, M = G.M;
+    ftab[tid] = G.ftab[tid];
+    if (tid < 64u) {
+        Ctx cx{P.W, P.H, P.D, P.W * P.H, (int)tid};
+        Env<OPL, CPL, NA> e;
+        load_env(P, e, cx, P.state + (size_t)(G.env_begin + i) * P.RW);
+#pragma unroll
+        for (int k = 0; k < OPL; ++k) d0s[tid + 64u * k] = e.d0[k];
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const uint32_t c = tid + 64u * k - row * W;               // (wraps for the cells in front of the row)
+            if (c < W) rowcell[c] = e.cell[k];
+        }
+        if (tid < (uint32_t)NA) ag[tid] = e.agw;
+        if (tid == 0u) status_s = e.status;
+    }
+    __syncthreads();
+    // ---- A: the cell's draws, counted and then written
+    uint32_t n_dyn = 0u, n_plate = 0u, plate_at = 0u, n_total = 0u;
+    bool agent_here = false;
+    const uint32_t here = tid | row << 8;                             // x | y << 8 of this thread's cell
+    if (tid < W) {
+        const uint32_t ty = rowcell[tid] & CELL_TYPE;
+        n_total = ty < 7u ? 2u : 0u;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const uint32_t w = ag[a], orient = (w >> 16) & 0xFFu;
+            if ((w & 0xFFFFu) == here) {
+                agent_here = true;
+                if (!((status_s >> (SPAWN_GONE0 + a)) & 1u)) n_total += 1u + (uint32_t)(orient - 1u < 4u);
+            }
+        }
+        for (uint32_t s = 0u; s < D; ++s) {
+            const uint32_t d0 = d0s[s], cls = (d0 >> 16) & 0xFFu;
+            if ((d0 & D_ALIVE) && cls < 10u && (d0 & 0xFFFFu) == here) {
+                if (cls == PLATE && n_plate++ == 0u) plate_at = n_dyn;
+                ++n_dyn;
+            }
+        }
+        n_total += n_dyn;
+        cnt[tid] = n_total;
+    }
+    __syncthreads();
+    if (tid < W) {
+        uint32_t at = 0u;
+        for (uint32_t x = 0u; x < tid; ++x) at += cnt[x];
+        start[tid] = at;
+        const uint32_t cv = rowcell[tid], ty = cv & CELL_TYPE;
+        const uint32_t mul_tile = render_mul(TP);
+        if (ty < 7u) {
+            cmd[at] = (ty == DELIVERSQUARE ? (uint32_t)RENDER_RECT : RENDER_SPR_COUNTER) | TP << 24;
+            cmdmul[at++] = mul_tile;
+            cmd[at] = ((((cv & (CELL_TOGGLE | CELL_ACTIVE | CELL_WALK)) ? RENDER_CELL_SET : RENDER_CELL_PLAIN) >> (4u * ty)) & 0xFu) | TP << 24;
+            cmdmul[at++] = mul_tile;
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const uint32_t w = ag[a], orient = (w >> 16) & 0xFFu;
+            if ((w & 0xFFFFu) == here && !((status_s >> (SPAWN_GONE0 + a)) & 1u)) {
+                cmd[at] = ((((G.vis >> a) & 1u) ? RENDER_SPR_ROBOT0 : RENDER_SPR_HUMAN0) + (uint32_t)a) | TP << 24;
+                cmdmul[at++] = mul_tile;
+                if (orient - 1u < 4u) {                               // draw_agents: left, right, down, up
+                    const uint32_t q = G.arrow, far = 3u * TP / 4u;
+                    const uint32_t ax = orient == 1u ? 0u : orient == 2u ? far : q, ay = orient == 3u ? far : orient == 4u ? 0u : q;
+                    cmd[at] = (RENDER_SPR_ARROW0 + orient - 1u) | ax << 8 | ay << 16 | q << 24;
+                    cmdmul[at++] = render_mul(q);
+                }
+            }
+        }
+        if (n_dyn) {
+            const uint32_t base = agent_here ? G.holding : TP, boff = agent_here ? G.holding_off : 0u;
+            const uint32_t inner = agent_here ? G.holding_container : G.container, ioff = agent_here ? G.holding_container_off : G.container_off;
+            const bool plated = n_plate == 1u;
+            const uint32_t n_stack = plated ? n_dyn - 1u : n_dyn, sbase = plated ? inner : base, soff = plated ? ioff : boff;
+            const uint32_t tiles = render_tiles(n_stack ? n_stack : 1u), size = sbase / tiles, mul_stack = render_mul(size), mul_base = render_mul(base);
+            uint32_t k = 0u, idx = 0u, col = 0u, rowi = 0u;           // k: place in the group; idx = rowi * tiles + col: place in the stack
+            for (uint32_t s = 0u; s < D; ++s) {
+                const uint32_t d0 = d0s[s], cls = (d0 >> 16) & 0xFFu;
+                if ((d0 & D_ALIVE) && cls < 10u && (d0 & 0xFFFFu) == here) {
+                    const uint32_t spr = (d0 & D_CHOPPED) ? (uint32_t)(RENDER_DYN_CHOPPED >> (5u * cls)) & 31u
+                                         : (d0 & D_MASHED) ? ((uint32_t)(RENDER_DYN_CHOPPED >> (5u * cls)) & 31u) + (uint32_t)(cls == CARROT)
+                                                           : (uint32_t)(RENDER_DYN_FRESH >> (5u * cls)) & 31u;
+                    if (plated && k == plate_at) {
+                        cmd[at] = spr | boff << 8 | boff << 16 | base << 24;
+                        cmdmul[at++] = mul_base;
+                    } else {
+                        cmd[at] = spr | (soff + size * col) << 8 | (soff + size * rowi) << 16 | size << 24;
+                        cmdmul[at++] = mul_stack;
+                        ++idx;
+                        if (++col == tiles) { col = 0u; ++rowi; }
+                    }
+                    ++k;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // ---- B: the pixels of the row
+    const uint32_t WP = W * TP, HP = H * TP;
+    const bool wide = (WP & 3u) == 0u;
+    const uint32_t per_row = wide ? WP >> 2 : WP, units = per_row * TP, NPIX = wide ? 4u : 1u;
+    uint8_t *rgb = G.rgb8 ? G.rgb8 + ((size_t)i * HP + (size_t)row * TP) * WP * 3u : nullptr;
+    float *pl = G.chw32 ? G.chw32 + (size_t)i * 3u * HP * WP + (size_t)row * TP * WP : nullptr;
+    const size_t plane = (size_t)HP * WP;
+    // blockIdx.y: which RENDER_BAND pixel rows of the row of cells this workgroup draws
+    const uint32_t u_end = min(units, (blockIdx.y + 1u) * (uint32_t)RENDER_BAND * per_row);
+    for (uint32_t u = blockIdx.y * (uint32_t)RENDER_BAND * per_row + tid; u < u_end; u += (uint32_t)RENDER_THREADS) {
+        const uint32_t py = (uint32_t)(((uint64_t)u * G.mul_row) >> RENDER_ROW_SHIFT), px0 = (u - py * per_row) * NPIX;
+        uint32_t r[4], g[4], b[4];
+#pragma unroll
+        for (uint32_t j = 0u; j < 4u; ++j) {
+            if (j >= NPIX) break;
+            const uint32_t px = px0 + j, cxl = (px * G.mul_p) >> 20, lx = px - cxl * TP;
+            uint32_t cr = RENDER_FLOOR_RGB & 0xFFu, cg = (RENDER_FLOOR_RGB >> 8) & 0xFFu, cb = RENDER_FLOOR_RGB >> 16;
+            const uint32_t c0 = start[cxl], c1 = c0 + cnt[cxl];
+            for (uint32_t c = c0; c < c1; ++c) {
+                const uint32_t w = cmd[c], size = w >> 24, dx = lx - ((w >> 8) & 0xFFu), dy = py - ((w >> 16) & 0xFFu);
+                if (dx < size && dy < size) {                         // (unsigned: also false in front of the draw)
+                    if ((w & 0xFFu) == (uint32_t)RENDER_RECT) {
+                        cr = RENDER_DELIVERY_RGB & 0xFFu; cg = (RENDER_DELIVERY_RGB >> 8) & 0xFFu; cb = RENDER_DELIVERY_RGB >> 16;
+                    } else {
+                        const uint32_t m = cmdmul[c], sx = (dx * M * m) >> RENDER_DIV_SHIFT, sy = (dy * M * m) >> RENDER_DIV_SHIFT;
+                        const uint32_t t = G.sheet[((w & 0xFFu) * M + sy) * M + sx], a = t >> 24;
+                        cr = render_blend(cr, t & 0xFFu, a);
+                        cg = render_blend(cg, (t >> 8) & 0xFFu, a);
+                        cb = render_blend(cb, (t >> 16) & 0xFFu, a);
+                    }
+                }
+            }
+            r[j] = cr; g[j] = cg; b[j] = cb;
+        }
+        const uint32_t o = py * WP + px0;                             // pixel index inside the row of cells
+        if (wide) {
+            if (rgb) {
+                stg<uint32_t>(rgb, o * 3u, r[0] | g[0] << 8 | b[0] << 16 | r[1] << 24);
+                stg<uint32_t>(rgb, o * 3u + 4u, g[1] | b[1] << 8 | r[2] << 16 | g[2] << 24);
+                stg<uint32_t>(rgb, o * 3u + 8u, b[2] | r[3] << 8 | g[3] << 16 | b[3] << 24);
+            }
+            if (pl) {
+                typedef float float4_t __attribute__((ext_vector_type(4)));
+                stg<float4_t>(pl, o * 4u, float4_t{ftab[r[0]], ftab[r[1]], ftab[r[2]], ftab[r[3]]});
+                stg<float4_t>(pl + plane, o * 4u, float4_t{ftab[g[0]], ftab[g[1]], ftab[g[2]], ftab[g[3]]});
+                stg<float4_t>(pl + 2u * plane, o * 4u, float4_t{ftab[b[0]], ftab[b[1]], ftab[b[2]], ftab[b[3]]});
+            }
+        } else {
+            if (rgb) {
+                stg<uint8_t>(rgb, o * 3u, (uint8_t)r[0]);
+                stg<uint8_t>(rgb, o * 3u + 1u, (uint8_t)g[0]);
+                stg<uint8_t>(rgb, o * 3u + 2u, (uint8_t)b[0]);
+            }
+            if (pl) {
+                stg<float>(pl, o * 4u, ftab[r[0]]);
+                stg<float>(pl + plane, o * 4u, ftab[g[0]]);
+                stg<float>(pl + 2u * plane, o * 4u, ftab[b[0]]);
+            }
+        }
+    }
+}
+
 // Shortest-path navigation (cz_navigate_device): BaseAgent.walk_to_location and reachable of the reference's scripted partner
 // (cooking_agents/base_agent.py:62-126) for every agent of every env and up to NAV_MAX_TARGETS candidate goals each;
 // cooking_zoo_amd/nav.py is the definition and the host model.  The reference searches breadth first from the agent over the Floor
@@ -2098,6 +2314,8 @@ struct Launchers {
     hipError_t (*partner)(const Params &, hipStream_t, int, const PartnerArgs &);
     // k_action_effects: count envs (one workgroup per env and agent), then its argument block; by agent count and action scheme
     hipError_t (*action_effects)(const Params &, hipStream_t, int, const EffectsArgs &);
+    // k_render: count envs (one workgroup per env and row of cells), then its argument block
+    hipError_t (*render)(const Params &, hipStream_t, int, const RenderArgs &);
 };
 
 // the run-time agent count (1..4; anything else: 4) and action scheme (3; anything else: 1) as template arguments of f's call
@@ -2205,9 +2423,17 @@ struct Inst {
             });
         });
     }
+    static hipError_t render(const Params &P, hipStream_t st, int n, const RenderArgs &G) {
+        return with_agents(P.A, [&](auto na) {
+            hipLaunchKernelGGL((k_render<OPL, CPL, decltype(na)::value>), dim3((unsigned)n * (unsigned)P.H, (G.P + RENDER_BAND - 1u) / RENDER_BAND), dim3(RENDER_THREADS), 0, st,
+                               P, G);
+            return hipGetLastError();
+        });
+    }
 #undef CZ_LAUNCH_PER_ENV
     static Launchers launchers() {
-        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate, &partner, &action_effects};
+        return Launchers{&step, &reset, &observe, HAS_LEAN, &observe_f32, &reset_where, &restore_where, &observe_grid, &navigate, &partner, &action_effects,
+                         &render};
     }
 };
 

@@ -325,8 +325,22 @@ class CookingEnvironment:
     def world(self):
         return WorldView(self._vec.dims, self._vec.get_state()[0])
 
+    RENDER_TILE = 80                                                              # graphic_pipeline.py:34 PIXEL_PER_TILE
+
     def render(self, **kwargs):
-        raise NotImplementedError("rendering (pygame GraphicPipeline) is outside the accelerated step path")
+        """the frame of the one env as uint8 (H * 80, W * 80, 3) - the "rgb_array" of `metadata` - drawn on the device
+        (cooking_zoo_amd/render.py; builtin sprites unless `self._vec.load_sprites` was given a sheet); agent a is a robot where
+        the constructor's `agent_visualization[a]` says so"""
+        vis = sum(1 << a for a, kind in enumerate(self.agent_visualization[:len(self.possible_agents)]) if kind == "robot")
+        return self._vec.render(0, 1, P=self.RENDER_TILE, vis=vis)[0]
+
+    def screenshot(self, path="screenshot.png"):
+        """the frame saved as an image file (needs PIL)"""
+        try:
+            from PIL import Image
+        except ImportError as exc:
+            raise RuntimeError("screenshot() needs PIL (pillow) to write image files; render() returns the array") from exc
+        Image.fromarray(self.render()).save(path)
 
     def close(self):
         self._vec.close()

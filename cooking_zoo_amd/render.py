@@ -1,0 +1,255 @@
+"""Frames: the reference's `GraphicPipeline.render` (environment/game/graphic_pipeline.py), defined on records.
+
+The reference renders with pygame: a fill, then per object `transform.scale(image, size)` and `blit(image, location)`.  Every
+class has a `file_name()`, every draw stays inside its own tile, and no supported class returns text or icons, so a frame is a
+DISPLAY LIST per cell - (sprite, x0, y0, size) in draw order - composited per pixel.  This module is that definition for the
+batched env, on the host, from records alone (numpy only; it never loads the device library); `k_render` (csrc/cz_kernels.h,
+`CookingVecEnv.render_device`) computes the same bytes on the device.
+
+The display list is reference semantics (tests/golden/render_ref.json.gz holds the ops of the unmodified reference's own
+pipeline under a recording stand-in for pygame).  Per cell, in order:
+  static   `Counter`, then the object's own sprite; a Deliversquare gets a rect of Color.DELIVERY, then its sprite
+  agents   the agent sprite `{human,robot}-{colour}`, then the orientation arrow of size P // 4 (draw_agents' four positions)
+  dynamic  the alive slots of the cell in slot order (the reference's get_object_list order).  Where any agent of the record
+           stands on the cell the base is (holding size, holding location) and the inner one (holding-container size and
+           location), otherwise (tile, tile origin) and (container size, container location).  Exactly one Plate in the group:
+           the Plate at the base, the rest as a food stack at the inner size and location; otherwise the whole group as a food
+           stack at the base.  Food stack of n: tiles = floor(sqrt(n - 1)) + 1, size = base // tiles, item idx at
+           base_loc + size * (idx % tiles, idx // tiles).  A draw of size 0 draws nothing.
+
+The compositing is the project's own definition.  A sprite sheet is uint8 [S][M][M][4] RGBA (`builtin_sprites`, or
+`load_directory` on a user's own asset folder); a draw of size s at (x0, y0) covers x0 <= px < x0 + s, y0 <= py < y0 + s and
+samples the sprite at ((px - x0) * M // s, (py - y0) * M // s); per channel t = src * a + dst * (255 - a) + 128,
+dst = (t + (t >> 8)) >> 8, which is round-half-up of the exact quotient by 255.  The canvas starts opaque at Color.FLOOR.
+Frames are uint8 [n][H * P][W * P][3] (gymnasium's (height, width, 3)); `to_chw32` gives float32 [n][3][H * P][W * P] through a
+256-entry table.  The table is np.float32(v) * (np.float32(1) / np.float32(255)): what torch computes for `frame.float() / 255` on
+the device (a tensor divided by a Python scalar is multiplied by the scalar's float32 reciprocal there), so the planes equal a
+torch user's own conversion bit for bit.  126 of its 256 entries are one ulp away from the correctly rounded quotient
+np.float32(v) / np.float32(255), which is what numpy and torch on the CPU compute.
+
+Deviations from the reference:
+ 1. Cucumber is drawn as `default_dynamic` without text (the reference's `font.render()` without arguments raises there).
+ 2. An agent whose despawn bit is set is not drawn (what it holds still is, at holding size), and agent a always uses `vis` bit
+    a and colour a.  The reference draws `relevant_agents`, which keeps a just-despawned agent one step longer, and indexes
+    `agent_visualization` by the position in that list.
+ 3. The sprite is resampled from the M x M master, not from the original file.
+ 4. The blend rule is the project's; equality with pygame's blitter is unverified (pygame is not available to the build).
+ 5. Slots or agents whose coordinates lie outside the grid (no valid record has one) are not drawn.
+"""
+from __future__ import annotations
+
+import math
+import os
+
+import numpy as np
+
+from cooking_zoo_amd import soa
+
+COLOR_FLOOR = (245, 230, 210)          # game/utils.py Color.FLOOR
+COLOR_DELIVERY = (96, 96, 96)          # Color.DELIVERY
+AGENT_COLORS = ["blue", "magenta", "yellow", "green"]          # cooking_world.py COLORS, by agent index
+HOLDING_SCALE, CONTAINER_SCALE = 0.5, 0.7                      # graphic_pipeline.py:35-36
+P_MIN, P_MAX, M_MAX = 4, 128, 128
+
+STATIC_SPRITES = ["Floor", "Counter", "DeliverySquare", "SwitchOn", "SwitchOff", "BlockActive", "cutboard", "blender_on", "blender3",
+                  "Plate"]
+# per food class of soa.DYNAMIC_CLASSES: fresh, chopped, mashed (file_name() of world_objects.py; chopped wins over mashed)
+FOOD_NAMES = {
+    "Onion": ("FreshOnion", "ChoppedOnion", "ChoppedOnion"), "Tomato": ("FreshTomato", "ChoppedTomato", "ChoppedTomato"),
+    "Lettuce": ("FreshLettuce", "ChoppedLettuce", "ChoppedLettuce"), "Carrot": ("FreshCarrot", "ChoppedCarrot", "CarrotMashed"),
+    "Cucumber": ("default_dynamic",) * 3, "Banana": ("FreshBanana", "ChoppedBanana", "ChoppedBanana"),
+    "Apple": ("FreshApple", "ChoppedApple", "ChoppedApple"), "Watermelon": ("FreshWatermelon", "ChoppedWatermelon", "ChoppedWatermelon"),
+    "Bread": ("Bread", "ChoppedFreshBread", "ChoppedFreshBread"),
+}
+SPRITES = list(STATIC_SPRITES)
+for _cls in soa.DYNAMIC_CLASSES[1:]:
+    for _n in FOOD_NAMES[_cls]:
+        if _n not in SPRITES:
+            SPRITES.append(_n)
+SPRITES += [f"{k}-{c}" for k in ("human", "robot") for c in AGENT_COLORS] + ["arrow_left", "arrow_right", "arrow_down", "arrow_up"]
+DEVIATION_ONLY = ["default_dynamic"]                                       # names only deviation 1 reaches
+RECT = -1                                                                  # display-list entry: the Deliversquare's rect
+_INDEX = {n: i for i, n in enumerate(SPRITES)}
+
+
+def sprite_index(name):
+    return _INDEX[name]
+
+
+# sprite of a dynamic slot by class and state (0 fresh, 1 chopped, 2 mashed); of a cell by type and (TOGGLE | ACTIVE | WALK) != 0
+DYN_SPRITE = [[_INDEX["Plate"]] * 3] + [[_INDEX[n] for n in FOOD_NAMES[c]] for c in soa.DYNAMIC_CLASSES[1:]]
+CELL_SPRITE = [[_INDEX[a], _INDEX[b]] for a, b in (("Floor", "Floor"), ("Counter", "Counter"), ("DeliverySquare", "DeliverySquare"),
+                                                    ("SwitchOff", "SwitchOn"), ("BlockActive", "Floor"), ("cutboard", "cutboard"),
+                                                    ("blender3", "blender_on"))]
+SPR_COUNTER, SPR_HUMAN0, SPR_ROBOT0, SPR_ARROW0 = _INDEX["Counter"], _INDEX["human-blue"], _INDEX["robot-blue"], _INDEX["arrow_left"]
+N_SPRITES = len(SPRITES)
+
+
+def geometry(P):
+    """the integers that depend on the tile size: the reference's own float expressions in its own order
+    (graphic_pipeline.py:46-55, 197-220), then int()"""
+    P = int(P)
+    return dict(tile=P, holding=int(P * HOLDING_SCALE), container=int(P * CONTAINER_SCALE),
+                holding_container=int(P * CONTAINER_SCALE * HOLDING_SCALE), arrow=P // 4,
+                holding_off=int(P * (1 - HOLDING_SCALE)), container_off=int(P * (1 - CONTAINER_SCALE) / 2),
+                holding_container_off=int(P * ((1 - HOLDING_SCALE) + (1 - CONTAINER_SCALE) / 2 * HOLDING_SCALE)))
+
+
+def stack_tiles(n):
+    return int(math.floor(math.sqrt(n - 1)) + 1)
+
+
+def display_list(dims, record, P, vis=0):
+    """one record -> (cells, ops).  cells[y * W + x] is the cell's list of (sprite, x0, y0, size) in draw order, pixel
+    coordinates of the frame, sprite an index into SPRITES or RECT; ops is the frame's fill and rect ops in the form of the
+    golden file: ("fill", rgb) and ("rect", rgb, x, y, w, h), the rects in cell order (the reference issues them in the order of
+    its object list; they do not overlap)"""
+    rec = np.asarray(record, dtype=np.uint32)
+    W, H = dims.W, dims.H
+    g = geometry(P)
+    cells = [[] for _ in range(W * H)]
+    ops = [("fill", COLOR_FLOOR)]
+    cb = soa.record_cells(dims, rec)
+    for c in range(W * H):
+        b, x0, y0 = int(cb[c]), (c % W) * P, (c // W) * P
+        ty = b & soa.CELL_TYPE_MASK
+        if ty >= len(CELL_SPRITE):
+            continue
+        if ty == soa.DELIVERSQUARE:
+            cells[c].append((RECT, x0, y0, P))
+            ops.append(("rect", COLOR_DELIVERY, x0, y0, P, P))
+        else:
+            cells[c].append((SPR_COUNTER, x0, y0, P))
+        cells[c].append((CELL_SPRITE[ty][1 if b & (soa.CELL_TOGGLE | soa.CELL_ACTIVE | soa.CELL_WALK) else 0], x0, y0, P))
+    status = int(rec[soa.W_STATUS])
+    agents = [soa.unpack_agent(rec[soa.AGENT_WORD0 + a]) for a in range(dims.A)]
+    q = g["arrow"]
+    arrow_at = {1: (0, q), 2: (3 * P // 4, q), 3: (q, 3 * P // 4), 4: (q, 0)}
+    for a, (x, y, orient, _h) in enumerate(agents):
+        if x >= W or y >= H or status >> (8 + a) & 1:
+            continue
+        lst = cells[y * W + x]
+        lst.append(((SPR_ROBOT0 if vis >> a & 1 else SPR_HUMAN0) + a, x * P, y * P, P))
+        if orient in arrow_at:
+            lst.append((SPR_ARROW0 + orient - 1, x * P + arrow_at[orient][0], y * P + arrow_at[orient][1], q))
+    groups = {}
+    for s in range(dims.D):
+        x, y, cls, flags = soa.unpack_dyn0(rec[dims.dyn0_word0 + s])
+        if not flags & soa.DYN_ALIVE or cls >= len(DYN_SPRITE) or x >= W or y >= H:
+            continue
+        state = 1 if flags & soa.DYN_CHOPPED else 2 if flags & soa.DYN_MASHED else 0
+        groups.setdefault(y * W + x, []).append((cls, DYN_SPRITE[cls][state]))
+    for c, grp in groups.items():
+        x, y = c % W, c // W
+        if any(ax == x and ay == y for ax, ay, _o, _h in agents):
+            base, boff, inner, ioff = g["holding"], g["holding_off"], g["holding_container"], g["holding_container_off"]
+        else:
+            base, boff, inner, ioff = g["tile"], 0, g["container"], g["container_off"]
+        plates = [i for i, (cls, _s) in enumerate(grp) if cls == soa.PLATE]
+        stack, sbase, soff = [s for _c, s in grp], base, boff
+        if len(plates) == 1:
+            cells[c].append((grp[plates[0]][1], x * P + boff, y * P + boff, base))
+            stack, sbase, soff = [s for i, (_c, s) in enumerate(grp) if i != plates[0]], inner, ioff
+        if stack:
+            tiles = stack_tiles(len(stack))
+            size = sbase // tiles
+            for idx, s in enumerate(stack):
+                cells[c].append((s, x * P + soff + size * (idx % tiles), y * P + soff + size * (idx // tiles), size))
+    for c, lst in enumerate(cells):
+        x0, y0 = (c % W) * P, (c // W) * P
+        for _s, dx, dy, size in lst:
+            assert x0 <= dx and y0 <= dy and dx + size <= x0 + P and dy + size <= y0 + P, "a draw leaves its tile"
+    return cells, ops
+
+
+def blend(dst, src, alpha):
+    """dst, src uint8 [..., 3], alpha uint8 [..., 1] -> uint8: round-half-up of (src * a + dst * (255 - a)) / 255"""
+    a = alpha.astype(np.uint32)
+    t = src.astype(np.uint32) * a + dst.astype(np.uint32) * (255 - a) + 128
+    return ((t + (t >> 8)) >> 8).astype(np.uint8)
+
+
+def paint(canvas, sprites, sprite, x0, y0, size):
+    """one draw onto canvas uint8 [Hpx][Wpx][3], in place"""
+    if size <= 0:
+        return
+    region = canvas[y0:y0 + size, x0:x0 + size]
+    if sprite == RECT:
+        region[...] = COLOR_DELIVERY
+        return
+    M = sprites.shape[1]
+    idx = (np.arange(size) * M) // size
+    src = sprites[sprite][idx[:, None], idx[None, :]]
+    region[...] = blend(region, src[..., :3], src[..., 3:])
+
+
+def host_frame(dims, records, P, sprites, vis=0):
+    """records uint32 [n][RW] (or one record) -> uint8 [n][H * P][W * P][3], composed cell by cell"""
+    recs = np.asarray(records, dtype=np.uint32)
+    single = recs.ndim == 1
+    recs = recs.reshape(-1, recs.shape[-1])
+    sprites = check_sheet(sprites)
+    out = np.empty((recs.shape[0], dims.H * P, dims.W * P, 3), dtype=np.uint8)
+    out[...] = COLOR_FLOOR
+    for i, rec in enumerate(recs):
+        for lst in display_list(dims, rec, P, vis)[0]:
+            for s, x0, y0, size in lst:
+                paint(out[i], sprites, s, x0, y0, size)
+    return out[0] if single else out
+
+
+_U8_TO_F32 = (np.arange(256, dtype=np.float32) * (np.float32(1) / np.float32(255))).astype(np.float32)
+
+
+def to_chw32(frame):
+    """uint8 [..., Hpx, Wpx, 3] -> float32 [..., 3, Hpx, Wpx] through the 256-entry table np.float32(v) * (np.float32(1) /
+    np.float32(255)) (module docstring)"""
+    f = _U8_TO_F32[np.asarray(frame, dtype=np.uint8)]
+    return np.ascontiguousarray(np.moveaxis(f, -1, -3))
+
+
+def float_table():
+    return _U8_TO_F32.copy()
+
+
+def check_sheet(sprites):
+    s = np.ascontiguousarray(sprites, dtype=np.uint8)
+    if s.ndim != 4 or s.shape[0] != N_SPRITES or s.shape[1] != s.shape[2] or s.shape[3] != 4 or not 1 <= s.shape[1] <= M_MAX:
+        raise ValueError(f"a sprite sheet is uint8 [{N_SPRITES}][M][M][4] with 1 <= M <= {M_MAX}, not {s.shape}")
+    return s
+
+
+def builtin_sprites(M=16):
+    """the project's own procedural sheet uint8 [S][M][M][4]: per name one base colour and one simple shape (disc, square,
+    diamond by turns) whose alpha falls from 255 at the centre to 0 at the corners.  Deterministic; nothing in it comes from
+    the reference's images.  (M >= 4 for every sprite to hold alpha 0, alpha 255 and something between.)"""
+    M = int(M)
+    u = (np.arange(M, dtype=np.float64) + 0.5) * 2.0 / M - 1.0
+    X, Y = np.meshgrid(u, u)
+    dist = [np.sqrt(X * X + Y * Y), np.maximum(np.abs(X), np.abs(Y)) * 1.25, (np.abs(X) + np.abs(Y)) * 0.9]
+    out = np.zeros((N_SPRITES, M, M, 4), dtype=np.uint8)
+    for i in range(N_SPRITES):
+        h = (i * 2654435761 + 0x9E3779B9) & 0xFFFFFFFF
+        base = np.array([64 + (h & 0x7F), 64 + ((h >> 8) & 0x7F), 64 + ((h >> 16) & 0x7F)], dtype=np.float64)
+        d = dist[i % 3]
+        shade = np.clip(1.0 - 0.35 * d, 0.0, 1.0)
+        out[i, :, :, :3] = np.floor(base[None, None, :] * shade[:, :, None] + 0.5).astype(np.uint8)
+        out[i, :, :, 3] = np.clip(np.floor(255.0 * (1.9 - 2.0 * d) + 0.5), 0, 255).astype(np.uint8)
+        out[i, 0, 0, 3] = out[i, 0, -1, 3] = out[i, -1, 0, 3] = out[i, -1, -1, 3] = 0
+    return out
+
+
+def load_directory(path, M=16):
+    """NAME.png of every name of SPRITES from a user's own asset folder, converted to RGBA and resized to M x M nearest-neighbour"""
+    try:
+        from PIL import Image
+    except ImportError as exc:
+        raise RuntimeError("render.load_directory needs PIL (pillow) to read PNG files; use builtin_sprites() without it") from exc
+    out = np.zeros((N_SPRITES, M, M, 4), dtype=np.uint8)
+    for i, name in enumerate(SPRITES):
+        file = os.path.join(path, name + ".png")
+        if not os.path.isfile(file):
+            raise FileNotFoundError(f"render.load_directory: {file} is missing (the sheet needs every name of render.SPRITES)")
+        with Image.open(file) as im:
+            out[i] = np.asarray(im.convert("RGBA").resize((M, M), Image.NEAREST), dtype=np.uint8)
+    return out

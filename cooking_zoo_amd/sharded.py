@@ -368,6 +368,33 @@ class ShardedVecEnv:
         parts = self._each(lambda i, env: env.action_mask(agents=agents, ignore=ignore))
         return tuple(np.concatenate([p[k] for p in parts]) for k in range(2))
 
+    def load_sprites(self, sprites=None, M=None):
+        """`CookingVecEnv.load_sprites` on every shard: the same sheet everywhere (None: the builtin one)"""
+        self._each(lambda i, env: env.load_sprites(sprites, M))
+
+    def frame_shape(self, P=16):
+        return self.shards[0].frame_shape(P)
+
+    def render_device(self, d_rgb8=None, d_chw32=None, P=16, vis=0):
+        """`CookingVecEnv.render_device` on every shard over its part of the ShardedBuffers (per env: rgb8 uint8 [H * P, W * P, 3],
+        chw32 float32 [3, H * P, W * P])"""
+        part = self._part
+        self._each(lambda i, env: env.render_device(part(d_rgb8, i), part(d_chw32, i), P=P, vis=vis))
+
+    def render(self, env_begin=0, env_count=1, P=16, vis=0):
+        """`CookingVecEnv.render` of envs [env_begin, env_begin + env_count) of the local shards, in global env order: every shard
+        renders its part of the range"""
+        lo, hi, cuts = int(env_begin), int(env_begin) + int(env_count), self._local_cuts
+        if lo < 0 or hi < lo or hi > int(cuts[-1]):
+            raise ValueError(f"render: env range [{lo}, {hi}) outside [0, {int(cuts[-1])})")
+
+        def span(i):                                                      # (first env, count) inside shard i; (0, 0) where they miss it
+            a, b = max(lo, int(cuts[i])), min(hi, int(cuts[i + 1]))
+            return (a - int(cuts[i]), b - a) if b > a else (0, 0)
+
+        parts = self._each(lambda i, env: env.render(*span(i), P=P, vis=vis))
+        return np.concatenate(parts)
+
     def reset_device(self, d_mask=None, d_layout_ids=None, d_obs=None, d_obs32=None, d_codes=None):
         """`CookingVecEnv.reset_device` on every shard, one call each, over its part of the ShardedBuffers (mask uint8 and layout ids
         int32 per env; the three observation forms).  The keyed draws use global env ids: the batch behaves like one handle."""

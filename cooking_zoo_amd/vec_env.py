@@ -12,7 +12,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, rotation as _rotation, soa
+from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, render as _render, rotation as _rotation, soa
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -624,6 +624,44 @@ class CookingVecEnv:
         finally:
             d_grid.free()
             d_xy.free()
+
+    def load_sprites(self, sprites=None, M=None):
+        """the sprite sheet `render_device` draws with: uint8 [render.N_SPRITES, M, M, 4] RGBA (cooking_zoo_amd/render.py: SPRITES,
+        `builtin_sprites`, `load_directory`); None: the builtin procedural sheet at M (default 16).  Uploads once and replaces an
+        earlier sheet; not capturable"""
+        if sprites is None:
+            sprites = _render.builtin_sprites(16 if M is None else M)
+        sheet = _render.check_sheet(sprites)
+        if M is not None and int(M) != sheet.shape[1]:
+            raise ValueError(f"load_sprites: M = {M}, the sheet is {sheet.shape[1]} x {sheet.shape[2]}")
+        _native.check(self._h, _native.lib().cz_load_sprites(self._h, _ptr(sheet), sheet.shape[0], sheet.shape[1]))
+        self._sprites_loaded = True
+
+    def frame_shape(self, P=16):
+        """(H * P, W * P, 3) of one env's frame at tile size P: gymnasium's (height, width, 3)"""
+        return (self.dims.H * int(P), self.dims.W * int(P), 3)
+
+    def render_device(self, d_rgb8=None, d_chw32=None, P=16, vis=0, env_begin=0, env_count=None):
+        """frames of the current state (cooking_zoo_amd/render.py) into device buffers, stream-ordered and capturable: `d_rgb8` uint8
+        [n, H * P, W * P, 3] and / or `d_chw32` float32 [n, 3, H * P, W * P] = `render.to_chw32` (what a convolution takes); at least one of
+        them.  `vis` bit a: agent a is drawn as a robot.  Needs a sheet (`load_sprites`)"""
+        n = self.num_envs if env_count is None else int(env_count)
+        _native.check(self._h, _native.lib().cz_render_device(self._h, env_begin, n, int(P), int(vis), _dev_ptr(d_rgb8), _dev_ptr(d_chw32)))
+
+    def render(self, env_begin=0, env_count=1, P=16, vis=0):
+        """host convenience: uint8 [n, H * P, W * P, 3] of envs [env_begin, env_begin + n); loads the builtin sheet on first use"""
+        n = int(env_count)
+        shape = (n,) + self.frame_shape(P)
+        if not getattr(self, "_sprites_loaded", False):
+            self.load_sprites()
+        if n == 0:
+            return np.zeros(shape, np.uint8)
+        d_rgb = DeviceBuffer(self, shape, np.uint8)
+        try:
+            self.render_device(d_rgb8=d_rgb, P=P, vis=vis, env_begin=env_begin, env_count=n)
+            return d_rgb.to_host()
+        finally:
+            d_rgb.free()
 
     def navigate_device(self, d_target, d_action=None, d_steps=None, d_field=None, walkable_blocks=False, env_begin=0, env_count=None,
                         T=None):

@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_action_effects_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_action_effects_device, cz_render_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -446,6 +446,31 @@ int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, const uint16
 int32_t cz_num_actions(cz_handle h);          /* 5 (scheme3) or 8 (scheme1); -1 for a null handle */
 int cz_action_effects_device(cz_handle h, int64_t env_begin, int64_t env_count, uint32_t agents, uint32_t ignore,
                              uint8_t *d_mask, uint8_t *d_effects);
+
+/* ---- frames ---------------------------------------------------------------------------------------- */
+/* Frames of the current state (k_render; cooking_zoo_amd/render.py is the definition and the host model): the reference's
+ * GraphicPipeline.render (environment/game/graphic_pipeline.py) as a display list per cell - (sprite, x0, y0, size) in draw order:
+ * Counter and the cell's own sprite (a Deliversquare: a rect of Color.DELIVERY, then its sprite), the agents on the cell with
+ * their orientation arrows, the cell's alive slots in slot order as Plate / food stack - composited per pixel with the project's
+ * own rule: a draw of size s at (x0, y0) samples the M x M sprite at ((px - x0) * M / s, (py - y0) * M / s) in integers, and per
+ * channel t = src * a + dst * (255 - a) + 128, dst = (t + (t >> 8)) >> 8 over a canvas that starts at Color.FLOOR.  P is the tile
+ * size in pixels (the reference's PIXEL_PER_TILE = 80), 4 <= P <= 128; the geometry follows from P by the reference's own double
+ * expressions.  d_rgb8 uint8 [env_count][H * P][W * P][3] and / or d_chw32 float [env_count][3][H * P][W * P] = v * (1.0f / 255.0f) (a table: torch's `x / 255` on the device);
+ * every byte is written exactly once.  d_rgb8 must be 4-byte aligned and d_chw32 16-byte aligned.  `vis` bit a: agent a is drawn
+ * as `robot`, otherwise as `human`.  env_count = 0 is a no-op.
+ * Deviations from the reference: (1) Cucumber is drawn as `default_dynamic` without text (the reference's font.render() without
+ * arguments raises there); (2) an agent whose despawn bit is set is not drawn (what it holds still is), and agent a always uses
+ * `vis` bit a and colour a - the reference draws relevant_agents, which keeps a just-despawned agent one step longer, and indexes
+ * agent_visualization by the position in that list; (3) the sprite is resampled from the M x M master, not from the original
+ * file; (4) the blend rule is the project's: equality with pygame's blitter is unverified; (5) slots or agents whose coordinates
+ * lie outside the grid are not drawn.
+ * cz_load_sprites takes the sheet uint8 [cz_render_sprites()][M][M][4] RGBA from HOST memory, 1 <= M <= 128, uploads it once
+ * together with the float table and replaces an earlier sheet; it allocates, copies and waits: NOT capturable.
+ * cz_render_device is one launch on the handle's stream: no copy, wait or allocation, legal inside a stream capture; the records
+ * are only read. */
+int32_t cz_render_sprites(void);              /* the number of sprites of a sheet (cooking_zoo_amd/render.py SPRITES) */
+int cz_load_sprites(cz_handle h, const uint8_t *rgba, int32_t n_sprites, int32_t M);
+int cz_render_device(cz_handle h, int64_t env_begin, int64_t env_count, int32_t P, uint32_t vis, uint8_t *d_rgb8, float *d_chw32);
 
 /* ---- step ------------------------------------------------------------------------------------------ */
 /* One batched env step = accumulated_step (cooking_env.py:243-269): world_step (cooking_world.py:104-112),
