@@ -1,5 +1,5 @@
 // cz_api.hip -- C-ABI (include/cookingzoo.h) of the MI355X-native CookingZoo step path: handle, tables, launches,
-// statistics, RCCL.  The kernels live in cz_kernels.h / cz_device.h (one wavefront per env instance) and are
+// statistics, RCCL.  The kernels live in cz_kernels.h / cz_offstep.h / cz_query.h / cz_device.h (one wavefront per env instance) and are
 // instantiated in cz_inst_small.hip / cz_inst_large.hip.  gfx950 only.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "../../include/cookingzoo.h"
-#include "cz_kernels.h"
+#include "cz_launch.h"
 #include "cz_generate.h"
 
 using namespace cz;
@@ -375,6 +375,7 @@ struct cz_handle_s {
 static thread_local std::string g_err;
 static int ready(cz_handle h);
 static int set_device(cz_handle h);
+static int begin_ranged_call(cz_handle h, int64_t b, int64_t c);
 static void mark_ranks(cz_handle h, int32_t first, int32_t count, int ok);
 static int flush_updates(cz_handle h, bool force);
 
@@ -1388,7 +1389,7 @@ extern "C" int cz_observe(cz_handle h, int64_t b, int64_t c, double *obs) {
 // that stays on the device needs after cz_reset / cz_set_state, before the first step has written anything.  Stream-ordered,
 // no synchronisation (legal inside a stream capture of the caller).
 extern "C" int cz_observe_device(cz_handle h, int64_t b, int64_t c, double *d_obs, uint8_t *d_codes) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (c == 0) return 0;
     if (!d_obs && !d_codes) return fail(h, "cz_observe_device: both output pointers are null");
     if (set_device(h)) return 1;
@@ -1418,9 +1419,6 @@ static int set_device(cz_handle h) {
     return 0;
 }
 
-// Begins a call that works on device pointers: the handle is ready, the entry point's own arguments are good (`bad_args`: its message
-// otherwise), a fused rollout (`rollout`: the entry point's name) stays inside the span the kernel addresses, the handle's device is
-// current, and a staged layout update whose time may have come is flushed - unless the caller is capturing.
 // the archive arguments of cz_save_device / cz_restore_device (`who`), in front of everything that needs the device
 static int check_archive(cz_handle h, const char *who, const int32_t *d_slot, const uint32_t *d_records, int64_t capacity) {
     if (!h) return fail(nullptr, "null handle");
@@ -1428,6 +1426,9 @@ static int check_archive(cz_handle h, const char *who, const int32_t *d_slot, co
     if (!d_slot && capacity < h->P.N) return fail(h, "%s: without slots the archive needs a row per env (capacity %lld < %d envs)", who, (long long)capacity, h->P.N);
     return 0;
 }
+// Begins a call that works on device pointers: the handle is ready, the entry point's own arguments are good (`bad_args`: its message
+// otherwise), a fused rollout (`rollout`: the entry point's name) stays inside the span the kernel addresses, the handle's device is
+// current, and a staged layout update whose time may have come is flushed - unless the caller is capturing.
 static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, const char *rollout = nullptr, int32_t T = 0) {
     if (ready(h)) return 1;
     if (!args_ok) return fail(h, "%s", bad_args);
@@ -1439,6 +1440,9 @@ static int begin_device_call(cz_handle h, bool args_ok, const char *bad_args, co
     if (!h->upd_ranges.empty() && !caller_capturing(h) && flush_updates(h, false)) return 1;
     return 0;
 }
+// Begins a device-pointer call on the envs [b, b + c): the handle is ready and the range lies inside the batch.  The call's own checks
+// follow in its own order, then set_device.
+static int begin_ranged_call(cz_handle h, int64_t b, int64_t c) { return ready(h) || check_range(h, b, c); }
 
 // reset() of cooking_env.py:178-210 for chosen envs, decided and carried out on the device: one launch of k_reset_where over the whole
 // batch on the handle's stream - no copy, no query, no wait, so it is legal inside a capture of the caller; outside one a staged layout
@@ -1530,7 +1534,7 @@ extern "C" int cz_set_f32_output(cz_handle h, float *d_obs32) {
 // observe() of the current state as float32 rows [env_count][A][F] into a DEVICE buffer: the first observation of a float32
 // consumer after cz_reset / cz_set_state.  Stream-ordered, nothing is synchronised (legal inside a stream capture of the caller).
 extern "C" int cz_observe_device_f32(cz_handle h, int64_t b, int64_t c, float *d_obs32) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (c == 0) return 0;
     if (!d_obs32) return fail(h, "cz_observe_device_f32: the output pointer is null");
     if (set_device(h)) return 1;
@@ -1539,13 +1543,13 @@ extern "C" int cz_observe_device_f32(cz_handle h, int64_t b, int64_t c, float *d
     HIPCHK(h, h->kl.observe_f32(P, h->stream, b, (int)c, d_obs32));
     return 0;
 }
-// The grid observation of the current state into DEVICE buffers (k_observe_grid, cz_kernels.h; definition: cooking_zoo_amd/grid.py): any
+// The grid observation of the current state into DEVICE buffers (k_observe_grid, cz_query.h; definition: cooking_zoo_amd/grid.py): any
 // of the three forms of the (W, H, C) tensor and the agents' locations, laid out for env_count envs.  Stream-ordered, nothing is copied,
 // waited for or queried (legal inside a stream capture of the caller).
 extern "C" int32_t cz_grid_channels(int32_t extended) { return extended == 0 ? 32 : extended == 1 ? 48 : -1; }
 extern "C" int cz_observe_grid_device(cz_handle h, int64_t b, int64_t c, int32_t extended, uint32_t *d_bits, uint8_t *d_grid8, float *d_grid32,
                                       int32_t *d_agent_xy) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (cz_grid_channels(extended) < 0) return fail(h, "cz_observe_grid_device: extended is %d, not 0 or 1", extended);
     if (c == 0) return 0;
     if (!d_bits && !d_grid8 && !d_grid32 && !d_agent_xy) return fail(h, "cz_observe_grid_device: all four output pointers are null");
@@ -1555,7 +1559,7 @@ extern "C" int cz_observe_grid_device(cz_handle h, int64_t b, int64_t c, int32_t
     HIPCHK(h, h->kl.observe_grid(h->P, h->stream, b, (int)c, extended, d_bits, d_grid8, d_grid32, d_agent_xy));
     return 0;
 }
-// Frames of the current state into DEVICE buffers (k_render, cz_kernels.h; definition: cooking_zoo_amd/render.py).  cz_load_sprites
+// Frames of the current state into DEVICE buffers (k_render, cz_query.h; definition: cooking_zoo_amd/render.py).  cz_load_sprites
 // takes the sheet uint8 [cz_render_sprites()][M][M][4] RGBA from HOST memory, uploads it with the table v * (1 / 255) and replaces an earlier
 // sheet; it allocates, copies and waits for the stream (not capturable).  cz_render_device is one launch on the env's stream: nothing
 // is copied, waited for, queried or allocated (legal inside a stream capture of the caller); the records are only read.
@@ -1579,7 +1583,7 @@ extern "C" int cz_load_sprites(cz_handle h, const uint8_t *rgba, int32_t n_sprit
     return 0;
 }
 extern "C" int cz_render_device(cz_handle h, int64_t b, int64_t c, int32_t P, uint32_t vis, uint8_t *d_rgb8, float *d_chw32) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (P < RENDER_P_MIN || P > RENDER_P_MAX) return fail(h, "cz_render_device: P = %d is outside [%d, %d]", P, RENDER_P_MIN, RENDER_P_MAX);
     if (!h->sprites_M) return fail(h, "cz_render_device: no sprite sheet is loaded (cz_load_sprites)");
     if (c == 0) return 0;
@@ -1611,13 +1615,13 @@ extern "C" int cz_render_device(cz_handle h, int64_t b, int64_t c, int32_t P, ui
     HIPCHK(h, h->kl.render(h->P, h->stream, (int)c, G));
     return 0;
 }
-// Shortest-path navigation on the current state into DEVICE buffers (k_navigate, cz_kernels.h; definition: cooking_zoo_amd/nav.py):
+// Shortest-path navigation on the current state into DEVICE buffers (k_navigate, cz_query.h; definition: cooking_zoo_amd/nav.py):
 // first move, path length and / or the whole distance field for every agent and T candidate goals each.  Stream-ordered, nothing is
 // copied, waited for or queried (legal inside a stream capture of the caller); the records are only read.
 extern "C" int32_t cz_nav_max_targets(void) { return NAV_MAX_TARGETS; }
 extern "C" int cz_navigate_device(cz_handle h, int64_t b, int64_t c, int32_t T, uint32_t flags, const int32_t *d_target, int32_t *d_action,
                                   int32_t *d_steps, uint16_t *d_field) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (T < 1 || T > NAV_MAX_TARGETS) return fail(h, "cz_navigate_device: T is %d, not in 1..%d targets per agent", T, NAV_MAX_TARGETS);
     if (flags & ~NAV_KNOWN_FLAGS) return fail(h, "cz_navigate_device: unknown flags bits 0x%x", flags & ~NAV_KNOWN_FLAGS);
     if (c == 0) return 0;
@@ -1694,12 +1698,12 @@ extern "C" int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t 
 static unsigned long long *partner_counter(cz_handle h) {
     return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_partner) + ((size_t)h->partner_rows_alloc * PARTNER_ROW_WORDS * 4 + 7) / 8 * 8);
 }
-// The scripted partner on the current state into DEVICE buffers (k_partner, cz_kernels.h; definition: cooking_zoo_amd/partner.py): the
+// The scripted partner on the current state into DEVICE buffers (k_partner, cz_query.h; definition: cooking_zoo_amd/partner.py): the
 // action the reference's CookingAgent would return for every chosen agent of every env.  Stream-ordered, nothing is copied, waited
 // for, queried or allocated (legal inside a stream capture of the caller); the records are only read.
 extern "C" int cz_partner_device(cz_handle h, int64_t b, int64_t c, uint32_t agents, uint32_t flags, const int32_t *d_recipe, int32_t *d_action,
                                  int32_t *d_target, uint8_t *d_status) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (agents == 0 || agents >> h->P.A) return fail(h, "cz_partner_device: agents is 0x%x, not a non-empty set of the %d agents", agents, h->P.A);
     if (flags) return fail(h, "cz_partner_device: unknown flags bits 0x%x", flags);
     if (!h->d_partner || h->n_partner == 0 || h->n_partner != h->n_recipes) return fail(h, "cz_partner_device: no partner table for the loaded recipes (cz_load_partner_table)");
@@ -1719,13 +1723,13 @@ extern "C" int64_t cz_partner_bad_recipes(cz_handle h) {
     if (!h || !h->d_partner) return h ? 0 : -1;
     return read_counter<unsigned long long>(h, partner_counter(h), "cz_partner_bad_recipes");
 }
-// Action effects and masks on the current state into DEVICE buffers (k_action_effects, cz_kernels.h; definition:
+// Action effects and masks on the current state into DEVICE buffers (k_action_effects, cz_query.h; definition:
 // cooking_zoo_amd/effects.py): for every chosen agent of every env and every action code, what the action would change if the agent
 // played it alone.  Stream-ordered, nothing is copied, waited for, queried or allocated (legal inside a stream capture of the caller);
 // the records are only read; not a step: counts nothing.
 extern "C" int32_t cz_num_actions(cz_handle h) { return h ? (h->P.scheme == 3 ? 5 : 8) : -1; }   // actions.py:17,50
 extern "C" int cz_action_effects_device(cz_handle h, int64_t b, int64_t c, uint32_t agents, uint32_t ignore, uint8_t *d_mask, uint8_t *d_effects) {
-    if (ready(h) || check_range(h, b, c)) return 1;
+    if (begin_ranged_call(h, b, c)) return 1;
     if (agents == 0 || agents >> h->P.A) return fail(h, "cz_action_effects_device: agents is 0x%x, not a non-empty set of the %d agents", agents, h->P.A);
     if (ignore & ~FX_ALL) return fail(h, "cz_action_effects_device: unknown ignore bits 0x%x", ignore & ~FX_ALL);
     if (!d_mask && !d_effects) return fail(h, "cz_action_effects_device: both output pointers are null");

@@ -4,7 +4,7 @@ The reference declares `obs_spaces=["full"]` as a dict of a `(W, H, 32)` tensor,
 (`cooking_env.py:118-123, 274-278`), allocates the tensor (`cooking_env.py:149-150`) and never writes it; every class of
 `world_objects.py` carries the per-object vector it was meant to hold (`numeric_state_representation()`, `state_length()`).
 This module is the definition of that tensor for the batched env, on the host, from records alone (it never loads the device
-library); `k_observe_grid` (csrc/cz_kernels.h, `CookingVecEnv.observe_grid_device`) computes the same words on the device.
+library); `k_observe_grid` (csrc/cz_query.h, `CookingVecEnv.observe_grid_device`) computes the same words on the device.
 
 Reference channels (32): the classes in `GAME_CLASSES` order (alphabetical), `state_length()` consecutive channels each; the
 content at `[x, y, off(cls) : off(cls) + len]` is `numeric_state_representation()` of an object of that class whose location is

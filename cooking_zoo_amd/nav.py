@@ -14,7 +14,7 @@ lexicographically smallest shortest path in move codes, so one flood fill from t
     no such neighbour: action 0, steps -1.
 
 `reachable(a, b)` of the reference is `steps >= 0`.  This module is the definition for the batched env, on the host, from records
-alone (it never loads the device library); `k_navigate` (csrc/cz_kernels.h, `CookingVecEnv.navigate_device`) computes the same
+alone (it never loads the device library); `k_navigate` (csrc/cz_query.h, `CookingVecEnv.navigate_device`) computes the same
 on the device.  `tests/golden/nav_ref.json.gz` (tools/gen_nav_golden.py) holds what the unmodified reference returns.
 
 Deviations from the reference:

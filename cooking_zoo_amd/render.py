@@ -3,7 +3,7 @@
 The reference renders with pygame: a fill, then per object `transform.scale(image, size)` and `blit(image, location)`.  Every
 class has a `file_name()`, every draw stays inside its own tile, and no supported class returns text or icons, so a frame is a
 DISPLAY LIST per cell - (sprite, x0, y0, size) in draw order - composited per pixel.  This module is that definition for the
-batched env, on the host, from records alone (numpy only; it never loads the device library); `k_render` (csrc/cz_kernels.h,
+batched env, on the host, from records alone (numpy only; it never loads the device library); `k_render` (csrc/cz_query.h,
 `CookingVecEnv.render_device`) computes the same bytes on the device.
 
 The display list is reference semantics (tests/golden/render_ref.json.gz holds the ops of the unmodified reference's own

@@ -7,6 +7,7 @@ include/cookingzoo.h; this class only prepares tables (layout pool, recipe table
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import random as _random
 
@@ -496,7 +497,7 @@ class CookingVecEnv:
         if return_codes:
             self.reset(layout_ids, False, env_begin, env_count)
             return self.observe_compact(env_begin, env_count)
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         ids, pools = self.initial_layout_ids()
         if layout_ids is not None:
             ids = np.ascontiguousarray(layout_ids, dtype=np.int32)
@@ -509,6 +510,24 @@ class CookingVecEnv:
         if self.spawn is not None:
             self.spawn.refresh(reset=True)
         return obs
+
+    def _count(self, env_count):
+        """the env count of a ranged call: every env unless given"""
+        return self.num_envs if env_count is None else int(env_count)
+
+    @contextlib.contextmanager
+    def _scratch(self, *specs):
+        """scratch DeviceBuffers for one call, one per (shape, dtype[, initial host array]); all freed on exit"""
+        bufs = []
+        try:
+            for shape, dtype, *init in specs:
+                bufs.append(DeviceBuffer(self, shape, dtype))
+                if init:
+                    bufs[-1].from_host(init[0])
+            yield bufs
+        finally:
+            for b in bufs:
+                b.free()
 
     def _host_array(self, key, shape, dtype):
         """a fresh array, or (pinned_outputs) the env's page-locked buffer of that role"""
@@ -576,14 +595,14 @@ class CookingVecEnv:
         return (int(marks) >> (bits * r)) & ((1 << bits) - 1)
 
     def observe(self, env_begin=0, env_count=None):
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         obs = self._host_array("obs", (n, self.num_agents, self.F), np.float64)
         _native.check(self._h, _native.lib().cz_observe(self._h, env_begin, n, _ptr(obs)))
         return obs
 
     def observe_compact(self, env_begin=0, env_count=None):
         """`observe` as one byte per feature: uint8 [n, A, codes_pitch]; `obs_table()[codes[..., :F]]` is the float64 observation"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         codes = self._host_array("codes", (n, self.num_agents, self.codes_pitch), np.uint8)
         _native.check(self._h, _native.lib().cz_observe_compact(self._h, env_begin, n, _ptr(codes)))
         return codes
@@ -591,7 +610,7 @@ class CookingVecEnv:
     def observe_device(self, d_obs=None, d_codes=None, env_begin=0, env_count=None, d_obs32=None):
         """the current observation into device buffers (float64 [n, A, F] and / or codes uint8 [n, A, codes_pitch] and / or float32
         [n, A, F] rows, the form of `step_device_f32`), stream-ordered: what a device-resident consumer reads before its first step"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         if d_obs is not None or d_codes is not None or d_obs32 is None:
             _native.check(self._h, _native.lib().cz_observe_device(self._h, env_begin, n, _dev_ptr(d_obs), _dev_ptr(d_codes)))
         if d_obs32 is not None:
@@ -606,24 +625,20 @@ class CookingVecEnv:
         device buffers, stream-ordered and capturable: `d_bits` uint32 [n, W, H, C / 32], `d_grid8` uint8 [n, W, H, C], `d_grid32`
         float32 [n, W, H, C] (a torch tensor's `permute(0, 3, 1, 2)` is the channels_last image), `d_agent_xy` int32 [n, A, 2];
         at least one of them"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_observe_grid_device(self._h, env_begin, n, int(extended), p(d_bits), p(d_grid8), p(d_grid32),
                                                                     p(d_agent_xy)))
 
     def observe_grid(self, extended=False, env_begin=0, env_count=None):
         """host convenience: (uint8 [n, W, H, C], int32 [n, A, 2]) of envs [env_begin, env_begin + n)"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         shape = (n,) + self.grid_shape(extended)
         if n == 0:
             return np.zeros(shape, np.uint8), np.zeros((0, self.num_agents, 2), np.int32)
-        d_grid, d_xy = DeviceBuffer(self, shape, np.uint8), DeviceBuffer(self, (n, self.num_agents, 2), np.int32)
-        try:
+        with self._scratch((shape, np.uint8), ((n, self.num_agents, 2), np.int32)) as (d_grid, d_xy):
             self.observe_grid_device(d_grid8=d_grid, d_agent_xy=d_xy, extended=extended, env_begin=env_begin, env_count=n)
             return d_grid.to_host(), d_xy.to_host()
-        finally:
-            d_grid.free()
-            d_xy.free()
 
     def load_sprites(self, sprites=None, M=None):
         """the sprite sheet `render_device` draws with: uint8 [render.N_SPRITES, M, M, 4] RGBA (cooking_zoo_amd/render.py: SPRITES,
@@ -645,7 +660,7 @@ class CookingVecEnv:
         """frames of the current state (cooking_zoo_amd/render.py) into device buffers, stream-ordered and capturable: `d_rgb8` uint8
         [n, H * P, W * P, 3] and / or `d_chw32` float32 [n, 3, H * P, W * P] = `render.to_chw32` (what a convolution takes); at least one of
         them.  `vis` bit a: agent a is drawn as a robot.  Needs a sheet (`load_sprites`)"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         _native.check(self._h, _native.lib().cz_render_device(self._h, env_begin, n, int(P), int(vis), _dev_ptr(d_rgb8), _dev_ptr(d_chw32)))
 
     def render(self, env_begin=0, env_count=1, P=16, vis=0):
@@ -656,12 +671,9 @@ class CookingVecEnv:
             self.load_sprites()
         if n == 0:
             return np.zeros(shape, np.uint8)
-        d_rgb = DeviceBuffer(self, shape, np.uint8)
-        try:
+        with self._scratch((shape, np.uint8)) as (d_rgb,):
             self.render_device(d_rgb8=d_rgb, P=P, vis=vis, env_begin=env_begin, env_count=n)
             return d_rgb.to_host()
-        finally:
-            d_rgb.free()
 
     def navigate_device(self, d_target, d_action=None, d_steps=None, d_field=None, walkable_blocks=False, env_begin=0, env_count=None,
                         T=None):
@@ -671,7 +683,7 @@ class CookingVecEnv:
         0..4; with T = 1 the array `step_device` takes), `d_steps` int32 [n, A, T] (0 at the goal, -1 unreachable), `d_field`
         uint16 [n, A, T, W * H] (cell (x, y) at x * H + y, 0xFFFF unreachable); at least one output.  T is read from the target
         buffer's shape ([n, A, T, 2], or [n, A, 2] for T = 1) unless given."""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         if T is None:
             shape = tuple(getattr(d_target, "shape", ()))
             if len(shape) not in (3, 4) or shape[-1] != 2 or shape[-3 if len(shape) == 4 else -2] != self.num_agents:
@@ -685,21 +697,16 @@ class CookingVecEnv:
     def navigate(self, targets, walkable_blocks=False, env_begin=0, env_count=None):
         """host convenience: targets int [n, A, T, 2] (or [n, A, 2]) -> (actions int32 [n, A, T], steps int32 [n, A, T]) of envs
         [env_begin, env_begin + n)"""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         tg = np.ascontiguousarray(targets, dtype=np.int32)
         T = tg.shape[2] if tg.ndim == 4 else 1
         if n == 0:
             return np.zeros((0, self.num_agents, T), np.int32), np.zeros((0, self.num_agents, T), np.int32)
         tg = tg.reshape(n, self.num_agents, T, 2)
         shape = (n, self.num_agents, T)
-        d_t, d_a, d_s = DeviceBuffer(self, tg.shape, np.int32), DeviceBuffer(self, shape, np.int32), DeviceBuffer(self, shape, np.int32)
-        try:
-            d_t.from_host(tg)
+        with self._scratch((tg.shape, np.int32, tg), (shape, np.int32), (shape, np.int32)) as (d_t, d_a, d_s):
             self.navigate_device(d_t, d_a, d_s, walkable_blocks=walkable_blocks, env_begin=env_begin, env_count=n)
             return d_a.to_host(), d_s.to_host()
-        finally:
-            for b in (d_t, d_a, d_s):
-                b.free()
 
     def _recipe_indices(self, recipes, n):
         """recipe names or table indices, one per agent or [n, A] -> int32 [n, A] indices into the loaded recipe table"""
@@ -716,7 +723,7 @@ class CookingVecEnv:
         of `navigate_device`), `d_status` uint8 [n, A] (partner.DONE / WALK / IDLE / RAISES / ABSENT); at least one output.
         `agents`: bit a = agent a is driven (None: all); the entries of the other agents are left untouched in every output.
         `d_recipe` int32 [n, A]: indices into the recipe table (`book_names`); None: every env's own recipes."""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         mask = (1 << self.num_agents) - 1 if agents is None else int(agents)
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_partner_device(self._h, env_begin, n, mask, 0, p(d_recipe), p(d_action), p(d_target), p(d_status)))
@@ -729,24 +736,18 @@ class CookingVecEnv:
         """host convenience: (actions int32 [n, A], targets int32 [n, A, 2], status uint8 [n, A]) of envs [env_begin, env_begin + n);
         `recipes`: names or table indices, one per agent or [n, A] (None: the envs' own).  An agent that is not driven reads
         0, (-1, -1), partner.IDLE."""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         A = self.num_agents
         if n == 0:
             return np.zeros((0, A), np.int32), np.zeros((0, A, 2), np.int32), np.zeros((0, A), np.uint8)
-        bufs = [DeviceBuffer(self, (n, A), np.int32), DeviceBuffer(self, (n, A, 2), np.int32), DeviceBuffer(self, (n, A), np.uint8)]
-        try:
-            bufs[0].from_host(np.zeros((n, A), np.int32))
-            bufs[1].from_host(np.full((n, A, 2), -1, np.int32))
-            bufs[2].from_host(np.full((n, A), _partner.IDLE, np.uint8))
-            if recipes is not None:
-                bufs.append(DeviceBuffer(self, (n, A), np.int32))
-                bufs[3].from_host(self._recipe_indices(recipes, n))
+        specs = [((n, A), np.int32, np.zeros((n, A), np.int32)), ((n, A, 2), np.int32, np.full((n, A, 2), -1, np.int32)),
+                 ((n, A), np.uint8, np.full((n, A), _partner.IDLE, np.uint8))]
+        if recipes is not None:
+            specs.append(((n, A), np.int32, self._recipe_indices(recipes, n)))
+        with self._scratch(*specs) as bufs:
             self.partner_device(bufs[0], bufs[1], bufs[2], agents=agents, d_recipe=bufs[3] if recipes is not None else None,
                                 env_begin=env_begin, env_count=n)
             return bufs[0].to_host(), bufs[1].to_host(), bufs[2].to_host()
-        finally:
-            for b in bufs:
-                b.free()
 
     @property
     def num_actions(self):
@@ -761,7 +762,7 @@ class CookingVecEnv:
         asked for (None: all); the rows of the other agents are left untouched in both outputs.  `ignore`: effect bits that do not
         make an action count (effects.TURNED: turning on the spot is a no-op).  A despawned agent and every agent of a finished env
         get the noop-only row.  The records are only read; not a step."""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         chosen = (1 << self.num_agents) - 1 if agents is None else int(agents)
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_action_effects_device(self._h, env_begin, n, chosen, int(ignore), p(d_mask), p(d_effects)))
@@ -769,21 +770,15 @@ class CookingVecEnv:
     def action_mask(self, agents=None, ignore=0, env_begin=0, env_count=None):
         """host convenience: (mask uint8 [n, A, num_actions], effects uint8 [n, A, num_actions]) of envs [env_begin, env_begin + n).
         An agent that is not asked for reads the noop-only row and effects 0."""
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         shape = (n, self.num_agents, self.num_actions)
         noop = np.zeros(shape, np.uint8)
         noop[..., 0] = 1
         if n == 0:
             return noop, np.zeros(shape, np.uint8)
-        d_m, d_e = DeviceBuffer(self, shape, np.uint8), DeviceBuffer(self, shape, np.uint8)
-        try:
-            d_m.from_host(noop)
-            d_e.from_host(np.zeros(shape, np.uint8))
+        with self._scratch((shape, np.uint8, noop), (shape, np.uint8, np.zeros(shape, np.uint8))) as (d_m, d_e):
             self.action_effects_device(d_m, d_e, agents=agents, ignore=ignore, env_begin=env_begin, env_count=n)
             return d_m.to_host(), d_e.to_host()
-        finally:
-            d_m.free()
-            d_e.free()
 
     # ------------------------------------------------------------------ device-resident API
     def alloc(self, shape, dtype):
@@ -985,7 +980,7 @@ class CookingVecEnv:
 
     # ------------------------------------------------------------------ state / stats
     def get_state(self, env_begin=0, env_count=None):
-        n = self.num_envs if env_count is None else int(env_count)
+        n = self._count(env_count)
         recs = np.empty((n, self.dims.RW), dtype=np.uint32)
         _native.check(self._h, _native.lib().cz_get_state(self._h, env_begin, n, _ptr(recs)))
         return recs
