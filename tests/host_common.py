@@ -1,7 +1,7 @@
 """Helpers of the host tests that GPU tests use as well: the gfx950 code objects inside the built library (`device_code`, a fixture
 a module imports by name: `from host_common import device_code  # noqa: F401`), the numpy models of cz_save_device /
-cz_restore_device's bookkeeping, the reference's despawn / respawn rule for one world, and the user recipes of the custom_wide_*
-golden sets."""
+cz_restore_device's bookkeeping, the numpy walk of an observation descriptor, the reference's despawn / respawn rule for one world,
+and the user recipes of the custom_wide_* golden sets."""
 import os
 import re
 import shutil
@@ -101,6 +101,50 @@ def row_ok(row, dims, n_layouts, n_recipes, recipes_per_env):
         return False
     d0, d1 = row[dims.dyn0_word0:dims.dyn0_word0 + dims.D], row[dims.dyn1_word0:dims.dyn1_word0 + dims.D]
     return not ((((d0 >> 24) & soa.DYN_ALIVE) == 0) & ((d1 & 0xFF) != 0)).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the observation descriptor, evaluated on the host
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def eval_descriptor(desc, d, rec):
+    """numpy restatement of the kernel's descriptor walk (host-side check of the table builder)."""
+    lut = np.zeros(soa.LUT_SIZE)
+    for i in range(2 * d.W - 1):
+        lut[i] = (i - (d.W - 1)) / d.W
+    for i in range(2 * d.H - 1):
+        lut[soa.LUT_Y0 + i] = (i - (d.H - 1)) / d.H
+    lut[soa.LUT_ONE] = 1.0
+    obj0, cell0, ag0, zero = d.img_layout()
+    img = np.full(zero + 2, soa.LUT_ABSENT, dtype=np.int64)
+    cells = soa.record_cells(d, rec)
+    ag = [soa.unpack_agent(rec[soa.AGENT_WORD0 + a]) for a in range(d.A)]
+    for s_ in range(d.D):
+        x, y, c, fl = soa.unpack_dyn0(rec[d.dyn0_word0 + s_])
+        if fl & soa.DYN_ALIVE:
+            ch, ma = bool(fl & soa.DYN_CHOPPED), bool(fl & soa.DYN_MASHED)
+            img[obj0 + 6 * s_:obj0 + 6 * s_ + 6] = [x + d.W - 1, y + soa.LUT_Y0 + d.H - 1, 126 + (not (ch or ma)),
+                                                                  126 + ch, 126 + ma, 127]
+    for c in range(d.C):
+        f = bool(cells[c] & (soa.CELL_ACTIVE | soa.CELL_WALK))
+        img[cell0 + 4 * c:cell0 + 4 * c + 4] = [c % d.W + d.W - 1, c // d.W + soa.LUT_Y0 + d.H - 1, 126 + f, 127]
+    for a in range(d.A):
+        x, y, o, _ = ag[a]
+        img[ag0 + 8 * a:ag0 + 8 * a + 7] = [x + d.W - 1, y + soa.LUT_Y0 + d.H - 1] + [126 + (o == k) for k in (1, 2, 3, 4)] + [127]
+    out = np.zeros((d.A, d.F))
+    for f, w in enumerate(desc):
+        w = int(w)
+        hw, code = (w & 0xFFFF) // 2, (w >> 16) // 4
+        for a in range(d.A):
+            sub = 0
+            if code == soa.AX_X:
+                sub = ag[a][0]
+            elif code == soa.AX_Y:
+                sub = ag[a][1]
+            elif code >= 4 and (code - 4) // 2 != a:
+                sub = ag[a][(code - 4) % 2]
+            out[a, f] = lut[img[hw] - sub]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

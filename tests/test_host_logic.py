@@ -10,6 +10,7 @@ from cooking_zoo_amd import _native, soa
 from cooking_zoo_amd.cooking_book.recipe_drawer import RECIPES, DEFAULT_NUM_GOALS
 from cooking_zoo_amd.cooking_world.layout import feature_length
 from cooking_zoo_amd.cooking_world.engine.load_level import load_meta_file
+from host_common import eval_descriptor
 from golden_io import GoldenSet, golden_sets, layout_from_episode, recipe_table, RECIPE_NAMES
 from oracle_binding import Oracle
 from vec_common import bits
@@ -50,46 +51,6 @@ def test_layout_record_and_descriptor_match_reference(name):
         for t in range(0, len(ep.states), 7):
             got = eval_descriptor(desc, ep.dims, ep.states[t])
             assert np.array_equal(bits(got), bits(ep.obs[t])), (name, t)
-
-
-def eval_descriptor(desc, d, rec):
-    """numpy restatement of the kernel's descriptor walk (host-side check of the table builder)."""
-    lut = np.zeros(soa.LUT_SIZE)
-    for i in range(2 * d.W - 1):
-        lut[i] = (i - (d.W - 1)) / d.W
-    for i in range(2 * d.H - 1):
-        lut[soa.LUT_Y0 + i] = (i - (d.H - 1)) / d.H
-    lut[soa.LUT_ONE] = 1.0
-    obj0, cell0, ag0, zero = d.img_layout()
-    img = np.full(zero + 2, soa.LUT_ABSENT, dtype=np.int64)
-    cells = soa.record_cells(d, rec)
-    ag = [soa.unpack_agent(rec[soa.AGENT_WORD0 + a]) for a in range(d.A)]
-    for s_ in range(d.D):
-        x, y, c, fl = soa.unpack_dyn0(rec[d.dyn0_word0 + s_])
-        if fl & soa.DYN_ALIVE:
-            ch, ma = bool(fl & soa.DYN_CHOPPED), bool(fl & soa.DYN_MASHED)
-            img[obj0 + 6 * s_:obj0 + 6 * s_ + 6] = [x + d.W - 1, y + soa.LUT_Y0 + d.H - 1, 126 + (not (ch or ma)),
-                                                                  126 + ch, 126 + ma, 127]
-    for c in range(d.C):
-        f = bool(cells[c] & (soa.CELL_ACTIVE | soa.CELL_WALK))
-        img[cell0 + 4 * c:cell0 + 4 * c + 4] = [c % d.W + d.W - 1, c // d.W + soa.LUT_Y0 + d.H - 1, 126 + f, 127]
-    for a in range(d.A):
-        x, y, o, _ = ag[a]
-        img[ag0 + 8 * a:ag0 + 8 * a + 7] = [x + d.W - 1, y + soa.LUT_Y0 + d.H - 1] + [126 + (o == k) for k in (1, 2, 3, 4)] + [127]
-    out = np.zeros((d.A, d.F))
-    for f, w in enumerate(desc):
-        w = int(w)
-        hw, code = (w & 0xFFFF) // 2, (w >> 16) // 4
-        for a in range(d.A):
-            sub = 0
-            if code == soa.AX_X:
-                sub = ag[a][0]
-            elif code == soa.AX_Y:
-                sub = ag[a][1]
-            elif code >= 4 and (code - 4) // 2 != a:
-                sub = ag[a][(code - 4) % 2]
-            out[a, f] = lut[img[hw] - sub]
-    return out
 
 
 def test_c_abi_exports_every_declared_symbol(repo_root):
