@@ -315,6 +315,10 @@ struct cz_handle_s {
     int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
     unsigned long long *d_reset_refused = nullptr;   // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
     unsigned long long *d_restore_refused = nullptr; // cz_restore_device: envs whose slot or row was refused (cz_restore_device_refused)
+    unsigned long long *d_tasks_refused = nullptr;   // cz_set_tasks_device: envs whose new recipe ids were out of range (cz_set_tasks_refused)
+    uint8_t *d_goal = nullptr;             // cz_load_goal_table: [n_goal_rows][GOAL_ROW_NODES] goal ids
+    int n_goal_rows = 0;                   // rows in use (0: none, or dropped by cz_load_recipes)
+    int num_goals = 0;                     // the length of a goal vector
     uint8_t *codes = nullptr;          // cz_set_compact_output: one-step launches also write the compact observation here
     float *obs32 = nullptr;            // cz_set_f32_output: one-step launches called with d_obs = NULL write float32 rows here
     void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
@@ -418,7 +422,7 @@ static int pool_levels(cz_handle h, const uint8_t *level_of, int32_t n_levels, c
 }
 
 // Is the stream this handle's work goes to (a stream of the caller, cz_set_stream) being captured - hipStreamBeginCapture,
-// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*), cz_reset_device, cz_save_device and cz_restore_device are then pure
+// torch.cuda.graph - right now?  The device-pointer steps (cz_step_device, _compact, _f32, _many, _ring, cz_rollout*), cz_reset_device, cz_set_tasks_device, cz_infos_device, cz_save_device and cz_restore_device are then pure
 // kernel launches: nothing that queries or synchronises (a staged layout update stays staged until the first call outside the
 // capture; no graphs of the library's own inside the caller's), so the capture stays valid and replays do what the launches did.
 static bool caller_capturing(cz_handle h) {
@@ -564,6 +568,8 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     CREATE_CHK(hipMemsetAsync(h->d_reset_refused, 0, sizeof(unsigned long long), h->stream));
     CREATE_CHK(hipMalloc(&h->d_restore_refused, sizeof(unsigned long long)));
     CREATE_CHK(hipMemsetAsync(h->d_restore_refused, 0, sizeof(unsigned long long), h->stream));
+    CREATE_CHK(hipMalloc(&h->d_tasks_refused, sizeof(unsigned long long)));
+    CREATE_CHK(hipMemsetAsync(h->d_tasks_refused, 0, sizeof(unsigned long long), h->stream));
     CREATE_CHK(hipMalloc(&h->d_stats_part, (size_t)STAT_CHAINS * 16 * sizeof(unsigned long long)));
     CREATE_CHK(hipStreamSynchronize(h->stream));
     P.state = h->d_state; P.stat_u = h->d_stat_u; P.stat_f = h->d_stat_f;
@@ -631,7 +637,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_tasks_refused, h->d_goal, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -809,6 +815,9 @@ extern "C" int cz_load_recipes(cz_handle h, const uint32_t *table, int32_t n, in
     h->P.recipes = h->d_recipes;
     h->tables_version++;
     h->n_partner = 0;                      // the partner table was built from the book this call replaces: cz_load_partner_table again
+    h->n_goal_rows = 0;                    // ... and so was the goal table: cz_load_goal_table again
+    // (walk_touches and wide, below, are derived from the WHOLE table, not from the recipes some env plays: every id of the table is
+    // valid for every step kernel this handle can select, so cz_set_tasks_device may give any env any of them)
     // Carrying an object from cell to cell changes no co-location (hence no recipe mark) when at most two agents
     // exist (they can never share a cell, cooking_world.py:206-221) and no recipe relates a dynamic-class node to a
     // node of a walkable static class (Floor, Switch, Block) -- the only statics a carried object can be "at".
@@ -1716,6 +1725,77 @@ extern "C" int cz_partner_device(cz_handle h, int64_t b, int64_t c, uint32_t age
     if (set_device(h)) return 1;
     PartnerArgs G{b, agents, h->n_partner, d_recipe, h->d_partner, h->d_lay_rank, partner_counter(h), d_action, d_target, d_status};
     HIPCHK(h, h->kl.partner(h->P, h->stream, (int)c, G));
+    return 0;
+}
+// The goal table: the goal id (RecipeNode.id_num, recipe.py:16) of every node of every recipe of the loaded table, 0xFF past a
+// recipe's last node, and the length of a goal vector (cooking_env.py:100-105 num_goals).  Checks everything k_infos relies on.
+extern "C" int cz_load_goal_table(cz_handle h, const uint8_t *goal_ids, int32_t n, int32_t num_goals) {
+    if (!h || !goal_ids) return fail(h, "cz_load_goal_table: bad arguments");
+    if (n != h->n_recipes || !h->d_recipes) return fail(h, "cz_load_goal_table: %d rows for the %d recipes of the loaded table (cz_load_recipes first)", n, h->n_recipes);
+    if (num_goals < 1 || num_goals > 255) return fail(h, "cz_load_goal_table: num_goals is %d, not in 1..255", num_goals);
+    if (set_device(h)) return 1;
+    if (caller_capturing(h)) return fail(h, "cz_load_goal_table: not inside a stream capture of the caller (it allocates and copies)");
+    // the node counts are the recipe table's (cz_load_recipes keeps them in word 0 of every row)
+    const size_t row_words = h->P.wide ? 1 + 2 * WIDE_NODES : 1 + MAX_NODES;
+    std::vector<uint32_t> rows((size_t)n * row_words);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(rows.data(), h->d_recipes, rows.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        const uint32_t nn = rows[(size_t)i * row_words] & 0xFFu;
+        for (uint32_t j = 0; j < (uint32_t)GOAL_ROW_NODES; ++j) {
+            const uint32_t id = goal_ids[(size_t)i * GOAL_ROW_NODES + j];
+            if (j < nn ? id >= (uint32_t)num_goals : id != 0xFFu)
+                return fail(h, "cz_load_goal_table: recipe %d node %u: goal id %u (a node of the recipe: below num_goals = %d; past its %u nodes: 0xFF)", i, j, id, num_goals, nn);
+        }
+    }
+    if (h->d_goal) { HIPCHK(h, hipFree(h->d_goal)); h->d_goal = nullptr; h->n_goal_rows = 0; }
+    const size_t bytes = (size_t)n * GOAL_ROW_NODES;
+    HIPCHK(h, hipMalloc(&h->d_goal, bytes));
+    HIPCHK(h, hipMemcpyAsync(h->d_goal, goal_ids, bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->n_goal_rows = n;
+    h->num_goals = num_goals;
+    return 0;
+}
+extern "C" int32_t cz_num_goals(cz_handle h) { return h && h->n_goal_rows ? h->num_goals : -1; }
+// New recipes for chosen envs, decided and carried out on the device (k_set_tasks, cz_offstep.h; definition: cooking_zoo_amd/tasks.py
+// host_set_tasks): one launch over the whole batch on the handle's stream - no copy, no query, no wait, no allocation, so it is legal
+// inside a capture of the caller; outside one a staged layout update is flushed as by every device-pointer call.  Not a step and not
+// a reset: t, status, episode, statistics and the last-episode row stay.
+extern "C" int cz_set_tasks_device(cz_handle h, const uint8_t *d_mask, const uint8_t *d_recipe_ids, const uint8_t *d_task_list, int32_t K,
+                                   uint64_t seed) {
+    if (ready(h)) return 1;
+    if (!d_recipe_ids && !d_task_list) return fail(h, "cz_set_tasks_device: neither recipe ids nor a task list");
+    if (!d_recipe_ids && K < 1) return fail(h, "cz_set_tasks_device: a task list of %d rows", K);
+    // (rows are read as words; a list beside an id array is ignored, whatever its address)
+    if ((uintptr_t)(d_recipe_ids ? d_recipe_ids : d_task_list) & 3u) return fail(h, "cz_set_tasks_device: the source of the ids must be 4-byte aligned");
+    if (begin_device_call(h, true, "")) return 1;
+    HIPCHK(h, h->kl.set_tasks(h->P, h->stream, d_mask, reinterpret_cast<const uint32_t *>(d_recipe_ids),
+                              d_recipe_ids ? nullptr : reinterpret_cast<const uint32_t *>(d_task_list), (uint32_t)(K > 0 ? K : 1), seed,
+                              (uint32_t)h->n_recipes, h->d_tasks_refused));
+    return 0;
+}
+// envs that cz_set_tasks_device left alone since cz_create because a new recipe id of a used slot was >= the table's size (waits for the stream); -1 on error
+extern "C" int64_t cz_set_tasks_refused(cz_handle h) {
+    return h ? read_counter<unsigned long long>(h, h->d_tasks_refused, "cz_set_tasks_refused") : -1;
+}
+// The task state on the current records into DEVICE buffers (k_infos, cz_query.h; definition: cooking_zoo_amd/tasks.py host_infos).
+// Stream-ordered, nothing is copied, waited for, queried or allocated (legal inside a stream capture of the caller); the records are
+// only read.
+extern "C" int cz_infos_device(cz_handle h, int64_t b, int64_t c, uint8_t *d_goal8, float *d_goal32, uint8_t *d_recipe_done, int32_t *d_task,
+                               int32_t *d_t) {
+    if (begin_ranged_call(h, b, c)) return 1;
+    if (!h->d_goal || h->n_goal_rows == 0 || h->n_goal_rows != h->n_recipes) return fail(h, "cz_infos_device: no goal table for the loaded recipes (cz_load_goal_table)");
+    if (!d_goal8 && !d_goal32 && !d_recipe_done && !d_task && !d_t) return fail(h, "cz_infos_device: all five output pointers are null");
+    if (((uintptr_t)d_goal32 | (uintptr_t)d_task | (uintptr_t)d_t) & 3u) return fail(h, "cz_infos_device: d_goal32, d_task and d_t must be 4-byte aligned");
+    if (c == 0) return 0;
+    if (set_device(h)) return 1;
+    const InfosArgs G{h->d_state, h->d_recipes, h->d_goal, b, (int32_t)c, h->P.RW, h->P.A, h->num_goals, h->n_recipes,
+                      d_goal8, d_goal32, d_recipe_done, d_task, d_t};
+    const dim3 grid((unsigned)((c + INFOS_WAVES - 1) / INFOS_WAVES)), block(64 * INFOS_WAVES);
+    if (h->P.wide) hipLaunchKernelGGL(k_infos<true>, grid, block, 0, h->stream, G);
+    else hipLaunchKernelGGL(k_infos<false>, grid, block, 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
     return 0;
 }
 // agents that were asked for a recipe index outside the table (they got IDLE) since cz_load_partner_table; -1 on error.  Waits.

@@ -20,6 +20,9 @@ struct Launchers {
     // k_restore_where over all P.N envs: slots, archive, its rows, recipes in the table, float64 rows, float32 rows, codes, refused counter
     hipError_t (*restore_where)(const Params &, hipStream_t, const int32_t *, const uint32_t *, int64_t, uint32_t, double *, float *, uint8_t *,
                                 unsigned long long *);
+    // k_set_tasks over all P.N envs: mask, recipe ids (a word per env), task list (a word per row), its rows, seed, recipes in the table, refused counter
+    hipError_t (*set_tasks)(const Params &, hipStream_t, const uint8_t *, const uint32_t *, const uint32_t *, uint32_t, uint64_t, uint32_t,
+                            unsigned long long *);
     // k_observe_grid: first env, count, extended, then bits, grid8, grid32, agent_xy (any may be null)
     hipError_t (*observe_grid)(const Params &, hipStream_t, int64_t, int, int32_t, uint32_t *, uint8_t *, float *, int32_t *);
     // k_navigate: first env, count, T, flags, targets, then actions, steps, field (any may be null)
@@ -92,6 +95,10 @@ struct Inst {
                                     uint32_t n_recipes, double *obs, float *obs32, uint8_t *codes, unsigned long long *refused) {
         return CZ_LAUNCH_PER_ENV(k_restore_where, P.N, slot, records, capacity, n_recipes, obs, obs32, codes, refused);
     }
+    static hipError_t set_tasks(const Params &P, hipStream_t st, const uint8_t *mask, const uint32_t *ids, const uint32_t *list, uint32_t K,
+                                uint64_t seed, uint32_t n_recipes, unsigned long long *refused) {
+        return CZ_LAUNCH_PER_ENV(k_set_tasks, P.N, mask, ids, list, K, seed, n_recipes, refused);
+    }
     static hipError_t observe_grid(const Params &P, hipStream_t st, int64_t b, int n, int32_t extended, uint32_t *bits, uint8_t *grid8,
                                    float *grid32, int32_t *agent_xy) {
         return CZ_LAUNCH_PER_ENV(k_observe_grid, n, b, extended, bits, grid8, grid32, agent_xy);
@@ -122,7 +129,7 @@ struct Inst {
         Launchers L{};
         L.step = &step; L.reset = &reset; L.observe = &observe; L.has_lean = HAS_LEAN; L.observe_f32 = &observe_f32;
         L.reset_where = &reset_where; L.restore_where = &restore_where; L.observe_grid = &observe_grid; L.navigate = &navigate;
-        L.partner = &partner; L.action_effects = &action_effects; L.render = &render;
+        L.partner = &partner; L.action_effects = &action_effects; L.render = &render; L.set_tasks = &set_tasks;
         return L;
     }
 };

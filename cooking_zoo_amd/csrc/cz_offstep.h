@@ -1,5 +1,6 @@
 // cz_offstep.h -- the kernels that begin or restore an episode or write observation rows outside a step: k_reset, k_observe,
-// k_observe_f32, k_reset_where and k_restore_where, and what they share (init_lut_f32, row_of, write_forms, begin_episode).
+// k_observe_f32, k_reset_where and k_restore_where, and what they share (init_lut_f32, row_of, write_forms, begin_episode); and
+// k_set_tasks, which gives an env other recipes on the world it has.
 // Nothing here is inlined by a step kernel.
 #pragma once
 #include "cz_kernels.h"
@@ -203,6 +204,63 @@ __global__ __launch_bounds__(64) void k_restore_where(const Params P, const int3
     }
     init_lds<CPL>(P, cx, lds);
     write_forms(P, e, cx, lds, lut, lutf, obs_out, obs32_out, codes_out, env);
+}
+
+// The row of a K-row task list that env `env_global` plays in episode `episode` (cooking_zoo_amd/tasks.py task_draw): the keyed
+// stream of the spawn code at t = 0 under an agent key of its own (spawn draws: agents 0..3, the layout generator: 0x100)
+constexpr uint32_t TASK_KEY = 0x200u;
+__host__ __device__ inline uint32_t task_draw(uint64_t seed, int64_t env_global, uint32_t episode, uint32_t K) {
+    const uint32_t k = (uint32_t)(spawn_uniform(seed, (uint64_t)env_global, (uint64_t)episode << 32, TASK_KEY, 0u) * (double)K);
+    return k < K ? k : K - 1u;
+}
+
+// New recipes for CHOSEN envs of the whole batch, everything in device memory (cz_set_tasks_device; definition:
+// cooking_zoo_amd/tasks.py host_set_tasks): lines 197-201 of the reference's reset() applied to fresh graphs of other names on
+// the env's current world.  Env e is chosen when mask[e] != 0 or, without a mask, when its record has t == 0 (the start of an
+// episode).  One wavefront per env and workgroup: the wave of an env that is not chosen leaves behind one load, before anything
+// is staged.  The new ids: row e of `ids` (4 bytes per env) or, without it, row task_draw(seed, global env id, the record's
+// episode, K) of `list` - an index below K by construction.  The bytes of slots >= R are forced to 0xFF; a byte >= n_recipes in
+// one of the first R slots refuses the env BEFORE any of them is an index: it stays word for word as it was, `refused` counts it.
+// Otherwise every recipe's marks are evaluated from scratch (all_marks) and the header words that change are stored: the recipe
+// ids, the marks and, for wide tables, word 7.  No cell, no object, no status word, no statistics.
+template <int OPL, int CPL, int NA>
+__global__ __launch_bounds__(64) void k_set_tasks(const Params P, const uint8_t *__restrict__ mask, const uint32_t *__restrict__ ids,
+                                                  const uint32_t *__restrict__ list, uint32_t K, uint64_t seed, uint32_t n_recipes,
+                                                  unsigned long long *refused) {
+    __shared__ Lds<CPL> lds;
+    const uint32_t env = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    uint32_t *rec = P.state + (size_t)env * P.RW;
+    if (mask) {
+        if (rfl((uint32_t)mask[env]) == 0u) return;
+    } else {
+        if (rfl(rec[W_T]) != 0u) return;
+    }
+    uint32_t want;
+    if (ids) want = rfl(ids[env]);
+    else want = rfl(list[task_draw(seed, P.env_id_base + (int64_t)env, rfl(rec[W_EPISODE]), K)]);
+    bool bad = false;
+    for (int r = 0; r < MAX_AGENTS; ++r) {
+        if (r >= P.R) want |= 0xFFu << (8 * r);
+        else if (((want >> (8 * r)) & 0xFFu) >= n_recipes) bad = true;
+    }
+    if (bad) {                                                       // refused: nothing of the env is touched
+        if (lane == 0) atomicAdd(refused, 1ull);
+        return;
+    }
+    Ctx cx{P.W, P.H, P.D, P.W * P.H, lane};
+    Env<OPL, CPL, NA> e;
+    load_env(P, e, cx, rec);
+    e.recipes = want;
+    const uint32_t rowv = load_recipe_rows(P, e.recipes, lane);
+    all_marks(P, e, cx, rowv, lds);
+    // a header-only store (store_env's header path also writes t, layout, status, episode, the pool word and the agents)
+    uint32_t h = 0;
+    h = wrl(e.marks, W_MARKS, h);
+    h = wrl(e.recipes, W_RECIPES, h);
+    h = wrl(e.marks_hi, W_MARKS_HI, h);
+    const uint32_t ul = (uint32_t)lane;
+    if (ul == W_MARKS || ul == W_RECIPES || (P.wide && ul == W_MARKS_HI)) stg<uint32_t>(rec, ul * 4u, h);
 }
 
 }  // namespace cz

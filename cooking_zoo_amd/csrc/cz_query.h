@@ -1,5 +1,5 @@
-// cz_query.h -- the read-only kernels, their argument blocks and constants: k_observe_grid, k_render, k_navigate, k_partner and
-// k_action_effects.  Each is a pure function of the records (no kernel here writes one); of the step path they use load_env, the
+// cz_query.h -- the read-only kernels, their argument blocks and constants: k_observe_grid, k_render, k_navigate, k_partner,
+// k_action_effects and k_infos.  Each is a pure function of the records (no kernel here writes one); of the step path they use load_env, the
 // constant block's coordinate table and, k_action_effects alone, the world step.
 #pragma once
 #include "cz_kernels.h"
@@ -993,6 +993,71 @@ __global__ __launch_bounds__(64) void k_action_effects(const Params P, const Eff
         if (G.effects) stg<uint8_t>(G.effects + row, lane, (uint8_t)fx);
         if (G.mask) stg<uint8_t>(G.mask + row, lane, (uint8_t)((lane == 0u || (fx & ~G.ignore) != 0u) ? 1u : 0u));
     }
+}
+
+// The task state of every env as tensors (cz_infos_device; definition: cooking_zoo_amd/tasks.py host_infos): what the reference's
+// infos and "full" observation report per agent - goal_vector = recipe_mapping[agent].goals_completed(num_goals) (cooking_env.py:277,
+// recipe.py:36-40), recipe_done and task (cooking_env.py:317-331) - and the env's step counter.  It needs four header words of the
+// record (t, marks, marks-hi, recipe ids), the recipe table's node counts and `counts` bits and the goal table: no load_env, no
+// image, and nothing of the kernel instance - one kernel for all three, by the width of the recipe tables.
+// One wavefront per env, INFOS_WAVES of them per workgroup, no wave talks to another (an idle wave of the last workgroup leaves at
+// once).  Lane 16 a + j stands for node j of the recipe of slot a: the node whose `counts` bit is set is the last of node_list with
+// its goal id (Recipe.flatten) and puts `not marked` at [a][id] of the env's [A][G] row in LDS, which the wave has zeroed before (ids
+// no node carries stay 0; the DS operations of one wave execute in order).  The row then goes out with consecutive lanes on
+// consecutive elements - an env's A * G elements are contiguous in both forms - and lanes a < A write recipe_done and task, lane 0
+// t.  A recipe id outside the table (no record the library let in has one in a used slot) reads as a recipe without nodes.  Plain
+// stores; every element of a written row exactly once; the records are only read.
+constexpr int INFOS_WAVES = 4, GOAL_ROW_NODES = 16, INFOS_ROW_BYTES = 1024;       // (4 agents x at most 255 goals)
+struct InfosArgs {
+    const uint32_t *state;             // [N][RW]
+    const uint32_t *recipes;           // the recipe table of the step kernels (cz_load_recipes)
+    const uint8_t *goal_ids;           // [n_recipes][GOAL_ROW_NODES] (cz_load_goal_table)
+    int64_t env_begin;
+    int32_t count, RW, A, G, n_recipes;
+    uint8_t *goal8;                    // [count][A][G]
+    float *goal32;                     // [count][A][G]
+    uint8_t *done;                     // [count][A]
+    int32_t *task;                     // [count][A]
+    int32_t *t;                        // [count]; any of the five may be null
+};
+template <bool WIDE>
+__global__ __launch_bounds__(64 * INFOS_WAVES) void k_infos(const InfosArgs G) {
+    __shared__ uint8_t rows[INFOS_WAVES][INFOS_ROW_BYTES];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const int64_t i = (int64_t)blockIdx.x * INFOS_WAVES + wave;
+    if (i >= G.count) return;
+    constexpr uint32_t ROW_WORDS = WIDE ? 1u + 2u * WIDE_NODES : 1u + MAX_NODES;
+    const uint32_t *rec = G.state + (size_t)(G.env_begin + i) * G.RW;
+    const uint32_t t = rfl(rec[W_T]), m_lo = rfl(rec[W_MARKS]), m_hi = WIDE ? rfl(rec[W_MARKS_HI]) : 0u, ids = rfl(rec[W_RECIPES]);
+    const uint32_t A = (uint32_t)G.A, NG = (uint32_t)G.G, row_len = A * NG;
+    uint8_t *row = rows[wave];
+    const auto marks_of = [&](uint32_t a) {
+        return WIDE ? ((a < 2u ? m_lo : m_hi) >> (16u * (a & 1u))) & 0xFFFFu : (m_lo >> (8u * a)) & 0xFFu;
+    };
+    for (uint32_t k = lane; k < row_len; k += 64u) row[k] = 0;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    {
+        const uint32_t a = lane >> 4, j = lane & 15u, r = (ids >> (8u * a)) & 0xFFu;
+        if (a < A && r < (uint32_t)G.n_recipes && (WIDE || j < (uint32_t)MAX_NODES)) {     // (before r or j is an index)
+            const uint32_t *rr = G.recipes + (size_t)r * ROW_WORDS;
+            const uint32_t nn = rr[0] & 0xFFu, w = rr[WIDE ? 1u + 2u * j : 1u + j], id = G.goal_ids[r * GOAL_ROW_NODES + j];
+            if (j < nn && ((w >> 8) & 1u) && id < NG) row[a * NG + id] = (uint8_t)(((marks_of(a) >> j) & 1u) ^ 1u);
+        }
+    }
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    const size_t out0 = (size_t)i * row_len;
+    for (uint32_t k = lane; k < row_len; k += 64u) {
+        const uint32_t v = row[k];
+        if (G.goal8) G.goal8[out0 + k] = (uint8_t)v;
+        if (G.goal32) G.goal32[out0 + k] = (float)v;
+    }
+    if (lane < A) {
+        if (G.done) G.done[(size_t)i * A + lane] = (uint8_t)(marks_of(lane) & 1u);
+        if (G.task) G.task[(size_t)i * A + lane] = (int32_t)((ids >> (8u * lane)) & 0xFFu);
+    }
+    if (lane == 0u && G.t) G.t[i] = (int32_t)t;
 }
 
 }  // namespace cz

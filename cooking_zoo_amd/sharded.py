@@ -418,6 +418,49 @@ class ShardedVecEnv:
         """envs `reset_device` refused (explicit layout id past the pool), summed over the local shards"""
         return sum(self._each(lambda i, env: env.reset_device_refused()))
 
+    @property
+    def num_goals(self):
+        """the length of a goal vector (cooking_env.py:100-105)"""
+        return self.shards[0].num_goals
+
+    def set_tasks_device(self, d_mask=None, d_recipe_ids=None, d_task_list=None, seed=0, K=None):
+        """`CookingVecEnv.set_tasks_device` on every shard, one call each.  d_mask (uint8 per env) and d_recipe_ids (uint8 [4] per env):
+        ShardedBuffers, cut along the env axis.  The task list has no env axis: d_task_list is a sequence with one device buffer per
+        local shard, each holding the same uint8 [K, 4] rows (as `collect_episodes` takes its list).  The keyed draws use global env
+        ids: the batch behaves like one handle."""
+        if d_task_list is not None and (isinstance(d_task_list, ShardedBuffer) or not isinstance(d_task_list, (list, tuple))
+                                        or len(d_task_list) != len(self.shards)):
+            raise ValueError(f"set_tasks_device: d_task_list is one device buffer per local shard, a list of {len(self.shards)} (the list "
+                             f"has no env axis to cut), not {type(d_task_list).__name__}")
+        P = self._part
+        self._each(lambda i, env: env.set_tasks_device(P(d_mask, i), P(d_recipe_ids, i), P(d_task_list, i), seed=seed, K=K))
+
+    def set_tasks_refused(self):
+        """envs `set_tasks_device` refused (a recipe id past the table), summed over the local shards"""
+        return sum(self._each(lambda i, env: env.set_tasks_refused()))
+
+    def infos_device(self, d_goal8=None, d_goal32=None, d_recipe_done=None, d_task=None, d_t=None):
+        """`CookingVecEnv.infos_device` on every shard over its part of the ShardedBuffers (per env: goal8 uint8 / goal32 float32
+        [A, num_goals], recipe_done uint8 [A], task int32 [A], t int32 []).  Always every env of every shard: the single handle's
+        `env_begin` / `env_count` have no counterpart here (a range would have to be cut across shards; ask a shard directly)"""
+        P = self._part
+        self._each(lambda i, env: env.infos_device(P(d_goal8, i), P(d_goal32, i), P(d_recipe_done, i), P(d_task, i), P(d_t, i)))
+
+    def set_tasks(self, recipes, mask=None):
+        """`CookingVecEnv.set_tasks` of every shard: `recipes` [R] or [N, R] and `mask` [N] are cut along the env axis; returns the
+        refusals summed"""
+        n = int(self._local_cuts[-1])
+        per_env = np.asarray(recipes, dtype=object).ndim == 2
+        if per_env and len(recipes) != n:
+            raise ValueError(f"set_tasks: recipes has {len(recipes)} rows, the local shards hold {n} envs")
+        rows = (lambda i: list(np.asarray(recipes, dtype=object)[self._local_cuts[i]:self._local_cuts[i + 1]])) if per_env else (lambda i: recipes)
+        return sum(self._each(lambda i, env: env.set_tasks(rows(i), None if mask is None else self._cut(mask, i))))
+
+    def infos(self):
+        """`CookingVecEnv.infos` of every shard, concatenated in global env order"""
+        parts = self._each(lambda i, env: env.infos())
+        return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
     def save_device(self, d_records, d_slot=None):
         """`CookingVecEnv.save_device` on every shard, over its part of the buffers: d_records a ShardedBuffer of uint32 with per-env
         shape (record_words,) - one row per env of the shard - or a list of one archive per shard; d_slot int32 per env.  Slots

@@ -13,7 +13,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, render as _render, rotation as _rotation, soa
+from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, render as _render, rotation as _rotation, soa, tasks as _tasks
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -133,6 +133,12 @@ class BatchTables:
         self.recipe_table = np.stack([g.flatten(self.recipe_nodes) for g in graphs])
         self.recipe_graphs = graphs                                      # the book as it stood when the tables were made
         self.partner_rows = _partner.partner_rows(graphs)               # the scripted partner's view of the same graphs
+        self.num_goals = _tasks.current_num_goals()                     # cooking_env.py:100-105
+        # the goal id of every node (infos_device).  A registry with more than 255 goals (the reference's id counter is process-global
+        # and never goes back: every registered recipe takes fresh ids) has none: a goal id no longer fits the table's byte, so
+        # `infos_device` is refused there (cz_num_goals: -1; `num_goals` stays the reference's number) and everything else works.
+        # A node id outside [0, num_goals) is a malformed book and raises here, as the reference does when the Recipe is made.
+        self.goal_table = _tasks.goal_table(graphs, self.num_goals) if self.num_goals <= _tasks.MAX_GOALS else None
         if isinstance(recipes, np.ndarray):
             rid = np.asarray(recipes, dtype=np.int64)
             assert rid.shape[0] == self.num_envs
@@ -240,6 +246,9 @@ class CookingVecEnv:
         assert L.cz_record_words(self._h) == self.dims.RW
         _native.check(self._h, L.cz_load_recipes(self._h, _ptr(self.recipe_table), len(self.book_names), self.recipe_nodes))
         _native.check(self._h, L.cz_load_partner_table(self._h, _ptr(self.partner_rows), len(self.book_names)))
+        # (no table: goal ids beyond a byte, or a library built before the task calls - CZ_LIB in an A/B run; the rest works without)
+        if self.goal_table is not None and _native.has("cz_load_goal_table"):
+            _native.check(self._h, L.cz_load_goal_table(self._h, _ptr(self.goal_table), len(self.book_names), self.num_goals))
         self._upload_layouts()
         self._buffers = []
         self._ep_bufs = None                  # finished_episodes: the packed list and the count
@@ -708,13 +717,15 @@ class CookingVecEnv:
             self.navigate_device(d_t, d_a, d_s, walkable_blocks=walkable_blocks, env_begin=env_begin, env_count=n)
             return d_a.to_host(), d_s.to_host()
 
-    def _recipe_indices(self, recipes, n):
-        """recipe names or table indices, one per agent or [n, A] -> int32 [n, A] indices into the loaded recipe table"""
+    def _recipe_indices(self, recipes, n, width=None):
+        """recipe names or table indices, one per agent or [n, A] -> int32 [n, A] indices into the loaded recipe table (`width`: per
+        recipe slot, [R] or [n, R], instead)"""
+        width = self.num_agents if width is None else int(width)
         flat = [self.book_names.index(r) if isinstance(r, str) else int(r) for r in np.asarray(recipes, dtype=object).reshape(-1)]
         idx = np.asarray(flat, dtype=np.int32)
-        if idx.size == self.num_agents:
+        if idx.size == width:
             idx = np.tile(idx, (n, 1))
-        return np.ascontiguousarray(idx.reshape(n, self.num_agents))
+        return np.ascontiguousarray(idx.reshape(n, width))
 
     def partner_device(self, d_action=None, d_target=None, d_status=None, agents=None, d_recipe=None, env_begin=0, env_count=None):
         """the scripted partner on the current state - the action the reference's heuristic `CookingAgent` returns
@@ -841,6 +852,73 @@ class CookingVecEnv:
         if n < 0:
             _native.check(self._h, 1)
         return n
+
+    # ------------------------------------------------------------------ tasks (cooking_zoo_amd/tasks.py)
+    def set_tasks_device(self, d_mask=None, d_recipe_ids=None, d_task_list=None, seed=0, K=None):
+        """New recipes for chosen envs, decided on the device: lines 197-201 of the reference's `reset()` applied to fresh graphs of
+        other names on the env's current world (cooking_zoo_amd/tasks.py `host_set_tasks`).  One launch on the env's stream, no copy
+        and no wait, legal inside a capture; not a step and not a reset.  d_mask uint8 [N]: env e is chosen when d_mask[e] != 0, in
+        mid-episode or finished; None: every env whose record has t == 0 (the start of an episode: after `reset`, `reset_device` or
+        the auto-reset pass).  d_recipe_ids uint8 [N, 4]: row e holds the new ids (indices into `book_names`; the bytes of slots >=
+        num_recipes are ignored); None: row `tasks.task_draw(seed, env_id_base + e, the env's episode, K)` of d_task_list uint8 [K, 4]
+        - keyed by the episode, so calling it after every step changes nothing until an env starts its next episode.  K is the list's
+        leading dimension where the buffer has a shape, else `K=`.  An id past the recipe table in a used slot is refused: the env
+        stays as it was, `set_tasks_refused` counts it.  Word 5 of the record and the marks change, nothing else.
+        `self.recipe_ids` does NOT follow: the device owns the truth, `get_state()[:, soa.W_RECIPES]` and `infos_device(d_task=)`
+        read it."""
+        if K is None:
+            shape = tuple(getattr(d_task_list, "shape", ()))
+            K = shape[0] if shape else 0
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_set_tasks_device(self._h, p(d_mask), p(d_recipe_ids), p(d_task_list), int(K), int(seed)))
+
+    def set_tasks_refused(self):
+        """envs `set_tasks_device` left alone because a new recipe id was past the recipe table, since the env was created (waits)"""
+        n = int(_native.lib().cz_set_tasks_refused(self._h))
+        if n < 0:
+            _native.check(self._h, 1)
+        return n
+
+    def infos_device(self, d_goal8=None, d_goal32=None, d_recipe_done=None, d_task=None, d_t=None, env_begin=0, env_count=None):
+        """the task state of the current records - what the reference's `infos` and `"full"` observation report per agent
+        (cooking_zoo_amd/tasks.py `host_infos`) - into device buffers, stream-ordered and capturable: `d_goal8` uint8 [n, A, num_goals]
+        and / or `d_goal32` float32 [n, A, num_goals] (`goal_vector` of the agent's recipe: `torch.cat([obs32, goal32], -1)` is a
+        task-conditioned policy's input), `d_recipe_done` uint8 [n, A], `d_task` int32 [n, A] (indices into `book_names`), `d_t` int32
+        [n]; at least one of them.  The records are only read."""
+        n = self._count(env_count)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_infos_device(self._h, env_begin, n, p(d_goal8), p(d_goal32), p(d_recipe_done), p(d_task), p(d_t)))
+
+    def set_tasks(self, recipes, mask=None):
+        """host convenience: `recipes` - names or indices into `book_names`, [R] (every chosen env the same) or [N, R] - become the
+        recipes of the envs where `mask` [N] is nonzero (None: all of them), wherever they are in their episodes; `self.recipe_ids`
+        follows.  Returns how many envs were refused (an index past the table); those keep their recipes, here as on the device."""
+        N, R = self.num_envs, self.num_recipes
+        ids = np.full((N, 4), 0xFF, dtype=np.uint8)
+        idx = self._recipe_indices(recipes, N, R)
+        if ((idx < 0) | (idx > 0xFF)).any():
+            raise ValueError("set_tasks: a recipe index outside 0..255")
+        ids[:, :R] = idx
+        chosen = np.ones(N, np.uint8) if mask is None else (np.asarray(mask).reshape(N) != 0).astype(np.uint8)
+        before = self.set_tasks_refused()
+        with self._scratch(((N,), np.uint8, chosen), ((N, 4), np.uint8, ids)) as (d_mask, d_ids):
+            self.set_tasks_device(d_mask, d_ids)
+            refused = self.set_tasks_refused() - before
+        ok = (chosen != 0) & (idx < len(self.book_names)).all(axis=1)
+        self.recipe_ids = self.recipe_ids.copy()
+        self.recipe_ids[ok] = ids[ok]
+        return refused
+
+    def infos(self, env_begin=0, env_count=None):
+        """host convenience: {"goal_vector": uint8 [n, A, num_goals], "recipe_done": uint8 [n, A], "task": int32 [n, A], "t": int32 [n]}
+        of envs [env_begin, env_begin + n)"""
+        n, A, G = self._count(env_count), self.num_agents, self.num_goals
+        if n == 0:
+            return {"goal_vector": np.zeros((0, A, G), np.uint8), "recipe_done": np.zeros((0, A), np.uint8),
+                    "task": np.zeros((0, A), np.int32), "t": np.zeros((0,), np.int32)}
+        with self._scratch(((n, A, G), np.uint8), ((n, A), np.uint8), ((n, A), np.int32), ((n,), np.int32)) as (d_g, d_d, d_k, d_t):
+            self.infos_device(d_goal8=d_g, d_recipe_done=d_d, d_task=d_k, d_t=d_t, env_begin=env_begin, env_count=n)
+            return {"goal_vector": d_g.to_host(), "recipe_done": d_d.to_host(), "task": d_k.to_host(), "t": d_t.to_host()}
 
     @staticmethod
     def _archive_rows(d_records, capacity):

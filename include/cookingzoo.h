@@ -117,7 +117,7 @@ int cz_sync(cz_handle h);                                  /* wait for the handl
 int cz_set_stream(cz_handle h, void *hip_stream);
 /* STREAM CAPTURE.  While that stream is being captured by the caller (hipStreamBeginCapture, torch.cuda.graph), the
  * device-pointer calls - cz_step_device, cz_step_device_compact, cz_step_device_f32, cz_step_device_many / _ring, cz_rollout*,
- * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_action_effects_device, cz_render_device, cz_reset_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
+ * cz_observe_device, cz_observe_device_f32, cz_observe_grid_device, cz_navigate_device, cz_partner_device, cz_action_effects_device, cz_render_device, cz_reset_device, cz_set_tasks_device, cz_infos_device, cz_save_device, cz_restore_device, cz_episodes_collect, cz_probe_policy - are pure kernel launches and legal inside the capture: nothing is queried or synchronised (a layout update
  * staged by cz_update_layouts stays staged until the first call outside the capture; ring runs go out as plain launches).  Replays
  * of the caller's graph then do exactly what the captured launches did (cooking_env.py:243-288 once per captured step).  Calls
  * that copy to / from the host or wait (cz_step, cz_reset, cz_get_state, cz_sync, cz_get_stats, cz_update_layouts,
@@ -400,6 +400,56 @@ int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t n_recipes);
  * as for cz_update_layouts - only for slots that no env plays on or can draw (nothing checks this).  The wait is put on the stream
  * the handle has at the time of the call: after a later cz_set_stream, cz_sync (or a wait of your own) before the next cz_partner_device. */
 int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, const uint16_t *ranks);
+
+/* TASKS: which recipes an env plays, changed and read on the device.  The reference fixes them in the constructor and rebuilds their
+ * graphs at every reset() (cooking_env.py:197-201); its infos carry recipe_done and task per agent (cooking_env.py:317-331) and the
+ * "full" observation goal_vector = recipe_mapping[agent].goals_completed(num_goals) (cooking_env.py:277, recipe.py:36-40).
+ * cooking_zoo_amd/tasks.py is the definition and the host model of both calls.
+ *
+ * cz_load_goal_table: goal_ids uint8 [n_recipes][16] - the goal id (RecipeNode.id_num, recipe.py:16) of node j of recipe r, 0xFF past
+ *   the recipe's last node - and num_goals, the length of a goal vector (1..255; cooking_env.py:100-105).  n_recipes must be the
+ *   loaded recipe table's; an id of a node must be < num_goals (the reference raises IndexError there, recipe.py:34).  After every
+ *   cz_load_recipes, which drops the table; not inside a capture.  cz_num_goals: num_goals, -1 before a table is loaded / null handle.
+ *
+ * cz_set_tasks_device: lines 197-201 of reset() applied to fresh graphs of OTHER names on the env's current world, for chosen envs.
+ *   d_mask        uint8 [N] or NULL   env e is chosen when d_mask[e] != 0, in mid-episode or finished (a finished env's status word is
+ *                                     not touched: it stays done until it is reset).  NULL: every env whose record has t == 0 - the
+ *                                     start of an episode, after cz_reset, cz_reset_device or the auto-reset pass; a finished env has
+ *                                     t >= 1 and is never chosen this way.
+ *   d_recipe_ids  uint8 [N][4]        the new ids of env e: row e.  NULL: row task_draw(seed, env_id_base + e, the record's episode
+ *   d_task_list   uint8 [K][4]        word, K) = min((int)(u * K), K - 1) of d_task_list, u = cz_spawn_uniform(seed, env_id_base + e,
+ *                                     episode, 0, 0x200, 0): the project's one counter-based stream under a key nobody else uses
+ *                                     (spawn draws: agents 0..3, cz_generate_layouts: 0x100).  Keyed by the episode word, so calling
+ *                                     it after every step is idempotent, with auto_reset = 1 and 0 alike.
+ *   A chosen env: record word 5 becomes the new ids (the bytes of slots >= num_recipes are ignored and stored as 0xFF), every recipe's
+ *   marks are evaluated from scratch on the current world (word 1, and word 7 for wide tables); everything else in the record - t,
+ *   status, episode, pool word, running returns, cells, objects - stays byte for byte, no statistics change, and the last-episode
+ *   row of cz_episodes_collect is left alone.  Any id of the table is valid for every step kernel the handle can select: what
+ *   cz_load_recipes derives for them it derives from the whole table.  An id >= n_recipes in one of the first num_recipes slots is
+ *   checked on the device before it is used: the env is refused - it stays word for word as it was - and cz_set_tasks_refused
+ *   counts it (envs refused since cz_create; waits for the stream; -1 on error).
+ *   Refused on the host, before anything is launched: both sources NULL, a list with K < 1, the source in use not 4-byte aligned
+ *   (with an id array the list is ignored, whatever it is).
+ *   One launch on the handle's stream: no copy, no query, no wait, no allocation - legal inside a stream capture of the caller;
+ *   outside one a layout update staged by cz_update_layouts is flushed first, as by cz_reset_device and every device-pointer call.
+ *
+ * cz_infos_device: the task state of envs [env_begin, env_begin + env_count) on the current records, any subset of five outputs
+ *   (not none):
+ *   d_goal8       uint8 [n][A][G]     G = num_goals.  The goal vector of agent a is that of recipe slot a (recipe_mapping,
+ *   d_goal32      float [n][A][G]     cooking_env.py:201): [id] = 1 while the LAST node of node_list that carries goal id `id` is
+ *                                     not marked, 0 once it is, and 0 for ids no node of the recipe carries; float: 0.0 / 1.0
+ *   d_recipe_done uint8 [n][A]        the root's mark (infos[agent]["recipe_done"])
+ *   d_task        int32 [n][A]        the recipe's index in the loaded table (infos[agent]["task"] names it)
+ *   d_t           int32 [n]           the record's step counter
+ *   Refused: no goal table for the loaded recipes, all five NULL, a range outside the batch.  env_count == 0 returns 0.  One launch:
+ *   no copy, no query, no wait, no allocation - legal inside a stream capture of the caller; the records are only read. */
+int cz_load_goal_table(cz_handle h, const uint8_t *goal_ids, int32_t n_recipes, int32_t num_goals);
+int32_t cz_num_goals(cz_handle h);
+int cz_set_tasks_device(cz_handle h, const uint8_t *d_mask, const uint8_t *d_recipe_ids, const uint8_t *d_task_list, int32_t K,
+                        uint64_t seed);
+int64_t cz_set_tasks_refused(cz_handle h);
+int cz_infos_device(cz_handle h, int64_t env_begin, int64_t env_count, uint8_t *d_goal8, float *d_goal32, uint8_t *d_recipe_done,
+                    int32_t *d_task, int32_t *d_t);
 
 /* ACTION EFFECTS AND MASKS: which of an agent's actions would do anything at all, from the current records (the PettingZoo
  * `action_mask` convention; the reference offers none).  cooking_zoo_amd/effects.py is the definition and the host model.
