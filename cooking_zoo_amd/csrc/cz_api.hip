@@ -334,12 +334,13 @@ struct cz_handle_s {
     struct RingKey {
         const int32_t *ring = nullptr; int64_t stride = 0; int32_t period = 0;
         double *obs = nullptr, *rew = nullptr; uint8_t *term = nullptr, *trunc = nullptr; hipStream_t stream = nullptr; uint64_t version = 0;
+        int32_t parts = 1;             // launch chains per run (cz_set_ring_split)
         bool operator==(const RingKey &o) const {
             return ring == o.ring && stride == o.stride && period == o.period && obs == o.obs && rew == o.rew && term == o.term &&
-                   trunc == o.trunc && stream == o.stream && version == o.version;
+                   trunc == o.trunc && stream == o.stream && version == o.version && parts == o.parts;
         }
     } ring_key;
-    struct RunGraph { int32_t slot, len; hipGraphExec_t ge; uint64_t used; };
+    struct RunGraph { int32_t slot, len; hipGraphExec_t ge, ge2; uint64_t used; };   // ge2: the second chain of a split run, or null
     std::vector<RunGraph> ring_graphs;             // replayable runs of this ring, keyed by (first slot, length)
     uint64_t ring_clock = 0;
     int64_t n_graph_kernels = 0, n_direct_kernels = 0;
@@ -371,6 +372,10 @@ struct cz_handle_s {
     int64_t n_ring_fused_steps = 0;
     int32_t graph_min_run = 48;    // CZ_GRAPH_MIN_RUN: shorter pieces of a ring run are launched directly (see ring_walk)
     int32_t ring_prefix = 0;       // CZ_RING_PREFIX: steps of a cz_step_device_ring call launched directly in front of its first graph
+    int32_t ring_split = -1;       // cz_set_ring_split / CZ_RING_SPLIT: -1 automatic, 0 off, 2 two launch chains (run_split)
+    bool few_queues = false;       // GPU_MAX_HW_QUEUES below 4 in the environment of cz_create: runs are never split
+    hipStream_t split_stream = nullptr;            // the second chain of a split run (made by its first one)
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     size_t zero_copy_bytes = (size_t)256 << 10;   // cz_step: batches whose buffers fit use the pinned device-mapped block (CZ_ZERO_COPY_BYTES)
     cz_stats *d_gather = nullptr;
     std::string err;
@@ -534,7 +539,10 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     if (const char *s = getenv("CZ_GRAPH_MIN_RUN")) h->graph_min_run = atoi(s) < 4 ? 4 : (atoi(s) > 256 ? 256 : atoi(s));   // 4..RING_MAX_GRAPH
     if (const char *s = getenv("CZ_RING_PREFIX")) h->ring_prefix = atoi(s) < 0 ? 0 : (atoi(s) > 16 ? 16 : atoi(s));
     if (const char *s = getenv("CZ_ZERO_COPY_BYTES")) h->zero_copy_bytes = (size_t)atoll(s);
-#ifdef CZ_SMALL_ONLY       // diagnostic libraries that carry the small instance only
+    if (const char *s = getenv("CZ_RING_SPLIT")) h->ring_split = atoi(s) == 2 ? 2 : atoi(s) == 0 ? 0 : -1;
+    // (read, never set: with fewer than 4 hardware queues the runtime can crash replaying a graph that has parallel branches)
+    if (const char *s = getenv("GPU_MAX_HW_QUEUES")) h->few_queues = atoi(s) < 4;
+#ifdef CZ_SMALL_ONLY      // diagnostic libraries that carry the small instance only
     if (!(P.D <= 64 && C <= 64)) { fail(nullptr, "cz_create: this diagnostic library holds the small kernel instance only"); cz_destroy(h); return 1; }
     h->kl = launchers_small();
 #else
@@ -641,8 +649,10 @@ extern "C" int cz_destroy(cz_handle h) {
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
-    for (auto &r : h->ring_graphs)
+    for (auto &r : h->ring_graphs) {
         if (r.ge) (void)hipGraphExecDestroy(r.ge);
+        if (r.ge2) (void)hipGraphExecDestroy(r.ge2);
+    }
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->ev_copy_done) (void)hipEventDestroy(h->ev_copy_done);
     if (h->ev_steps_issued) (void)hipEventDestroy(h->ev_steps_issued);
@@ -650,6 +660,9 @@ extern "C" int cz_destroy(cz_handle h) {
     if (h->h_lay_stage) (void)hipHostFree(h->h_lay_stage);
     if (h->rank_stream) { (void)hipStreamSynchronize(h->rank_stream); (void)hipStreamDestroy(h->rank_stream); }
     if (h->ev_rank_done) (void)hipEventDestroy(h->ev_rank_done);
+    if (h->split_stream) { (void)hipStreamSynchronize(h->split_stream); (void)hipStreamDestroy(h->split_stream); }
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->h_rank_stage) (void)hipHostFree(h->h_rank_stage);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_small) (void)hipHostFree(h->h_small);
@@ -1294,7 +1307,40 @@ static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm 
     return !fused && !P.actions ? hipErrorInvalidValue : hipSuccess;
 }
 
-static int launch_step(cz_handle h, const StepCall &call) {
+// The Params of envs [begin, begin + count) of a resolved one-step launch: N = count, the global env ids start `begin` later, and
+// every array a one-step kernel indexes by env - records, actions, the outputs in the launch's `form`, marks, statistics - starts
+// `begin` rows of its own row size later (a null pointer stays null).  Everything decided on the whole call's N - P.wt, the kernel
+// (choose_step) - is decided before this.  `begin` may be any env index: a part's last workgroup may be partial, as a launch's may.
+static Params sub_range(const Params &P, ObsForm form, int32_t begin, int32_t count) {
+    Params Q = P;
+    const size_t b = (size_t)begin, row = (size_t)P.A * (size_t)P.F;
+    Q.N = count;
+    Q.env_id_base = P.env_id_base + begin;
+    Q.state = P.state + b * (size_t)P.RW;
+    if (P.actions) Q.actions = P.actions + b * (size_t)P.A;
+    if (P.obs) Q.obs = P.obs + b * row;
+    if (P.rewards) Q.rewards = P.rewards + b * (size_t)P.A;
+    if (P.term) Q.term = P.term + b * (size_t)P.A;
+    if (P.trunc) Q.trunc = P.trunc + b * (size_t)P.A;
+    if (P.marks_out) Q.marks_out = P.marks_out + b * 2;
+    if (form == OBS_F32) Q.obs32 = P.obs32 + b * row;
+    else if (P.codes) Q.codes = P.codes + b * (size_t)P.A * (size_t)codes_pitch(P.F);
+    Q.stat_u = P.stat_u + b * SU_WORDS;
+    Q.stat_f = P.stat_f + b * SF_WORDS;
+#ifdef CZ_PROFILE
+    if (P.stamps) Q.stamps = P.stamps + b * 16;
+#endif
+#ifdef CZ_TIMELINE
+    if (P.timeline) Q.timeline = P.timeline + b * 2;
+#endif
+    return Q;
+}
+
+// A run of one-step launches as two launch chains (cz_set_ring_split): where part 1 begins and the stream its launches go to.
+// launch_step with a RunSplit issues the step's two launches, part 0 on the handle's stream; the run's fork and join are the caller's.
+struct RunSplit { int32_t begin1; hipStream_t side; int only = -1; };   // only: 0 / 1 - that part's launch alone (its graph's capture)
+
+static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split = nullptr) {
     if ((h->P.auto_reset & 2) && h->spawn_layouts != h->n_layouts)
         return fail(h, "despawn / respawn is on, but the layout pool was reloaded since cz_set_spawn (now %d layouts): call cz_set_spawn "
                        "again (it maps every layout to the level whose spawn areas it uses)", h->n_layouts);
@@ -1346,7 +1392,10 @@ static int launch_step(cz_handle h, const StepCall &call) {
     h->last_step_mode = choice.mode;
     h->last_step_variant = !choice.lean ? -1 : choice.cfg < 0 ? 0 : (0x100 | P.R | (P.end_all << 4) | (P.walk_touches << 5));
     HIPCHK(h, chosen);
-    HIPCHK(h, h->kl.step(P, stream, choice));
+    if (split && !fused) {
+        if (split->only != 1) HIPCHK(h, h->kl.step(sub_range(P, form, 0, split->begin1), stream, choice));
+        if (split->only != 0) HIPCHK(h, h->kl.step(sub_range(P, form, split->begin1, P.N - split->begin1), split->side, choice));
+    } else HIPCHK(h, h->kl.step(P, stream, choice));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -1862,6 +1911,79 @@ extern "C" const void *cz_obs_table_device(cz_handle h) { return h ? (const void
 
 static bool ring_fusable(cz_handle h, const StepCall &c, int32_t K, int64_t stride);
 static int launch_ring_fused(cz_handle h, const StepCall &c, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot);
+
+// SPLIT RUNS (cz_set_ring_split).  A run of one-step launches - cz_step_device_ring, cz_step_device_many - goes out as two launch
+// chains over the two halves of the batch, part 0 on the handle's stream and part 1 on a second stream of the handle's: one half
+// computes while the other is in its kernel boundary, its ramp or its first round trip to the records.  Envs never interact and every
+// array a step touches is indexed by env, so each part is an ordinary launch over its envs (sub_range) and the results are those of
+// the whole launches.  The chains are ordered by their streams alone: the second stream waits for an event of the first in front of
+// the run (fork) and the first for an event of the second behind it (join) - one fork and join per graph replay or directly launched
+// piece, none per step; no wave waits on memory another launch writes.
+// A replayed piece is TWO linear graphs, one per chain and stream, between a fork and a join issued with the replay - not one graph
+// with two branches: this runtime replays a graph that forks inside at 6.2-7.5 us per step of 4096 envs, against 5.2-5.3 us for the
+// unsplit graph and for the two linear ones (profiles/r28/README.md).
+// Automatic mode splits the batch sizes at which the split cleared the project's rule - its slowest run faster than the unsplit run's
+// fastest, alternated in fresh processes - in the size sweep of profiles/r28/README.md: 4096 to 32768 envs; 1024 and 2048 lose 6 %, and
+// nothing above 32768 was measured.  Small instance only: no other was measured.
+constexpr int32_t RING_SPLIT_MIN_N = 4096, RING_SPLIT_MAX_N = 32768;
+// Which pieces of a run go out as two chains now.  Never split: a run inside a stream capture of the caller (`capturing`), with kernel
+// timing on, as fused launches (those never get here), of fewer than two envs, or in a process whose environment holds the runtime
+// to fewer than 4 hardware queues.  Mode 2 splits the replayed and the directly launched pieces.  Automatic mode splits the replayed
+// ones only: launched directly the host issues two launches per step, and a 20-step region of 4096 envs took 7.0-10.2 us per step
+// against 6.1-6.4 us unsplit (8192 envs: 10.3-22.2 against 10.3-10.8, profiles/r28/README.md).
+enum : int { SPLIT_GRAPHS = 1, SPLIT_DIRECT = 2 };
+static int run_split(cz_handle h, bool capturing) {
+    if (h->ring_split == 0 || capturing || h->ktime || h->few_queues || h->P.N < 2) return 0;
+    if (h->ring_split == 2) return SPLIT_GRAPHS | SPLIT_DIRECT;
+    return h->instance == 0 && h->P.N >= RING_SPLIT_MIN_N && h->P.N <= RING_SPLIT_MAX_N ? SPLIT_GRAPHS : 0;
+}
+// Part 1 begins at ceil(N / 2), rounded up to whole workgroups where that leaves it an env.  Makes the second stream on first use.
+static int split_begin(cz_handle h, RunSplit &s) {
+    const int32_t N = h->P.N, epw = h->instance == 2 ? envs_per_wg<16>() : envs_per_wg<1>(), half = (N + 1) / 2;
+    const int32_t whole = (half + epw - 1) / epw * epw;
+    s.begin1 = whole < N ? whole : half;
+    if (!h->split_stream) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+    }
+    s.side = h->split_stream;
+    return 0;
+}
+static int split_fork(cz_handle h) {
+    HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->split_stream, h->ev_fork, 0));
+    return 0;
+}
+static int split_join(cz_handle h) {
+    HIPCHK(h, hipEventRecord(h->ev_join, h->split_stream));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    return 0;
+}
+// The phase offset of a replayed split run: the first node of the second chain's graph, one wave that sleeps a fixed time and touches
+// no memory.  Chains of equal period that start together stay in phase - both halves idle and compute at the same moments -, and how
+// far apart they start decides how their live windows interleave for the whole replay: 12 sleeps took 4096 envs from 5.16-5.24 to
+// 5.10-5.16 us per step and 6144 envs from 6.42-6.59 to 6.19-6.27, and left 8192 where it was; 20 to 80 sleeps gave the gain back
+// (profiles/r28/README.md).
+#ifndef CZ_RING_DELAY_SLEEPS
+#define CZ_RING_DELAY_SLEEPS 12
+#endif
+__global__ __launch_bounds__(64) void k_ring_delay() {
+#pragma unroll
+    for (int i = 0; i < CZ_RING_DELAY_SLEEPS; ++i) __builtin_amdgcn_s_sleep(16);
+}
+// launches `count` steps over slots [slot, slot + count) directly, as one chain or as two between a fork and a join
+static int launch_slots(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t count, const RunSplit *split) {
+    if (count < 1) return 0;
+    if (split && split_fork(h)) return 1;
+    int bad = 0;
+    for (int32_t j = 0; j < count && !bad; ++j) {
+        c.actions = d_ring + (int64_t)(slot + j) * stride;
+        bad = launch_step(h, c, split);
+    }
+    if (split && split_join(h)) return 1;        // (also behind a failed launch: what did go to the second stream is joined)
+    return bad;
+}
 // K consecutive steps, one launch each, issued from C: step k reads actions d_actions + k * action_stride (int32 units,
 // wrapping every `action_period` steps) and overwrites the same output buffers.  Same work as K cz_step_device calls
 // without K trips through the host language.
@@ -1870,11 +1992,16 @@ extern "C" int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_acti
     if (begin_device_call(h, d_actions && K >= 1 && action_period >= 1, "cz_step_device_many: bad arguments")) return 1;
     StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
     if (ring_fusable(h, c, K, action_stride)) return launch_ring_fused(h, c, K, d_actions, action_stride, action_period, 0);   // cz_set_ring_fused
-    for (int32_t k = 0; k < K; ++k) {
+    RunSplit split;
+    const bool two = (run_split(h, caller_capturing(h)) & SPLIT_DIRECT) != 0;
+    if (two && (split_begin(h, split) || split_fork(h))) return 1;
+    int bad = 0;
+    for (int32_t k = 0; k < K && !bad; ++k) {
         c.actions = d_actions + (int64_t)(k % action_period) * action_stride;
-        if (launch_step(h, c)) return 1;
+        bad = launch_step(h, c, two ? &split : nullptr);
     }
-    return 0;
+    if (two && split_join(h)) return 1;
+    return bad;
 }
 
 // The same K launches for callers that keep their actions in a ring of `period` slots (slot s at d_ring + s * stride):
@@ -1886,16 +2013,21 @@ extern "C" int cz_step_device_many(cz_handle h, int32_t K, const int32_t *d_acti
 // most RING_CACHE graphs are kept (least recently used goes first), so a caller that keeps asking for new (slot, length)
 // pairs pays a capture each time -- keep the runs of a loop aligned.  Results are identical to cz_step_device_many.
 constexpr int RING_MAX_GRAPH = 256, RING_CACHE = 64;   // (rocprofv3 --kernel-trace aborts on replays of ~1000 kernel nodes: malformed AQL packet)
-// captures the launches of slots [slot, slot + len) (nothing executes) and instantiates them
-static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &ge) {
+// captures the launches of slots [slot, slot + len) on stream `on` (nothing executes) and instantiates them: the whole launches
+// (part < 0), or one chain of a split run - part 0 on the handle's stream, part 1 on the second stream, behind the phase offset
+static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipStream_t on,
+                        const RunSplit *split, int part, hipGraphExec_t &ge) {
+    RunSplit one;
+    if (split) { one = *split; one.only = part; }
     hipGraph_t g = nullptr;
-    HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    HIPCHK(h, hipStreamBeginCapture(on, hipStreamCaptureModeThreadLocal));
+    if (part == 1 && CZ_RING_DELAY_SLEEPS > 0) hipLaunchKernelGGL(k_ring_delay, dim3(1), dim3(64), 0, on);
     int bad = 0;
     for (int s = 0; s < len && !bad; ++s) {
         c.actions = d_ring + (int64_t)(slot + s) * stride;
-        bad = launch_step(h, c);
+        bad = launch_step(h, c, split ? &one : nullptr);
     }
-    const hipError_t ec = hipStreamEndCapture(h->stream, &g);
+    const hipError_t ec = hipStreamEndCapture(on, &g);
     if (bad) { if (g) (void)hipGraphDestroy(g); return 1; }
     HIPCHK(h, ec);
     const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
@@ -1903,38 +2035,47 @@ static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t
     if (ei != hipSuccess) { ge = nullptr; HIPCHK(h, ei); }
     return 0;
 }
+// drops every cached graph (waits for the ones still executing: a split replay ends joined onto the handle's stream)
+static void ring_drop(cz_handle h) {
+    if (!h->ring_graphs.empty()) (void)hipStreamSynchronize(h->stream);
+    for (auto &r : h->ring_graphs) {
+        if (r.ge) (void)hipGraphExecDestroy(r.ge);
+        if (r.ge2) (void)hipGraphExecDestroy(r.ge2);
+    }
+    h->ring_graphs.clear();
+}
 static bool ring_select(cz_handle h, const int32_t *d_ring, int64_t stride, int32_t period, double *d_obs, double *d_rewards,
-                        uint8_t *d_term, uint8_t *d_trunc) {
+                        uint8_t *d_term, uint8_t *d_trunc, int32_t parts) {
     if (h->ktime || !h->graphs_enabled) return false;
     cz_handle_s::RingKey key;
     key.ring = d_ring; key.stride = stride; key.period = period; key.obs = d_obs; key.rew = d_rewards; key.term = d_term;
-    key.trunc = d_trunc; key.stream = h->stream; key.version = h->tables_version;
-    if (!(key == h->ring_key)) {                   // another ring, other output buffers or new tables: every graph is stale
-        if (!h->ring_graphs.empty()) (void)hipStreamSynchronize(h->stream);
-        for (auto &r : h->ring_graphs)
-            if (r.ge) (void)hipGraphExecDestroy(r.ge);
-        h->ring_graphs.clear();
+    key.trunc = d_trunc; key.stream = h->stream; key.version = h->tables_version; key.parts = parts;
+    if (!(key == h->ring_key)) {                   // another ring, other output buffers, new tables or another split: every graph is stale
+        ring_drop(h);
         h->ring_key = key;
     }
     return true;
 }
-// the graph of run [slot, slot + len), captured on first use
-static int ring_graph(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipGraphExec_t &out) {
+// the graph of run [slot, slot + len) - of a split run: the graphs of its two chains -, captured on first use
+static int ring_graph(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, const RunSplit *split,
+                      hipGraphExec_t &out, hipGraphExec_t &out2) {
     h->ring_clock++;
     for (auto &r : h->ring_graphs)
-        if (r.slot == slot && r.len == len) { r.used = h->ring_clock; out = r.ge; return 0; }
+        if (r.slot == slot && r.len == len) { r.used = h->ring_clock; out = r.ge; out2 = r.ge2; return 0; }
     if ((int)h->ring_graphs.size() >= RING_CACHE) {
         size_t victim = 0;
         for (size_t i = 1; i < h->ring_graphs.size(); ++i)
             if (h->ring_graphs[i].used < h->ring_graphs[victim].used) victim = i;
         HIPCHK(h, hipStreamSynchronize(h->stream));            // it may still be executing
         (void)hipGraphExecDestroy(h->ring_graphs[victim].ge);
+        if (h->ring_graphs[victim].ge2) (void)hipGraphExecDestroy(h->ring_graphs[victim].ge2);
         h->ring_graphs.erase(h->ring_graphs.begin() + (long)victim);
     }
-    hipGraphExec_t ge = nullptr;
-    if (ring_capture(h, c, d_ring, stride, slot, len, ge)) return 1;
-    h->ring_graphs.push_back({slot, len, ge, h->ring_clock});
-    out = ge;
+    hipGraphExec_t ge = nullptr, ge2 = nullptr;
+    if (ring_capture(h, c, d_ring, stride, slot, len, h->stream, split, split ? 0 : -1, ge)) return 1;
+    if (split && ring_capture(h, c, d_ring, stride, slot, len, split->side, split, 1, ge2)) { (void)hipGraphExecDestroy(ge); return 1; }
+    h->ring_graphs.push_back({slot, len, ge, ge2, h->ring_clock});
+    out = ge; out2 = ge2;
     return 0;
 }
 // cz_set_ring_fused: the run as fused launches over the ring's own action rows (cz_rollout_actions' kernel, every step's outputs
@@ -1971,7 +2112,12 @@ static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stri
     StepCall c{d_ring, d_obs, d_rewards, d_term, d_trunc};
     if (ring_fusable(h, c, K, stride)) return launch ? launch_ring_fused(h, c, K, d_ring, stride, period, first_slot) : 0;
     // (inside a capture of the caller: plain launches - a capture of the library's own cannot nest in it)
-    const bool graphs = !caller_capturing(h) && ring_select(h, d_ring, stride, period, d_obs, d_rewards, d_term, d_trunc);
+    const bool capturing = caller_capturing(h);
+    RunSplit two;
+    const int parts = run_split(h, capturing);
+    const RunSplit *const split = parts & SPLIT_GRAPHS ? &two : nullptr, *const split_direct = parts & SPLIT_DIRECT ? &two : nullptr;
+    if (parts && split_begin(h, two)) return 1;
+    const bool graphs = !capturing && ring_select(h, d_ring, stride, period, d_obs, d_rewards, d_term, d_trunc, split ? 2 : 1);
     int32_t k = 0;
     while (k < K) {
         const int32_t slot = (int32_t)(((int64_t)first_slot + k) % period);
@@ -1986,22 +2132,21 @@ static int ring_walk(cz_handle h, int32_t K, const int32_t *d_ring, int64_t stri
         // while the host submits the graph of the rest behind them.
         const int32_t pre = k == 0 ? h->ring_prefix : 0;
         if (graphs && run >= h->graph_min_run + pre) {
-            hipGraphExec_t ge = nullptr;
-            if (ring_graph(h, c, d_ring, stride, slot + pre, run - pre, ge)) return 1;
+            hipGraphExec_t ge = nullptr, ge2 = nullptr;
+            if (ring_graph(h, c, d_ring, stride, slot + pre, run - pre, split, ge, ge2)) return 1;
             if (launch) {
-                for (int32_t j = 0; j < pre; ++j) {
-                    c.actions = d_ring + (int64_t)(slot + j) * stride;
-                    if (launch_step(h, c)) return 1;
-                }
+                if (launch_slots(h, c, d_ring, stride, slot, pre, split_direct)) return 1;
+                if (ge2 && split_fork(h)) return 1;
                 HIPCHK(h, hipGraphLaunch(ge, h->stream));
+                if (ge2) {
+                    HIPCHK(h, hipGraphLaunch(ge2, h->split_stream));
+                    if (split_join(h)) return 1;
+                }
                 h->n_graph_kernels += run - pre;
                 h->n_direct_kernels += pre;
             }
         } else if (launch) {
-            for (int32_t j = 0; j < run; ++j) {
-                c.actions = d_ring + (int64_t)(slot + j) * stride;
-                if (launch_step(h, c)) return 1;
-            }
+            if (launch_slots(h, c, d_ring, stride, slot, run, split_direct)) return 1;
             h->n_direct_kernels += run;
         }
         k += run;
@@ -2032,6 +2177,25 @@ extern "C" int cz_set_ring_fused(cz_handle h, int32_t enabled) {
     h->ring_fused = enabled != 0;
     return was;
 }
+// Split runs (see run_split): -1 automatic (the default), 0 off, 2 two launch chains; anything else is refused.  Drops the cached ring
+// graphs.  Returns the previous mode, -2 on error.
+extern "C" int cz_set_ring_split(cz_handle h, int32_t mode) {
+    if (!h) { fail(nullptr, "null handle"); return -2; }
+    if (mode != -1 && mode != 0 && mode != 2) { fail(h, "cz_set_ring_split: mode %d is none of -1 (automatic), 0 (off), 2 (two parts)", mode); return -2; }
+    const int was = h->ring_split;
+    if (mode != was && !caller_capturing(h)) {
+        if (hipSetDevice(h->cfg.device_id) != hipSuccess) { fail(h, "cz_set_ring_split: hipSetDevice failed"); return -2; }
+        ring_drop(h);
+    }
+    h->ring_split = mode;
+    h->tables_version++;
+    return was;
+}
+// in how many launch chains the replayed pieces of a run of this handle go out as things stand (1 or 2; a run inside a capture of the
+// caller: always 1)
+extern "C" int32_t cz_ring_split_parts(cz_handle h) { return h ? (run_split(h, false) ? 2 : 1) : 0; }
+// how many ring graphs the handle holds (tests: what a setting dropped)
+extern "C" int32_t cz_diag_ring_graphs(cz_handle h) { return h ? (int32_t)h->ring_graphs.size() : 0; }
 extern "C" int64_t cz_ring_fused_steps(cz_handle h, int32_t reset) {
     if (!h) return 0;
     const int64_t n = h->n_ring_fused_steps;

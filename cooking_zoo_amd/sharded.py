@@ -534,6 +534,9 @@ class ShardedVecEnv:
     def set_ring_fused(self, enabled=True):
         return self._each(lambda i, env: env.set_ring_fused(enabled))[0]
 
+    def set_ring_split(self, mode=-1):
+        return self._each(lambda i, env: env.set_ring_split(mode))[0]
+
     def rollout(self, T, seed, step0=0, d_obs=None, d_rewards=None, d_term=None, d_trunc=None):
         P = self._part
         self._each(lambda i, env: env.rollout(T, seed, step0, P(d_obs, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))

@@ -810,6 +810,20 @@ class CookingVecEnv:
     def ring_fused_steps(self, reset=False):
         return int(_native.lib().cz_ring_fused_steps(self._h, 1 if reset else 0))
 
+    def set_ring_split(self, mode=-1):
+        """Runs of `step_device_ring` / `step_device_many` as two launch chains over the two halves of the batch, on two streams of
+        the handle (cz_set_ring_split): -1 automatic (the default: the replayed pieces of the batch sizes at which it measured
+        faster), 0 off, 2 two parts whatever the size, directly launched pieces included.  Results are bit for bit those of the
+        unsplit run.  Drops the ring graphs built so far.  Returns the previous mode."""
+        rc = _native.lib().cz_set_ring_split(self._h, int(mode))
+        if rc < -1:
+            raise _native.NativeError((_native.lib().cz_last_error(self._h) or b"cz_set_ring_split failed").decode())
+        return int(rc)
+
+    def ring_split_parts(self):
+        """in how many launch chains (1 or 2) a run outside a stream capture of the caller goes out as things stand"""
+        return int(_native.lib().cz_ring_split_parts(self._h))
+
     def set_stream(self, stream=None):
         """Order this env's device work on the caller's HIP stream: an int / ctypes pointer, or an object with a
         `cuda_stream` attribute such as torch.cuda.current_stream().  None = the env's own stream."""

@@ -608,6 +608,21 @@ int cz_ring_prepare(cz_handle h, int32_t K, const int32_t *d_ring, int64_t actio
 int cz_set_ring_fused(cz_handle h, int32_t enabled);
 int64_t cz_ring_fused_steps(cz_handle h, int32_t reset);
 
+/* SPLIT RUNS.  A run of one-step launches of cz_step_device_ring / _many can go out as two launch chains over the two halves of the
+ * batch - envs [0, ceil(N / 2)) rounded up to whole workgroups, and the rest -, part 0 on the handle's stream and part 1 on a
+ * second stream of the handle's, forked from and joined onto the handle's stream once per graph replay or directly launched piece:
+ * one half computes while the other sits in its kernel boundary.  A replayed piece is two linear graphs, one per chain; the second
+ * one starts behind a short fixed delay that keeps the chains out of phase.  Envs never interact, so state, outputs, statistics and
+ * cz_launch_counts (which keeps counting steps) are bit for bit those of the unsplit run.  mode: -1 automatic (the default: the
+ * replayed pieces of the batch sizes at which the split measured faster, DESIGN.md "Ring runs"; directly launched pieces stay
+ * whole), 0 off, 2 two parts, replayed and directly launched pieces alike; CZ_RING_SPLIT in the environment of cz_create sets
+ * the initial mode.  Never split, whatever the mode: a run inside a stream capture of the caller, with kernel timing on, as fused
+ * launches (cz_set_ring_fused), of fewer than 2 envs, and any run of a process whose environment sets GPU_MAX_HW_QUEUES below 4
+ * (the variable is only read).  Drops the ring graphs built so far.  Returns the previous mode, -2 on error.
+ * cz_ring_split_parts: in how many chains (1 or 2) the replayed pieces of a run outside a capture go out as things stand. */
+int cz_set_ring_split(cz_handle h, int32_t mode);
+int32_t cz_ring_split_parts(cz_handle h);
+
 /* How many step kernels cz_step_device_ring has replayed from graphs / launched directly on this handle so far
  * (reset != 0: zero both after reading).  bench.py describes its run from these numbers.  Fused ring runs (cz_set_ring_fused) are
  * not in either count: cz_ring_fused_steps has theirs. */
