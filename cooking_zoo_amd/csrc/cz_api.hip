@@ -282,6 +282,8 @@ struct cz_handle_s {
     uint16_t *h_rank_stage = nullptr;      // pinned staging of cz_load_layout_ranks, a place per slot
     hipStream_t rank_stream = nullptr;     // its copies run here; the handle's stream waits for them on the device
     hipEvent_t ev_rank_done = nullptr;
+    float *d_policy = nullptr;             // cz_load_policy_device: POLICY_MAX_SETS packed weight sets (cz_policy.h), allocated on the first load
+    int32_t n_policy_sets = 0;             // sets the last load filled; 0: no table
     uint32_t *d_partner = nullptr;         // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
     int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
     int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
@@ -645,7 +647,7 @@ extern "C" int cz_destroy(cz_handle h) {
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_tasks_refused, h->d_goal, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
+    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_tasks_refused, h->d_goal, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_policy, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
                     h->d_actions, h->d_obs, h->d_small, h->d_gather};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -1257,6 +1259,9 @@ struct StepCall {
     uint32_t *marks = nullptr;     // every env's recipe marks (the host step)
     bool fused = false;            // T steps in one launch (the rollouts, fused ring runs); seed and step0 are theirs as well
     int32_t T = 1; uint64_t seed = 0; uint32_t step0 = 0;
+    // cz_rollout_policy (fused, float32 only): the packed sets and mode (policy_pack_sets), and the two outputs of its own - `actions`
+    // above stays null, the launch plays no actions of the caller
+    bool policy = false; uint32_t policy_packed = 0; int32_t *actions_out = nullptr; float *logits_out = nullptr;
 };
 enum ObsForm { OBS_F64, OBS_CODES, OBS_F32 };      // what a launch writes its observation as (OBS_CODES: float64 rows beside the codes if P.obs)
 
@@ -1278,10 +1283,17 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
     P.actions = c.actions; P.obs = c.obs; P.rewards = c.rewards; P.term = c.term; P.trunc = c.trunc; P.marks_out = c.marks;
     P.T = c.T; P.seed = c.seed; P.step0 = c.step0;
     if (obs32) P.obs32 = obs32; else P.codes = codes;
+    if (c.policy) {
+        // ROLLOUT_POLICY reads three slots no float32 fused launch uses (StepTraits::policy): the block must not grow
+        P.actions = c.actions_out;
+        P.obs = reinterpret_cast<double *>(c.logits_out);
+        P.marks_out = reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(h->d_policy) | ((uintptr_t)c.policy_packed << 48));
+    }
     return nullptr;
 }
 
 // Which kernel a launch gets (the same table is in DESIGN.md section 4).  `form` is resolve_step's; P.wt is decided by then.
+//   fused, OBS_F32, a policy call     -> ROLLOUT_POLICY       (cz_rollout_policy)
 //   fused, OBS_F32 and P.actions      -> ROLLOUT_ACTIONS_F32  (cz_rollout_actions_f32)
 //   fused, OBS_F32                    -> ROLLOUT_F32          (cz_rollout_f32)
 //   fused, P.actions                  -> ROLLOUT_ACTIONS      (cz_rollout_actions, fused rings)
@@ -1294,9 +1306,13 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 //                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
 //                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
 //   one step without P.actions        -> hipErrorInvalidValue
-static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c) {
+static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c, bool policy = false) {
     c.lean = false;
     c.cfg = -1;
+    if (policy) {
+        c.mode = ROLLOUT_POLICY;
+        return fused && form == OBS_F32 ? hipSuccess : hipErrorInvalidValue;
+    }
     if (fused && form == OBS_F32) c.mode = P.actions ? ROLLOUT_ACTIONS_F32 : ROLLOUT_F32;
     else if (fused) c.mode = P.actions ? ROLLOUT_ACTIONS : form != OBS_CODES ? ROLLOUT : P.obs ? ROLLOUT_CODES : ROLLOUT_CODES_ONLY;
     else c.mode = form == OBS_F32 ? STEP_F32 : form == OBS_CODES ? STEP_CODES : STEP;
@@ -1387,7 +1403,7 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
         HIPCHK(h, hipEventRecord(e0, stream));
     }
     StepChoice choice;
-    const hipError_t chosen = choose_step(h, P, fused, form, choice);
+    const hipError_t chosen = choose_step(h, P, fused, form, choice, call.policy);
     h->last_step_lean = choice.lean ? 1 : 0;
     h->last_step_mode = choice.mode;
     h->last_step_variant = !choice.lean ? -1 : choice.cfg < 0 ? 0 : (0x100 | P.R | (P.end_all << 4) | (P.walk_touches << 5));
@@ -2262,6 +2278,82 @@ extern "C" int cz_rollout_actions_f32(cz_handle h, int32_t T, const int32_t *d_a
                           "cz_rollout_actions_f32", T)) return 1;
     StepCall c{d_actions, nullptr, d_rewards, d_term, d_trunc};
     c.obs32 = d_obs32; c.fused = true; c.T = T;
+    return launch_step(h, c);
+}
+
+// ---- the MLP policy (definition: cooking_zoo_amd/policy.py; device code: cz_policy.h, k_policy / k_policy_pack in cz_query.h)
+// Loads n_sets weight sets from DEVICE memory in torch.nn.Linear's layouts - W1 float32 [n][64][F], b1 [n][64], W2 [n][C][64], b2 [n][C],
+// F the handle's row length and C = cz_num_actions - with one repack launch on the handle's stream.  The table (room for 4 sets) is
+// allocated by the handle's first call and never again: every later call is stream-ordered work only and legal inside a capture.
+// F and C are fixed by cz_create, so neither cz_load_layouts nor cz_load_recipes drops the table.
+extern "C" int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2) {
+    if (!h) return fail(nullptr, "null handle");
+    if (n_sets < 1 || n_sets > POLICY_MAX_SETS) return fail(h, "cz_load_policy_device: n_sets is %d, not 1..%d", n_sets, POLICY_MAX_SETS);
+    if (!d_w1 || !d_b1 || !d_w2 || !d_b2) return fail(h, "cz_load_policy_device: a weight pointer is null");
+    if (set_device(h)) return 1;
+    const size_t per_set = policy_set_floats(h->P.F);
+    if (!h->d_policy) {
+        if (caller_capturing(h)) return fail(h, "cz_load_policy_device: the handle's first load allocates the table: call it once outside the capture");
+        HIPCHK(h, hipMalloc(&h->d_policy, per_set * POLICY_MAX_SETS * sizeof(float)));
+        if (reinterpret_cast<uintptr_t>(h->d_policy) >> 48) return fail(h, "cz_load_policy_device: device address above 2^48");
+    }
+    const uint32_t total = (uint32_t)(per_set * (size_t)n_sets);
+    hipLaunchKernelGGL((k_policy_pack<0>), dim3((total + 255u) / 256u), dim3(256), 0, h->stream, h->d_policy, n_sets, h->P.F, cz_num_actions(h),
+                       d_w1, d_b1, d_w2, d_b2);
+    HIPCHK(h, hipGetLastError());
+    h->n_policy_sets = n_sets;
+    return 0;
+}
+extern "C" int32_t cz_policy_sets(cz_handle h) { return h ? h->n_policy_sets : -1; }
+// `sets` and `mode` of a policy call, checked: the packed form, or -1 after fail()
+static int64_t check_policy_call(cz_handle h, const char *who, uint32_t sets, int32_t mode, bool need_one) {
+    if (!h->d_policy || h->n_policy_sets == 0) { fail(h, "%s: no weight table loaded (cz_load_policy_device)", who); return -1; }
+    if (mode != (int32_t)POLICY_GREEDY && mode != (int32_t)POLICY_SAMPLE) { fail(h, "%s: mode is %d, not CZ_POLICY_GREEDY (0) or CZ_POLICY_SAMPLE (1)", who, mode); return -1; }
+    int with_set = 0;
+    for (int a = 0; a < h->P.A; ++a) {
+        const uint32_t s = (sets >> (8 * a)) & 0xFFu;
+        if (s == POLICY_NONE) continue;
+        if (s >= (uint32_t)h->n_policy_sets) { fail(h, "%s: agent %d asks for weight set %u, but %d are loaded", who, a, s, h->n_policy_sets); return -1; }
+        ++with_set;
+    }
+    if (need_one && with_set == 0) { fail(h, "%s: every agent's set is 0xFF (that is cz_rollout_f32)", who); return -1; }
+    return (int64_t)policy_pack_sets(sets, (uint32_t)mode, h->P.A);
+}
+// The policy on rows of the caller: d_obs32 float32 [env_count][A][F] -> d_actions int32 [env_count][A] and / or d_logits float32
+// [env_count][A][C].  `sets`: agent a's weight set in byte a, 0xFF = none - that agent's entries are left untouched in both outputs.
+// `step` keys the draw of CZ_POLICY_SAMPLE, spawn_uniform(seed, global env id, step, 0x300 + a, 0).  One launch of k_policy on the
+// handle's stream: nothing is copied, waited for or allocated (legal inside a stream capture of the caller); no record is touched.
+extern "C" int cz_policy_device(cz_handle h, int64_t b, int64_t c, const float *d_obs32, uint32_t sets, int32_t mode, uint64_t seed, uint32_t step,
+                                int32_t *d_actions, float *d_logits) {
+    if (begin_ranged_call(h, b, c)) return 1;
+    const int64_t packed = check_policy_call(h, "cz_policy_device", sets, mode, false);
+    if (packed < 0) return 1;
+    if (c == 0) return 0;
+    if (!d_obs32) return fail(h, "cz_policy_device: the rows pointer is null");
+    if (!d_actions && !d_logits) return fail(h, "cz_policy_device: both output pointers are null");
+    if (set_device(h)) return 1;
+    const int A = h->P.A, F = h->P.F;
+    const size_t rows = (size_t)A * (size_t)policy_quads(F) * 16u;
+    PolicyArgs G{h->P.env_id_base + b, d_obs32, h->d_policy, F, cz_num_actions(h), (uint32_t)packed, step, seed, d_actions, d_logits};
+    HIPCHK(h, with_agents(A, [&](auto na) {
+        hipLaunchKernelGGL((k_policy<decltype(na)::value>), dim3((unsigned)c), dim3(64), rows, h->stream, G);
+        return hipGetLastError();
+    }));
+    return 0;
+}
+// cz_rollout_f32 with the policy in front of every fused step (k_step<..., ROLLOUT_POLICY>): agent a's action at step t is the policy's on
+// the env's float32 row before that step - for t = 0 what cz_observe_device_f32 would write at launch, later row t - 1 of the trajectory,
+// the row of a reset pass included - with the draw keyed by step0 + t; agents whose byte of `sets` is 0xFF play cz_rollout's stream,
+// cz_action(seed, env, a, step0 + t).  d_obs32 float32 [T][N][A][F] is required; d_actions int32 [T][N][A] (every agent's action as
+// played) and d_logits float32 [T][N][A][C] (policy agents only) are optional; the rest is cz_rollout_actions_f32 over those actions.
+extern "C" int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t mode, uint64_t seed, uint32_t step0, float *d_obs32, int32_t *d_actions,
+                                 float *d_logits, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
+    if (begin_device_call(h, T >= 1 && d_obs32, "cz_rollout_policy: T must be >= 1 and the float32 trajectory pointer non-null", "cz_rollout_policy", T)) return 1;
+    const int64_t packed = check_policy_call(h, "cz_rollout_policy", sets, mode, true);
+    if (packed < 0) return 1;
+    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
+    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
     return launch_step(h, c);
 }
 

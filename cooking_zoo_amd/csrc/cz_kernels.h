@@ -2,6 +2,7 @@
 // cz_launch.h build on it; the per-size instantiation units include the last).
 #pragma once
 #include "cz_device.h"
+#include "cz_policy.h"
 #include <type_traits>
 
 namespace cz {
@@ -66,12 +67,14 @@ enum StepMode : int {
                               // the observation (cz_rollout_f32)
     ROLLOUT_ACTIONS_F32 = 8,  // the same over the caller's actions [t][env][agent] (cz_rollout_actions_f32): its own instance for the reason
                               // ROLLOUT_ACTIONS is one; always writes row t (the in-place form of fused ring runs is not offered in float32)
+    ROLLOUT_POLICY = 9,       // ROLLOUT_F32 whose actions are the MLP policy's (cz_policy.h) on the env's float32 row before the step, staged
+                              // in LDS next to its store (cz_rollout_policy): agents without a weight set play the on-device stream
 };
 template <int MODE, bool LEAN = false>
 struct StepTraits {
-    static_assert(MODE >= STEP && MODE <= ROLLOUT_ACTIONS_F32 && (!LEAN || MODE == STEP), "no such variant");
+    static_assert(MODE >= STEP && MODE <= ROLLOUT_POLICY && (!LEAN || MODE == STEP), "no such variant");
     static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY ||
-                                  MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32;   // P.T steps per launch
+                                  MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY;   // P.T steps per launch
     static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_ACTIONS_F32;   // a fused launch that reads the caller's actions
     static constexpr bool codes = MODE == STEP_CODES || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // writes the compact observation
     // a fused rollout that writes codes ONLY (cz_rollout_compact without a float64 trajectory).  Without the float64 path - its six
@@ -80,7 +83,11 @@ struct StepTraits {
     static constexpr bool codes_only = MODE == ROLLOUT_CODES_ONLY;
     // the float32 rows: np.float32 of the float64 feature (round to nearest even), gathered from a float32 copy of the table that the
     // workgroup makes while it stages the table into LDS - no arithmetic on values, no float64 path beside it
-    static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32;
+    static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY;
+    // the policy in front of every fused step.  A float32 fused launch leaves three slots of the argument block unused, and the block must
+    // not grow: `actions` carries the int32 [T][N][A] actions OUTPUT, `obs` the float [T][N][A][C] logits output (either may be null) and
+    // `marks_out` the weight table with policy_pack_sets in the 16 bits above a device address (resolve_step in cz_api.hip puts them there)
+    static constexpr bool policy = MODE == ROLLOUT_POLICY;
     static constexpr bool f64 = !codes_only && !f32;                                     // carries the float64 observation path
     // The CodesPrefetch words (the b128 descriptor loads of the codes and of the float32 rows): fetched once behind the prologue and held
     // in registers - a fused launch fetches them again only when a reset pass has moved the env to another layout - or, desc_per_step,
@@ -426,9 +433,11 @@ __device__ __forceinline__ void build_image(const PB &P, const Env<OPL, CPL, NA>
 // is no padding.  P.wt selects the stores' cache policy as in observe.
 // (The descriptor / image / subtrahend gather is spelled out here and in observe's codes loop: moved into one helper of both, 32 of the
 // small instance's 76 instruction streams change and k_observe grows by 46 to 78 instructions.)
-template <int OPL, int CPL, int NA>
+// STAGE (ROLLOUT_POLICY): 1 = every value also goes to `xrow`, the env's rows in LDS the policy reads (NA rows of 4 * policy_quads(F) floats,
+// zero behind F) - the registers that feed the store, nothing is read back from memory; 2 = to `xrow` only (the row before step 0)
+template <int OPL, int CPL, int NA, int STAGE = 0>
 __device__ __forceinline__ void write_rows_f32(const Params &P, const Env<OPL, CPL, NA> &e, const Ctx &cx, Lds<CPL> &s, const float *lut,
-                                               float *__restrict__ out32 /* [A][F] of this env */, CodesPrefetch *pre) {
+                                               float *__restrict__ out32 /* [A][F] of this env */, CodesPrefetch *pre, float *xrow = nullptr) {
     const char *lutb = reinterpret_cast<const char *>(lut);
     const char *imgb = reinterpret_cast<const char *>(s.img);
     const char *subb = reinterpret_cast<const char *>(s.sub);
@@ -436,7 +445,7 @@ __device__ __forceinline__ void write_rows_f32(const Params &P, const Env<OPL, C
     // (a row starts wherever the rows before it end: 4-byte aligned when F is odd.  Buffer stores of several dwords need dword
     // alignment only, and the range check works dword by dword - what the float64 rows of an odd F, 8-byte aligned, rely on too)
 #pragma unroll
-    for (int a = 0; a < NA; ++a) r32[a] = __builtin_amdgcn_make_buffer_rsrc(out32 + (size_t)a * (uint32_t)P.F, 0, P.F * 4, 0x00020000);
+    for (int a = 0; a < NA; ++a) r32[a] = __builtin_amdgcn_make_buffer_rsrc(out32 + (size_t)a * (uint32_t)P.F, 0, STAGE == 2 ? 0 : P.F * 4, 0x00020000);
     const uint32_t wt = (uint32_t)P.wt;                                              // wave-uniform
     for (int f0 = 0; f0 < P.F; f0 += 256) {
         const uint32_t f = (uint32_t)f0 + 4u * (uint32_t)cx.lane;                       // this lane's first feature
@@ -461,6 +470,18 @@ __device__ __forceinline__ void write_rows_f32(const Params &P, const Env<OPL, C
             for (int k = 0; k < 4; ++k) w[k] = *reinterpret_cast<const uint32_t *>(lutb + (((int)b[k] - sb[a][k]) >> 1));
             v[a].x = w[0]; v[a].y = w[1]; v[a].z = w[2]; v[a].w = w[3];
         }
+        if constexpr (STAGE != 0) {
+            const uint32_t F4 = 4u * (uint32_t)policy_quads(P.F), left = (uint32_t)P.F - f;       // (left: meaningful where f < F4)
+            if (f < F4) {
+#pragma unroll
+                for (int a = 0; a < NA; ++a) {
+                    uint4_t z = v[a];
+                    z.y = left > 1u ? z.y : 0u; z.z = left > 2u ? z.z : 0u; z.w = left > 3u ? z.w : 0u;
+                    *reinterpret_cast<uint4_t *>(xrow + (uint32_t)a * F4 + f) = z;
+                }
+            }
+        }
+        if constexpr (STAGE == 2) continue;
 #define CZ_OBS_WRITE_ROWS32(AUX)                                                                                             \
     _Pragma("unroll") for (int a = 0; a < NA; ++a) __builtin_amdgcn_raw_buffer_store_b128(v[a], r32[a], f * 4u, 0, AUX)
         if (wt == 1u) { CZ_OBS_WRITE_ROWS32(16); }          // sc1: write-through
@@ -873,6 +894,15 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         for (int r = 0; r < CODES_PREFETCH; ++r) cpre.d[r] = load_desc4(P, e.layout, 256u * r + 4u * (uint32_t)lane);
     }
 
+    // ROLLOUT_POLICY: this env's rows in LDS, and the row before step 0 - what cz_observe_device_f32 would write now - staged into them
+    float *xrow = nullptr;
+    if constexpr (V::policy) {
+        xrow = reinterpret_cast<float *>(policy_rows) + (uint32_t)wave * (uint32_t)(NA * 4 * policy_quads(P.F));
+        build_image<OPL, CPL, NA>(P, e, cx, lds, submask, true, true);
+        write_rows_f32<OPL, CPL, NA, 2>(P, e, cx, lds, lutf, nullptr, &cpre, xrow);
+        img_objs = false; img_cells = false;
+    }
+
     const int T = V::fused ? P.T : 1;
 #ifdef CZ_TIMELINE
     uint32_t tl_dbg = 0u;
@@ -912,6 +942,31 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             // (cz_rollout_actions checks that T * N * A * 4 fits 32 bits; the last step re-reads its own row)
             av = ldg<int>(e_actions, act_lane + (uint32_t)min(t + 1, T - 1) * ((uint32_t)Pt.N * (uint32_t)NA * 4u));
         } else acts = action_hash(Pt.seed, env_global, lane & 3, Pt.step0 + (uint32_t)t, SCHEME == 3 ? 5u : 8u);
+        if constexpr (V::policy) {
+            // agents with a weight set: the policy on the row in LDS - row t - 1 of the trajectory, whatever wrote it, or the row before
+            // step 0 - in place of the stream's action; every agent's action as played and the policy agents' logits go to row t
+            constexpr int C = SCHEME == 3 ? 5 : 8;
+            const uint64_t slot = (uint64_t)reinterpret_cast<uintptr_t>(Pt.marks_out);
+            const float *const table = reinterpret_cast<const float *>(static_cast<uintptr_t>(slot & 0xFFFFFFFFFFFFull));
+            const uint32_t pk = (uint32_t)(slot >> 48);
+            const size_t prow = (size_t)t * (size_t)Pt.N + (size_t)env;
+            float *const lrow = Pt.obs ? reinterpret_cast<float *>(Pt.obs) + prow * (size_t)(NA * C) : nullptr;
+            const int Fq = policy_quads(Pt.F);
+#pragma unroll
+            for (int a = 0; a < NA; ++a) {
+                const uint32_t si = (pk >> (3 * a)) & 7u;
+                if (si != 7u) {
+                    int action;
+                    float mylogit;
+                    policy_act<C>(table + (size_t)si * policy_set_floats(Pt.F), Fq, xrow + (uint32_t)(a * 4 * Fq), lane, (pk >> 12) & 1u, Pt.seed,
+                                  env_global, Pt.step0 + (uint32_t)t, a, action, mylogit);
+                    acts = lane == a ? (uint32_t)action : acts;
+                    if (lrow && lane < C) lrow[a * C + lane] = mylogit;
+                }
+            }
+            // (cz_rollout_policy checks that T * N * A * 8 fits 32 bits)
+            if (e_actions && lane < NA) stg<int32_t>(const_cast<int32_t *>(e_actions), ((uint32_t)prow * (uint32_t)NA + (uint32_t)lane) * 4u, (int32_t)acts);
+        }
         Dirty dt{};
         StepOut o;
         step_env<OPL, CPL, NA, SCHEME, V::fused, V::lean>(Pt, block_offset<typename V::Block>(), e, cx, acts, env_global, rowv, lds, dsc, dt, o);
@@ -985,7 +1040,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             // float[T][N][A][F], a 64-bit product like the float64 trajectory's, and the image is rebuilt where the step changed it)
             float *const obs_row = Pt.obs32 + (uint64_t)(uint32_t)row * (uint64_t)(uint32_t)(NA * Pt.F);
             build_image<OPL, CPL, NA>(Pt, e, cx, lds, submask, img_objs, img_cells);
-            write_rows_f32<OPL, CPL, NA>(Pt, e, cx, lds, lutf, obs_row, &cpre);
+            write_rows_f32<OPL, CPL, NA, V::policy ? 1 : 0>(Pt, e, cx, lds, lutf, obs_row, &cpre, xrow);
             if (V::fused) { img_objs = false; img_cells = false; }
         } else if (V::lean || Pt.obs || V::codes) {
             // (env row x row length: a 32 x 32 -> 64-bit product, two scalar multiplies)
@@ -1124,14 +1179,32 @@ inline hipError_t with_scheme(int scheme, F &&f) {
 // one launch of a step kernel: one wavefront per env, the leading scalar arguments spelled out for the preload (Early)
 // (`block`: the kernel's by-value block - P itself, or its lean block)
 template <int CPL, class K, class B>
-inline hipError_t launch_step_kernel(K kernel, const Params &P, const B &block_arg, hipStream_t st) {
+inline hipError_t launch_step_kernel(K kernel, const Params &P, const B &block_arg, hipStream_t st, size_t dynamic_lds = 0) {
     constexpr int EPW = envs_per_wg<CPL>();
     const dim3 grid((unsigned)((P.N + EPW - 1) / EPW)), block(64 * EPW);
     const Early E = early_of(P);
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, block_arg);
+    hipLaunchKernelGGL(kernel, grid, block, dynamic_lds, st, E.state, E.actions, E.lut, E.N, E.RW, E.W, E.H, E.D, E.dyn0_off, E.dyn1_off, block_arg);
     return hipGetLastError();
 }
 template <int CPL, class K>
 inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) { return launch_step_kernel<CPL>(kernel, P, P, st); }
+// ROLLOUT_POLICY: the workgroup's policy rows (cz_policy.h) are dynamic LDS, sized by the handle's F - A rows of 4 * policy_quads(F)
+// floats per env - next to the kernel's static LDS; more than the default limit of a launch is asked for by name
+constexpr size_t LDS_PER_WORKGROUP = 160u << 10;
+template <int CPL>
+inline size_t policy_rows_bytes(const Params &P) { return (size_t)envs_per_wg<CPL>() * (size_t)P.A * (size_t)policy_quads(P.F) * 16u; }
+template <int CPL, class K>
+inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream_t st) {
+    const size_t rows = policy_rows_bytes<CPL>(P);
+    hipFuncAttributes attr;
+    hipError_t err = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
+    if (err != hipSuccess) return err;
+    if (attr.sharedSizeBytes + rows > LDS_PER_WORKGROUP) return hipErrorInvalidValue;
+    if (attr.sharedSizeBytes + rows > (48u << 10)) {
+        err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows);
+        if (err != hipSuccess) return err;
+    }
+    return launch_step_kernel<CPL>(kernel, P, P, st, rows);
+}
 
 }  // namespace cz

@@ -66,6 +66,7 @@ struct Inst {
                 case STEP_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_F32>, P, st);
                 case ROLLOUT_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_F32>, P, st);
                 case ROLLOUT_ACTIONS_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_ACTIONS_F32>, P, st);
+                case ROLLOUT_POLICY: return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY>, P, st);
                 }
                 return hipErrorInvalidValue;
             });

@@ -1,0 +1,113 @@
+// cz_policy.h -- the MLP policy the library evaluates itself (definition and host model: cooking_zoo_amd/policy.py): the packed
+// weight table, cz_exp, and policy_act, the one device function that goes from a float32 row in LDS to an action.  k_policy
+// (cz_query.h) and k_step<..., ROLLOUT_POLICY> (cz_kernels.h) both call it, so the launch of its own and the fused rollout cannot differ.
+#pragma once
+#include "cz_device.h"
+
+namespace cz {
+
+constexpr int POLICY_HIDDEN = 64;            // one lane per hidden unit
+constexpr int POLICY_MAX_SETS = 4, POLICY_MAX_ACTIONS = 8;
+constexpr uint32_t POLICY_NONE = 0xFFu;      // an agent's byte of `sets`: no policy for this agent
+constexpr uint32_t POLICY_AGENT_KEY = 0x300u;   // agent key of the sampling draw (0..3 spawn draws, 0x100 layouts, 0x200 tasks)
+enum : uint32_t { POLICY_GREEDY = 0, POLICY_SAMPLE = 1 };
+
+// One weight set in the table, as floats: W1 as [Fq][64][4] - unit j's weights of features 4q .. 4q+3 in one 16-byte word, so that
+// lane j's load of a quad is coalesced with its neighbours'; weights of features past F are 0.0 - then b1 [64], W2 [8][64] and b2 [8]
+// (rows past C are 0.0 and never read).
+__host__ __device__ inline int policy_quads(int F) { return (F + 3) >> 2; }
+__host__ __device__ inline uint32_t policy_set_floats(int F) {
+    return (uint32_t)policy_quads(F) * 256u + POLICY_HIDDEN + POLICY_MAX_ACTIONS * POLICY_HIDDEN + POLICY_MAX_ACTIONS;
+}
+// `sets` (agent a's set in byte a, 0xFF none) and the mode in 13 bits: three bits per agent, 7 = none, mode in bit 12
+__host__ __device__ inline uint32_t policy_pack_sets(uint32_t sets, uint32_t mode, int A) {
+    uint32_t pk = (mode & 1u) << 12;
+    for (int a = 0; a < MAX_AGENTS; ++a) {
+        const uint32_t s = a < A ? (sets >> (8 * a)) & 0xFFu : POLICY_NONE;
+        pk |= (s == POLICY_NONE ? 7u : s) << (3 * a);
+    }
+    return pk;
+}
+
+typedef float float4_t __attribute__((ext_vector_type(4)));
+// the float32 rows a policy reads, in LDS: per env A rows of 4 * policy_quads(F) floats, the tail zeroed (sized by the launch)
+extern __shared__ float4_t policy_rows[];
+
+// exp on [-64, 0] in plain float64 arithmetic, every operation rounded on its own (the build has -ffp-contract=off): numpy
+// reproduces it bit for bit (policy.cz_exp)
+__host__ __device__ inline double policy_exp(double z) {
+    const double k = floor(z * 1.4426950408889634 + 0.5);
+    const double r = (z - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+    constexpr double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0,
+                              1.0 / 362880.0, 1.0 / 3628800.0, 1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
+    double p = c[13];
+#pragma unroll
+    for (int i = 12; i >= 0; --i) p = p * r + c[i];
+    return ldexp(p, (int)k);
+}
+
+// p + p of lane (lane xor 2^k) for k = 0..5.  After level k every aligned group of 2^(k+1) lanes holds one value, so a lane may
+// take its partner's value from ANY lane of the partner group: the mirrors of the DPP row stand in for xor 4 and xor 8.
+__device__ __forceinline__ float policy_butterfly(float p) {
+    auto dpp = [](float v, auto ctrl) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), decltype(ctrl)::value, 0xF, 0xF, false));
+    };
+    p = p + dpp(p, std::integral_constant<int, 0xB1>{});         // quad_perm [1, 0, 3, 2]
+    p = p + dpp(p, std::integral_constant<int, 0x4E>{});         // quad_perm [2, 3, 0, 1]
+    p = p + dpp(p, std::integral_constant<int, 0x141>{});        // row_half_mirror
+    p = p + dpp(p, std::integral_constant<int, 0x140>{});        // row_mirror
+    p = p + __shfl_xor(p, 16);
+    p = p + __shfl_xor(p, 32);
+    return p;
+}
+
+// One agent's action from its row: `set` the agent's weight set (wave-uniform), `x` the row in LDS (4 * Fq floats, 16-byte aligned,
+// zero behind F), C the action count.  Every lane returns the same action; lane c < C returns logit c in `mylogit`.
+// The draw of POLICY_SAMPLE is spawn_uniform(seed, global env id, step, 0x300 + agent, 0).
+template <int C>
+__device__ __forceinline__ void policy_act(const float *__restrict__ set, int Fq, const float *x, int lane, uint32_t mode, uint64_t seed,
+                                           int64_t env_global, uint32_t step, int agent, int &action, float &mylogit) {
+    static_assert(C >= 1 && C <= POLICY_MAX_ACTIONS, "action count");
+    const float *const b1 = set + (uint32_t)Fq * 256u, *const w2 = b1 + POLICY_HIDDEN, *const b2 = w2 + POLICY_MAX_ACTIONS * POLICY_HIDDEN;
+    // hidden layer, lane = unit: one rounding per feature, features ascending
+    float acc = b1[lane];
+#pragma unroll 4
+    for (int q = 0; q < Fq; ++q) {
+        const float4_t w = *reinterpret_cast<const float4_t *>(set + ((uint32_t)q * 64u + (uint32_t)lane) * 4u);
+        const float4_t v = *reinterpret_cast<const float4_t *>(x + 4 * q);                 // the same address on every lane: a broadcast
+        acc = __builtin_fmaf(w.x, v.x, acc);
+        acc = __builtin_fmaf(w.y, v.y, acc);
+        acc = __builtin_fmaf(w.z, v.z, acc);
+        acc = __builtin_fmaf(w.w, v.w, acc);
+    }
+    const float hid = acc > 0.0f ? acc : 0.0f;
+    float logit[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) logit[c] = policy_butterfly(w2[c * POLICY_HIDDEN + lane] * hid) + b2[c];
+    float best = logit[0];
+    int arg = 0;
+    mylogit = logit[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) {
+        if (logit[c] > best) { best = logit[c]; arg = c; }          // the smallest c with the largest logit
+        mylogit = lane == c ? logit[c] : mylogit;
+    }
+    action = arg;
+    if (mode == POLICY_SAMPLE) {
+        const double u = spawn_uniform(seed, (uint64_t)env_global, (uint64_t)step, POLICY_AGENT_KEY + (uint32_t)agent, 0u);
+        double S[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const double z = (double)logit[c] - (double)best;
+            const double ex = policy_exp(z > -64.0 ? z : -64.0);
+            S[c] = c == 0 ? ex : S[c - 1] + ex;
+        }
+        const double thr = u * S[C - 1];
+        int pick = C - 1;
+#pragma unroll
+        for (int c = C - 2; c >= 0; --c) pick = S[c] > thr ? c : pick;
+        action = pick;
+    }
+}
+
+}  // namespace cz

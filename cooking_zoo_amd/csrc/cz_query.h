@@ -1060,4 +1060,68 @@ __global__ __launch_bounds__(64 * INFOS_WAVES) void k_infos(const InfosArgs G) {
     if (lane == 0u && G.t) G.t[i] = (int32_t)t;
 }
 
+// ---- the MLP policy as a launch of its own (cz_policy_device; definition: cooking_zoo_amd/policy.py, device function: cz_policy.h).
+// Reads the caller's float32 rows and the weight table and nothing of the records.
+struct PolicyArgs {
+    int64_t env_global0;           // the global id of the first env (the sampling draw is keyed by it)
+    const float *obs32;            // [count][A][F]
+    const float *table;            // the packed weight sets (k_policy_pack)
+    int32_t F, C;
+    uint32_t packed;               // policy_pack_sets: every agent's set and the mode
+    uint32_t step;
+    uint64_t seed;
+    int32_t *actions;              // [count][A] or null
+    float *logits;                 // [count][A][C] or null
+};
+// One wavefront per env: the env's rows go to LDS (zero behind F), then policy_act per agent with a weight set; the entries of the
+// other agents are left as they are in both outputs.
+template <int NA>
+__global__ __launch_bounds__(64) void k_policy(const PolicyArgs G) {
+    const int lane = (int)threadIdx.x;
+    const size_t i = blockIdx.x;
+    const int Fq = policy_quads(G.F);
+    float *const x = reinterpret_cast<float *>(policy_rows);
+    const float *const src = G.obs32 + i * (size_t)(NA * G.F);
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+        for (int f = lane; f < 4 * Fq; f += 64) x[a * 4 * Fq + f] = f < G.F ? src[(size_t)a * G.F + f] : 0.0f;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        const uint32_t si = (G.packed >> (3 * a)) & 7u;
+        if (si == 7u) continue;
+        int action;
+        float mylogit;
+        const float *const set = G.table + (size_t)si * policy_set_floats(G.F);
+        const uint32_t mode = (G.packed >> 12) & 1u;
+        if (G.C == 5) policy_act<5>(set, Fq, x + a * 4 * Fq, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
+        else policy_act<8>(set, Fq, x + a * 4 * Fq, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
+        if (G.actions && lane == 0) G.actions[i * NA + a] = action;
+        if (G.logits && lane < G.C) G.logits[(i * NA + a) * (size_t)G.C + lane] = mylogit;
+    }
+}
+// torch's layouts - W1 [n][64][F], b1 [n][64], W2 [n][C][64], b2 [n][C] - into the table's (cz_policy.h): one thread per float of it
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_policy_pack(float *__restrict__ table, int32_t n_sets, int32_t F, int32_t C, const float *__restrict__ w1,
+                                                     const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2) {
+    const uint32_t per_set = policy_set_floats(F), idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= per_set * (uint32_t)n_sets) return;
+    const uint32_t s = idx / per_set, o = idx - s * per_set, w1_end = (uint32_t)policy_quads(F) * 256u;
+    float v = 0.0f;
+    if (o < w1_end) {
+        const uint32_t q = o >> 8, j = (o >> 2) & 63u, f = 4u * q + (o & 3u);
+        if (f < (uint32_t)F) v = w1[((size_t)s * POLICY_HIDDEN + j) * (size_t)F + f];
+    } else if (o < w1_end + POLICY_HIDDEN) {
+        v = b1[s * POLICY_HIDDEN + (o - w1_end)];
+    } else if (o < w1_end + POLICY_HIDDEN + POLICY_MAX_ACTIONS * POLICY_HIDDEN) {
+        const uint32_t r = o - w1_end - POLICY_HIDDEN, c = r >> 6;
+        if (c < (uint32_t)C) v = w2[((size_t)s * C + c) * POLICY_HIDDEN + (r & 63u)];
+    } else {
+        const uint32_t c = o - w1_end - POLICY_HIDDEN - POLICY_MAX_ACTIONS * POLICY_HIDDEN;
+        if (c < (uint32_t)C) v = b2[s * C + c];
+    }
+    table[idx] = v;
+}
+
 }  // namespace cz

@@ -558,6 +558,28 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.rollout_actions_f32(P(d_actions, i), T, P(d_obs32, i), P(d_rewards, i), P(d_term, i), P(d_trunc, i)))
 
+    def load_policy(self, w1, b1, w2, b2):
+        """`CookingVecEnv.load_policy` on every shard: the same weight sets everywhere (numpy arrays, or device tensors every shard's
+        device can read)"""
+        self._each(lambda i, env: env.load_policy(w1, b1, w2, b2))
+
+    @property
+    def policy_sets(self):
+        return self.shards[0].policy_sets
+
+    def policy_device(self, d_obs32, d_actions=None, d_logits=None, sets=(0, 0, 0, 0), mode="greedy", seed=0, step=0):
+        """`CookingVecEnv.policy_device` on every shard over its part of the ShardedBuffers (per env: rows float32 [A, F], actions
+        int32 [A], logits float32 [A, num_actions]).  The draws of "sample" are keyed by the global env id: shards reproduce one handle."""
+        P = self._part
+        self._each(lambda i, env: env.policy_device(P(d_obs32, i), P(d_actions, i), P(d_logits, i), sets=sets, mode=mode, seed=seed, step=step))
+
+    def rollout_policy(self, T, d_obs32, d_actions=None, d_logits=None, d_rewards=None, d_term=None, d_trunc=None, sets=(0, 0, 0, 0),
+                       mode="greedy", seed=0, step0=0):
+        """`CookingVecEnv.rollout_policy` on every shard (the buffers: ShardedBuffers with leading = (T,))"""
+        P = self._part
+        self._each(lambda i, env: env.rollout_policy(T, P(d_obs32, i), P(d_actions, i), P(d_logits, i), P(d_rewards, i), P(d_term, i),
+                                                     P(d_trunc, i), sets=sets, mode=mode, seed=seed, step0=step0))
+
     def sync(self):
         self._each(lambda i, env: env.sync())
 

@@ -13,7 +13,7 @@ import random as _random
 
 import numpy as np
 
-from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, render as _render, rotation as _rotation, soa, tasks as _tasks
+from cooking_zoo_amd import _native, effects as _effects, grid as _grid, nav as _nav, partner as _partner, policy as _policy, render as _render, rotation as _rotation, soa, tasks as _tasks
 from cooking_zoo_amd.cooking_book import recipe_drawer
 from cooking_zoo_amd.cooking_world.actions import ACTION_SCHEMES
 from cooking_zoo_amd.cooking_world.engine import load_level as _ll
@@ -251,6 +251,7 @@ class CookingVecEnv:
             _native.check(self._h, L.cz_load_goal_table(self._h, _ptr(self.goal_table), len(self.book_names), self.num_goals))
         self._upload_layouts()
         self._buffers = []
+        self._policy_stage = {}          # load_policy's device copies of numpy weights, by role and shape
         self._ep_bufs = None                  # finished_episodes: the packed list and the count
         self._fork_buf = None                 # fork_device: the scratch archive, one row per env
         self._steps = 0                       # env steps issued so far (every stepping method counts; `advance` adds replayed ones)
@@ -1065,6 +1066,66 @@ class CookingVecEnv:
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_rollout_actions_f32(self._h, int(T), p(d_actions), p(d_obs32), p(d_rewards),
                                                                     p(d_term), p(d_trunc)))
+        self._issued(T)
+
+    # ------------------------------------------------------------------ the MLP policy (cooking_zoo_amd/policy.py)
+    def load_policy(self, w1, b1, w2, b2):
+        """load weight sets of `Sequential(Linear(F, 64), ReLU(), Linear(64, num_actions))` in torch's own layouts: w1 [64, F],
+        b1 [64], w2 [C, 64], b2 [C], float32 - one set, or a stack of up to 4 with a leading axis.  Device tensors (anything with
+        `data_ptr()`, contiguous float32: `module[0].weight` as it is) are repacked by one launch on the env's stream with no host
+        trip, so a learner reloads after every optimiser step; numpy arrays go through `alloc` + `from_host` first."""
+        F, Cn, H = self.F, self.num_actions, _policy.HIDDEN
+        stacked = len(tuple(w1.shape)) == 3
+        n = int(w1.shape[0]) if stacked else 1
+        want = [(n, H, F), (n, H), (n, Cn, H), (n, Cn)]
+        parts = []
+        for v, shape in zip((w1, b1, w2, b2), want):
+            got = tuple(int(s) for s in v.shape)
+            if got != (shape if stacked else shape[1:]):
+                raise ValueError(f"load_policy: shape {got}, expected {shape if stacked else shape[1:]} (F = {F}, C = {Cn})")
+            if hasattr(v, "data_ptr") or hasattr(v, "ptr"):
+                if str(v.dtype) not in ("torch.float32", "float32"):
+                    raise ValueError(f"load_policy: device tensors must be float32, not {v.dtype}")
+                parts.append(v)
+            else:
+                key = ("policy", len(parts), shape)
+                buf = self._policy_stage.get(key)
+                if buf is None:
+                    buf = self._policy_stage[key] = self.alloc(shape, np.float32)
+                buf.from_host(np.ascontiguousarray(v, np.float32).reshape(shape))
+                parts.append(buf)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_load_policy_device(self._h, n, p(parts[0]), p(parts[1]), p(parts[2]), p(parts[3])))
+
+    @property
+    def policy_sets(self):
+        """weight sets the last `load_policy` filled (0: none loaded)"""
+        return int(_native.lib().cz_policy_sets(self._h))
+
+    def policy_device(self, d_obs32, d_actions=None, d_logits=None, sets=(0, 0, 0, 0), mode="greedy", seed=0, step=0, env_begin=0,
+                      env_count=None):
+        """the policy on float32 rows of the caller, one launch, stream-ordered and capturable: `d_obs32` float32 [n, A, F] ->
+        `d_actions` int32 [n, A] and / or `d_logits` float32 [n, A, num_actions].  `sets`: agent a's weight set, None / 0xFF = none -
+        that agent's entries are left untouched in both outputs (so a partner's and a learner's actions can share one array).
+        `mode`: "greedy" (the smallest action with the largest logit) or "sample" (softmax sampling with the draw keyed by `seed`,
+        the global env id, `step` and the agent).  No record is read or written."""
+        n = self._count(env_count)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_policy_device(self._h, env_begin, n, p(d_obs32), _policy.pack_sets(sets, self.num_agents),
+                                                              _policy.MODES[mode], int(seed), int(step), p(d_actions), p(d_logits)))
+
+    def rollout_policy(self, T, d_obs32, d_actions=None, d_logits=None, d_rewards=None, d_term=None, d_trunc=None, sets=(0, 0, 0, 0),
+                       mode="greedy", seed=0, step0=0):
+        """`rollout_f32` driven by the loaded policy, T policy-driven steps in one launch: agent a's action at fused step t is the
+        policy's on the env's float32 row before that step (t = 0: what `observe_device(d_obs32=...)` would write now; later: row
+        t - 1 of the trajectory, a reset pass's row included), the draw of "sample" keyed by step0 + t.  Agents whose set is None /
+        0xFF play `rollout`'s own action stream of `seed`.  `d_obs32` float32 [T, N, A, F] is required; `d_actions` int32 [T, N, A]
+        (every agent's action as played) and `d_logits` float32 [T, N, A, num_actions] (policy agents only, the rest untouched)
+        are optional; rewards, flags, state, statistics and episode records are `rollout_actions_f32`'s over the same actions."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_rollout_policy(self._h, int(T), _policy.pack_sets(sets, self.num_agents), _policy.MODES[mode],
+                                                               int(seed), int(step0), p(d_obs32), p(d_actions), p(d_logits), p(d_rewards),
+                                                               p(d_term), p(d_trunc)))
         self._issued(T)
 
     def sync(self):

@@ -661,6 +661,43 @@ int cz_rollout_f32(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, float 
 int cz_rollout_actions_f32(cz_handle h, int32_t T, const int32_t *d_actions, float *d_obs32, double *d_rewards,
                            uint8_t *d_terminations, uint8_t *d_truncations);
 
+/* ---- The MLP policy the library evaluates itself (definition and numpy model: cooking_zoo_amd/policy.py).
+ * A weight set is the parameters of Sequential(Linear(F, 64), ReLU(), Linear(64, C)) in torch's own layout: W1 float32 [64][F],
+ * b1 [64], W2 [C][64], b2 [C]; F the handle's row length, C = cz_num_actions(h), hidden width 64; up to 4 sets per handle.  For a
+ * float32 row x: acc_j = b1[j], then acc_j = fmaf(W1[j][f], x[f], acc_j) for f ascending; h_j = acc_j > 0 ? acc_j : 0; per action
+ * p_j = W2[c][j] * h_j, six butterfly levels p_j += p_(j xor 2^k) in float32, logit_c = p + b2[c].  CZ_POLICY_GREEDY: the smallest c
+ * with the largest logit.  CZ_POLICY_SAMPLE, in float64, every operation rounded on its own: z_c = logit_c - max,
+ * e_c = cz_exp(max(z_c, -64)), running sums S_c, thr = u * S_(C-1), the smallest c with S_c > thr, else C - 1;
+ * u = cz_spawn_uniform(seed, global env id, 0, step, 0x300 + agent, 0).  numpy reproduces all of it bit for bit; NaN, infinities and
+ * subnormal intermediates are NOT pinned.
+ *
+ * cz_load_policy_device: n_sets (1..4) sets from DEVICE memory, sets contiguous in the layouts above; one repack launch on the
+ * handle's stream.  The handle's first call allocates the table (room for 4 sets), no later call allocates: those are legal inside a
+ * stream capture, so a learner reloads after every optimiser step with no host trip.  F and C are fixed by cz_create: neither
+ * cz_load_layouts nor cz_load_recipes drops the table.  Refused: n_sets outside 1..4, a NULL pointer. */
+#define CZ_POLICY_GREEDY 0
+#define CZ_POLICY_SAMPLE 1
+int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d_w1, const float *d_b1, const float *d_w2, const float *d_b2);
+int32_t cz_policy_sets(cz_handle h);           /* sets the last load filled; 0: none */
+/* The policy on rows of the caller, one launch (k_policy): d_obs32 float32 [env_count][A][F] -> d_actions int32 [env_count][A] and /
+ * or d_logits float32 [env_count][A][C].  `sets`: agent a's set index in byte a, 0xFF = none - that agent's entries are left
+ * untouched in both outputs (cz_partner_device's convention: a partner's and a learner's actions can share one array).  `step` keys
+ * the draw of CZ_POLICY_SAMPLE.  Stream-ordered: no copy, no wait, no allocation - legal inside a stream capture of the caller; no
+ * record is read.  Refused: a set index >= the loaded count, no table loaded, both outputs NULL, a range outside the batch. */
+int cz_policy_device(cz_handle h, int64_t env_begin, int64_t env_count, const float *d_obs32, uint32_t sets, int32_t mode,
+                     uint64_t seed, uint32_t step, int32_t *d_actions, float *d_logits);
+/* cz_rollout_f32 (cooking_env.py:243-269 T times, :352-373) with the policy in front of every fused step, T policy-driven steps in one
+ * launch (k_step<..., ROLLOUT_POLICY>): agent a's action at fused step t is the policy's on the env's float32 row before that step -
+ * t = 0: what cz_observe_device_f32 would write at launch; t > 0: row t - 1 of the trajectory, whatever it is, the row of a reset
+ * pass included - with the draw keyed by step = step0 + t.  Agents whose byte of `sets` is 0xFF play cz_rollout's own stream,
+ * cz_action(seed, env, a, step0 + t, C).  d_obs32 float32 [T][N][A][F] is required; d_actions int32 [T][N][A] (every agent's action
+ * as played, stream agents included) and d_logits float32 [T][N][A][C] (policy agents only, the rest untouched) may be NULL; rewards,
+ * flags, state, statistics and episode records are cz_rollout_actions_f32's over the same actions.  The rows are staged in LDS next
+ * to their stores (A * 4 * ceil(F / 4) * 4 bytes per env): a handle whose rows do not fit a workgroup's LDS is refused.  Refused
+ * besides: what cz_rollout_f32 refuses, every agent at 0xFF, a set index >= the loaded count, no table loaded. */
+int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t mode, uint64_t seed, uint32_t step0, float *d_obs32,
+                      int32_t *d_actions, float *d_logits, double *d_rewards, uint8_t *d_terminations, uint8_t *d_truncations);
+
 /* the action the on-device stream draws (host mirror, for parity tests) */
 uint32_t cz_action(uint64_t seed, int64_t env_global, int32_t agent, uint32_t step, uint32_t n_actions);
 /* the layout an env draws for its k-th episode under auto_reset */
