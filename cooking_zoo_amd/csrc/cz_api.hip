@@ -361,6 +361,7 @@ struct cz_handle_s {
     int wt_override = -1;          // CZ_WT experiment switch, read once
     bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
     bool lean_cfg_enabled = true;  // CZ_LEAN_CFG=0: lean launches always take k_step_lean, never a k_step_lean_cfg (A/B runs)
+    int gae_shape = GAE_DEPTH * 1000 + GAE_BLOCK;   // CZ_GAE_SHAPE=<rows ahead>x<workgroup size>: k_gae's instance (tools/targets_sizes.py)
     int last_step_variant = -1;    // cz_diag_last_step_variant
     int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
     int last_step_mode = -1;       // the StepMode of that launch (cz_diag_last_step_mode)
@@ -538,6 +539,10 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     if (const char *s = getenv("CZ_LEAN")) h->lean_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_LEAN_CFG")) h->lean_cfg_enabled = atoi(s) != 0;
     if (const char *s = getenv("CZ_GRAPHS")) h->graphs_enabled = atoi(s) != 0;
+    if (const char *s = getenv("CZ_GAE_SHAPE")) {
+        int d = 0, w = 0;
+        if (sscanf(s, "%dx%d", &d, &w) == 2) h->gae_shape = d * 1000 + w;      // (a shape the library does not carry is refused by the call)
+    }
     if (const char *s = getenv("CZ_GRAPH_MIN_RUN")) h->graph_min_run = atoi(s) < 4 ? 4 : (atoi(s) > 256 ? 256 : atoi(s));   // 4..RING_MAX_GRAPH
     if (const char *s = getenv("CZ_RING_PREFIX")) h->ring_prefix = atoi(s) < 0 ? 0 : (atoi(s) > 16 ? 16 : atoi(s));
     if (const char *s = getenv("CZ_ZERO_COPY_BYTES")) h->zero_copy_bytes = (size_t)atoll(s);
@@ -2355,6 +2360,67 @@ extern "C" int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t 
     c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
     c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
     return launch_step(h, c);
+}
+
+// ---- what a learner trains on (definition: cooking_zoo_amd/targets.py; k_gae / k_logprob in cz_query.h).  Both calls work on dense
+// arrays of the caller whose extents the caller names - a shard or a slice passes its own - and are one launch on the handle's stream:
+// nothing is copied, waited for or allocated (legal inside a stream capture of the caller); no record is read.
+template <int D, int WG>
+static hipError_t launch_gae(hipStream_t stream, const GaeArgs &G) {
+    hipLaunchKernelGGL((k_gae<D, WG>), dim3((unsigned)((G.n + WG - 1) / WG)), dim3(WG), 0, stream, G);
+    return hipGetLastError();
+}
+// Generalised advantage estimation over [T][env_count][A] series, t descending, in float64 (targets.host_gae): d_values float32
+// [T + 1][env_count][A] holds the critic on the state before step t in row t and the bootstrap in row T; a termination or truncation
+// at t cuts both the bootstrap and the carry.  Series of agents outside `agents` are neither read nor written.
+extern "C" int cz_gae_device(cz_handle h, int32_t T, int64_t env_count, const double *d_rewards, const uint8_t *d_term, const uint8_t *d_trunc,
+                             const float *d_values, double gamma, double lambda, uint32_t agents, float *d_adv, float *d_ret) {
+    if (ready(h)) return 1;
+    const int A = h->P.A;
+    if (T < 1) return fail(h, "cz_gae_device: T is %d, not >= 1", T);
+    if (env_count < 1 || env_count > (int64_t)0x7FFFFFFF * 64 / A) return fail(h, "cz_gae_device: env_count is %lld, not 1..%lld", (long long)env_count, (long long)((int64_t)0x7FFFFFFF * 64 / A));
+    if (!d_rewards || !d_term || !d_values) return fail(h, "cz_gae_device: the rewards, terminations or values pointer is null");
+    if (!d_adv && !d_ret) return fail(h, "cz_gae_device: both output pointers are null");
+    if (!(agents & ((1u << A) - 1u))) return fail(h, "cz_gae_device: agents is 0x%x: none of the %d agents", agents, A);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(h, "cz_gae_device: gamma is %g, not in [0, 1]", gamma);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(h, "cz_gae_device: lambda is %g, not in [0, 1]", lambda);
+    if (set_device(h)) return 1;
+    const GaeArgs G{env_count * A, T, A, agents, d_rewards, d_term, d_trunc, d_values, gamma, gamma * lambda, d_adv, d_ret};
+    hipError_t e = hipErrorInvalidValue;
+    switch (h->gae_shape) {
+    case 2064: e = launch_gae<2, 64>(h->stream, G); break;
+    case 4064: e = launch_gae<4, 64>(h->stream, G); break;
+    case 8064: e = launch_gae<8, 64>(h->stream, G); break;
+    case 16064: e = launch_gae<16, 64>(h->stream, G); break;
+    case 2256: e = launch_gae<2, 256>(h->stream, G); break;
+    case 4256: e = launch_gae<4, 256>(h->stream, G); break;
+    case 8256: e = launch_gae<8, 256>(h->stream, G); break;
+    case 16256: e = launch_gae<16, 256>(h->stream, G); break;
+    default: return fail(h, "cz_gae_device: CZ_GAE_SHAPE names %d rows ahead x %d threads; the library carries 2, 4, 8, 16 x 64, 256", h->gae_shape / 1000, h->gae_shape % 1000);
+    }
+    HIPCHK(h, e);
+    return 0;
+}
+// Log-probability of the action played and entropy of the softmax CZ_POLICY_SAMPLE draws from (targets.host_logprob): d_logits float32
+// [rows][A][C], d_actions int32 [rows][A] -> d_logp and / or d_entropy float32 [rows][A]; an action outside 0 .. C-1 gets 0.0.  Agents
+// whose byte of `sets` is 0xFF are left untouched in both outputs (cz_policy_device's convention: their logits were never written).
+extern "C" int cz_logprob_device(cz_handle h, int64_t rows, const float *d_logits, const int32_t *d_actions, uint32_t sets, float *d_logp,
+                                 float *d_entropy) {
+    if (ready(h)) return 1;
+    const int A = h->P.A;
+    if (rows < 1 || rows > (int64_t)0x7FFFFFFF * 256 / A) return fail(h, "cz_logprob_device: rows is %lld, not 1..%lld", (long long)rows, (long long)((int64_t)0x7FFFFFFF * 256 / A));
+    if (!d_logits || !d_actions) return fail(h, "cz_logprob_device: the logits or actions pointer is null");
+    if (!d_logp && !d_entropy) return fail(h, "cz_logprob_device: both output pointers are null");
+    int chosen = 0;
+    for (int a = 0; a < A; ++a) chosen += ((sets >> (8 * a)) & 0xFFu) != POLICY_NONE;
+    if (!chosen) return fail(h, "cz_logprob_device: every agent's byte of sets is 0xFF");
+    if (set_device(h)) return 1;
+    const LogprobArgs G{rows * A, A, sets, d_logits, d_actions, d_logp, d_entropy};
+    const dim3 grid((unsigned)((G.total + 255) / 256));
+    if (cz_num_actions(h) == 5) hipLaunchKernelGGL((k_logprob<5>), grid, dim3(256), 0, h->stream, G);
+    else hipLaunchKernelGGL((k_logprob<8>), grid, dim3(256), 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    return 0;
 }
 
 // the device address of pinned, device-mapped host memory (cz_host_alloc, hipHostMalloc, hipHostRegister); nullptr for

@@ -1,6 +1,8 @@
 // cz_policy.h -- the MLP policy the library evaluates itself (definition and host model: cooking_zoo_amd/policy.py): the packed
 // weight table, cz_exp, and policy_act, the one device function that goes from a float32 row in LDS to an action.  k_policy
 // (cz_query.h) and k_step<..., ROLLOUT_POLICY> (cz_kernels.h) both call it, so the launch of its own and the fused rollout cannot differ.
+// Beside them cz_log and policy_logprob, the log-probability and entropy of the distribution policy_act samples from (k_logprob;
+// definition: cooking_zoo_amd/targets.py).
 #pragma once
 #include "cz_device.h"
 
@@ -44,6 +46,48 @@ __host__ __device__ inline double policy_exp(double z) {
 #pragma unroll
     for (int i = 12; i >= 0; --i) p = p * r + c[i];
     return ldexp(p, (int)k);
+}
+
+// log on [1, 8] in the same arithmetic, with no division (targets.cz_log): the chord of log under [1, 2] scaled by the power of two,
+// then five Newton steps on S * exp(-y) = 1.  policy_log(1.0) is 0.0 exactly.
+__host__ __device__ inline double policy_log(double S) {
+    constexpr double ln2 = 0.6931471805599453;
+    const int k = (S >= 2.0) + (S >= 4.0) + (S >= 8.0);
+    const double m = S * (k == 0 ? 1.0 : k == 1 ? 0.5 : k == 2 ? 0.25 : 0.125);
+    double y = (double)k * ln2 + (m - 1.0) * ln2;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const double ny = -y;
+        y = y + (S * policy_exp(ny > -64.0 ? ny : -64.0) - 1.0);
+    }
+    return y;
+}
+
+// The softmax policy_act samples from, as log-probabilities (targets.host_logprob): the C logits of one row -> the float64
+// log-probability of `action` (0.0 for an action outside 0 .. C-1) and the entropy, each rounded to float32 by the caller.
+template <int C>
+__host__ __device__ __forceinline__ void policy_logprob(const float (&logit)[C], int action, double &logp, double &entropy) {
+    float best = logit[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) best = logit[c] > best ? logit[c] : best;
+    double z[C], S = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        z[c] = (double)logit[c] - (double)best;
+        const double ex = policy_exp(z[c] > -64.0 ? z[c] : -64.0);
+        S = c == 0 ? ex : S + ex;
+    }
+    const double L = policy_log(S);
+    double za = 0.0, acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        za = action == c ? z[c] : za;
+        const double q = z[c] - L;
+        const double pq = policy_exp(q > -64.0 ? q : -64.0) * q;
+        acc = c == 0 ? pq : acc + pq;
+    }
+    logp = (unsigned)action < (unsigned)C ? za - L : 0.0;
+    entropy = -acc;
 }
 
 // p + p of lane (lane xor 2^k) for k = 0..5.  After level k every aligned group of 2^(k+1) lanes holds one value, so a lane may

@@ -1124,4 +1124,97 @@ __global__ __launch_bounds__(256) void k_policy_pack(float *__restrict__ table, 
     table[idx] = v;
 }
 
+// ---- what a learner trains on (cz_gae_device, cz_logprob_device; definition: cooking_zoo_amd/targets.py).  Neither kernel reads a
+// record: both work on the caller's dense arrays alone.
+struct GaeArgs {
+    int64_t n;                     // series: env_count * A; row t of every array is n contiguous elements
+    int32_t T, A;
+    uint32_t agents;               // bit a: agent a's series are computed; the others are neither read nor written
+    const double *rewards;         // [T][n]
+    const uint8_t *term, *trunc;   // [T][n]; trunc may be null
+    const float *values;           // [T + 1][n]
+    double gamma, gl;              // gl = gamma * lambda, rounded once by the host
+    float *adv, *ret;              // [T][n]; one of them may be null
+};
+// One thread per series, t descending: the recurrence is serial, but no load depends on it, so the rows are loaded a block of D ahead
+// of the block the chain is working on - two register blocks, the loads of the next one issued before the first use of this one.
+// Rows below 0 of the last block are loaded from row 0 (in bounds, never used) so that every block's loads are one straight run.
+// Without truncations the terminations stand in for them (the same byte twice): no branch between the loads.
+// The library carries D in {2, 4, 8, 16} x WG in {64, 256}; a launch takes GAE_DEPTH x GAE_BLOCK unless CZ_GAE_SHAPE names another.
+constexpr int GAE_DEPTH = 8, GAE_BLOCK = 64;
+template <int D, int WG>
+__global__ __launch_bounds__(WG) void k_gae(const GaeArgs G) {
+    const size_t i = (size_t)blockIdx.x * WG + threadIdx.x, n = (size_t)G.n;
+    if (i >= n || !((G.agents >> (uint32_t)(i % (size_t)G.A)) & 1u)) return;
+    struct Rows { double r[D]; float v[D]; uint32_t done[D]; };
+    const uint8_t *const trunc = G.trunc ? G.trunc : G.term;
+    auto load = [&](int top, Rows &b) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const int t = top - k;
+            const size_t o = (size_t)(t < 0 ? 0 : t) * n + i;
+            b.r[k] = G.rewards[o];
+            b.v[k] = G.values[o];
+            b.done[k] = (uint32_t)G.term[o] | (uint32_t)trunc[o];
+        }
+    };
+    Rows cur, nxt;
+    load(G.T - 1, cur);
+    double vnext = (double)G.values[(size_t)G.T * n + i], A = 0.0;
+    for (int top = G.T - 1; top >= 0; top -= D) {
+        load(top - D, nxt);
+        double v[D], d[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) {                              // off the chain: the TD errors of the block
+            v[k] = (double)cur.v[k];
+            d[k] = (cur.r[k] + (cur.done[k] ? 0.0 : G.gamma * (k == 0 ? vnext : v[k - 1]))) - v[k];
+        }
+        vnext = v[D - 1];
+        if (top >= D - 1) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                A = d[k] + (cur.done[k] ? 0.0 : G.gl * A);
+                const size_t o = (size_t)(top - k) * n + i;
+                if (G.adv) G.adv[o] = (float)A;
+                if (G.ret) G.ret[o] = (float)(A + v[k]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                if (k > top) continue;
+                A = d[k] + (cur.done[k] ? 0.0 : G.gl * A);
+                const size_t o = (size_t)(top - k) * n + i;
+                if (G.adv) G.adv[o] = (float)A;
+                if (G.ret) G.ret[o] = (float)(A + v[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < D; ++k) { cur.r[k] = nxt.r[k]; cur.v[k] = nxt.v[k]; cur.done[k] = nxt.done[k]; }      // (element by element: registers)
+    }
+}
+
+struct LogprobArgs {
+    int64_t total;                 // rows * A
+    int32_t A;
+    uint32_t sets;                 // agent a's byte 0xFF: its entries are left untouched in both outputs
+    const float *logits;           // [rows][A][C]
+    const int32_t *actions;        // [rows][A]
+    float *logp, *entropy;         // [rows][A]; one of them may be null
+};
+// One thread per (row, agent): the C logits, policy_logprob (cz_policy.h) in float64, two float32 stores.
+template <int C>
+__global__ __launch_bounds__(256) void k_logprob(const LogprobArgs G) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= (size_t)G.total) return;
+    const uint32_t a = (uint32_t)(i % (size_t)G.A);
+    if (((G.sets >> (8u * a)) & 0xFFu) == POLICY_NONE) return;
+    float logit[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) logit[c] = G.logits[i * C + c];
+    double logp, entropy;
+    policy_logprob<C>(logit, G.actions[i], logp, entropy);
+    if (G.logp) G.logp[i] = (float)logp;
+    if (G.entropy) G.entropy[i] = (float)entropy;
+}
+
 }  // namespace cz

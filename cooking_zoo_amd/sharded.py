@@ -580,6 +580,30 @@ class ShardedVecEnv:
         self._each(lambda i, env: env.rollout_policy(T, P(d_obs32, i), P(d_actions, i), P(d_logits, i), P(d_rewards, i), P(d_term, i),
                                                      P(d_trunc, i), sets=sets, mode=mode, seed=seed, step0=step0))
 
+    def gae_device(self, T, d_rewards, d_term, d_trunc, d_values, d_adv=None, d_ret=None, gamma=0.99, lam=0.95, agents=None, env_count=None):
+        """`CookingVecEnv.gae_device` on every shard over its part of the ShardedBuffers: leading = (T,), and (T + 1,) for the
+        values.  Every series is an env's own, so shards reproduce one handle.  `env_count` must stay None: a shard's extent is its
+        own env count."""
+        if env_count is not None:
+            raise ValueError("gae_device over shards: every shard passes its own env count")
+        P = self._part
+        self._each(lambda i, env: env.gae_device(T, P(d_rewards, i), P(d_term, i), P(d_trunc, i), P(d_values, i), P(d_adv, i), P(d_ret, i),
+                                                 gamma=gamma, lam=lam, agents=agents))
+
+    def logprob_device(self, d_logits, d_actions, d_logp=None, d_entropy=None, sets=(0, 0, 0, 0), rows=None):
+        """`CookingVecEnv.logprob_device` on every shard over its part of the ShardedBuffers.  `rows` counts the [A]-rows of the
+        whole batch - T * N for buffers with leading = (T,), a multiple of N - and every shard takes its share; None reads T from
+        the leading shape of `d_logits`."""
+        if rows is None:
+            per_env = int(np.prod(d_logits.leading, dtype=np.int64)) if isinstance(d_logits, ShardedBuffer) else 1
+        else:
+            per_env, rest = divmod(int(rows), self.num_envs)
+            if rest or per_env < 1:
+                raise ValueError(f"logprob_device over shards: rows = {rows} is not a positive multiple of the {self.num_envs} envs")
+        P = self._part
+        self._each(lambda i, env: env.logprob_device(P(d_logits, i), P(d_actions, i), P(d_logp, i), P(d_entropy, i), sets=sets,
+                                                     rows=per_env * env.num_envs))
+
     def sync(self):
         self._each(lambda i, env: env.sync())
 

@@ -1128,6 +1128,31 @@ class CookingVecEnv:
                                                                p(d_term), p(d_trunc)))
         self._issued(T)
 
+    # ------------------------------------------------------------------ what a learner trains on (cooking_zoo_amd/targets.py)
+    def gae_device(self, T, d_rewards, d_term, d_trunc, d_values, d_adv=None, d_ret=None, gamma=0.99, lam=0.95, agents=None, env_count=None):
+        """generalised advantage estimation over a trajectory in device memory, one launch, stream-ordered and capturable:
+        `d_rewards` float64 [T, n, A], `d_term` / `d_trunc` uint8 [T, n, A] (`d_trunc` may be None) - what `rollout_policy` wrote -
+        and `d_values` float32 [T + 1, n, A] - row t the critic on the state before step t, row T the bootstrap - ->
+        `d_adv` and / or `d_ret` float32 [T, n, A], bit for bit `targets.host_gae`.  A termination or truncation at t cuts the
+        bootstrap and the carry.  `agents`: bit a = agent a's series are computed (None: all), the others neither read nor
+        written.  `env_count`: n, the caller's own extent (None: the handle's N).  No record is read."""
+        n = self._count(env_count)
+        mask = (1 << self.num_agents) - 1 if agents is None else int(agents)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_gae_device(self._h, int(T), n, p(d_rewards), p(d_term), p(d_trunc), p(d_values), float(gamma),
+                                                           float(lam), mask, p(d_adv), p(d_ret)))
+
+    def logprob_device(self, d_logits, d_actions, d_logp=None, d_entropy=None, sets=(0, 0, 0, 0), rows=None):
+        """the log-probability of the action played and the entropy of the distribution "sample" draws from, one launch,
+        stream-ordered and capturable: `d_logits` float32 [rows, A, num_actions], `d_actions` int32 [rows, A] -> `d_logp` and / or
+        `d_entropy` float32 [rows, A], bit for bit `targets.host_logprob`.  `rows` counts [A]-rows: None is the handle's N (the
+        output of `policy_device`), a trajectory of `rollout_policy` passes T * N.  An action outside 0 .. num_actions - 1 gets
+        logp 0.0.  `sets` as in `policy_device`: an agent at None / 0xFF is left untouched in both outputs - its logits were never
+        written (the index itself plays no part).  No record is read."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_logprob_device(self._h, self._count(rows), p(d_logits), p(d_actions),
+                                                               _policy.pack_sets(sets, self.num_agents), p(d_logp), p(d_entropy)))
+
     def sync(self):
         _native.check(self._h, _native.lib().cz_sync(self._h))
 

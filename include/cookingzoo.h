@@ -698,6 +698,34 @@ int cz_policy_device(cz_handle h, int64_t env_begin, int64_t env_count, const fl
 int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t mode, uint64_t seed, uint32_t step0, float *d_obs32,
                       int32_t *d_actions, float *d_logits, double *d_rewards, uint8_t *d_terminations, uint8_t *d_truncations);
 
+/* ---- What an on-policy learner trains on, from the trajectory cz_rollout_policy leaves in device memory (definition and numpy
+ * model: cooking_zoo_amd/targets.py).  Float64 throughout, every operation rounded on its own, outputs rounded to float32 once; numpy
+ * reproduces both calls bit for bit; NaN, infinities and subnormal intermediates are NOT pinned.  Both are one launch on the handle's
+ * stream over dense arrays of the caller - no copy, no wait, no allocation, legal inside a stream capture of the caller; no record is
+ * read.  The extents are the caller's own and not tied to the handle's batch: a shard or a slice passes its own.
+ *
+ * cz_gae_device: generalised advantage estimation.  d_rewards float64 [T][env_count][A], d_terminations / d_truncations uint8
+ * [T][env_count][A] (d_truncations may be NULL), d_values float32 [T + 1][env_count][A]: row t the critic on the state BEFORE step t,
+ * row T the bootstrap.  Per series, gl = gamma * lambda, A = 0, for t = T - 1 down to 0: done = term[t] || trunc[t];
+ * d = (r[t] + (done ? 0 : gamma * V[t + 1])) - V[t]; A = d + (done ? 0 : gl * A); adv[t] = (float)A; ret[t] = (float)(A + V[t]).  The
+ * serial order is the definition.  Done is terminal for truncations too: under auto-reset the row behind a finished episode is the
+ * next episode's first observation.  `agents`: bit a = agent a's series are computed, the others neither read nor written.  One of
+ * d_advantages / d_returns may be NULL.  Refused: T < 1, env_count < 1, NULL rewards / terminations / values, both outputs NULL,
+ * `agents` without an agent below A, gamma or lambda outside [0, 1] or NaN. */
+int cz_gae_device(cz_handle h, int32_t T, int64_t env_count, const double *d_rewards, const uint8_t *d_terminations,
+                  const uint8_t *d_truncations, const float *d_values, double gamma, double lambda, uint32_t agents,
+                  float *d_advantages, float *d_returns);
+/* cz_logprob_device: the log-probability of the action played and the entropy of the distribution CZ_POLICY_SAMPLE draws from, from
+ * its own z_c = logit_c - max, e_c = cz_exp(max(z_c, -64)) and running sum S: logp = (float)(z_a - cz_log(S)); q_c = z_c - cz_log(S),
+ * p_c = cz_exp(max(q_c, -64)), entropy = (float)(-(p_0 q_0 + p_1 q_1 + ...)) in ascending c.  cz_log on [1, 8]: k = (S >= 2) + (S >= 4)
+ * + (S >= 8), m = S * 2^-k, y = k ln2 + (m - 1) ln2, five steps y = y + (S * cz_exp(max(-y, -64)) - 1); no division; cz_log(1) = 0.
+ * d_logits float32 [rows][A][C], d_actions int32 [rows][A] -> d_logp and / or d_entropy float32 [rows][A]; `rows` counts [A]-rows: T * N
+ * for a trajectory, n for cz_policy_device's output.  An action outside 0 .. C-1 gets logp 0.0 (its entropy is written).  Agents whose
+ * byte of `sets` is 0xFF are left untouched in both outputs (their logits were never written).  Refused: rows < 1, NULL logits or
+ * actions, both outputs NULL, every agent below A at 0xFF. */
+int cz_logprob_device(cz_handle h, int64_t rows, const float *d_logits, const int32_t *d_actions, uint32_t sets,
+                      float *d_logp, float *d_entropy);
+
 /* the action the on-device stream draws (host mirror, for parity tests) */
 uint32_t cz_action(uint64_t seed, int64_t env_global, int32_t agent, uint32_t step, uint32_t n_actions);
 /* the layout an env draws for its k-th episode under auto_reset */
