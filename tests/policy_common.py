@@ -60,6 +60,65 @@ def weights(F, C, n_sets=2, seed=0, scale=0.3, scale2=None):
     return tuple((rng.standard_normal(s) * k).astype(np.float32) for s, k in zip(shapes, scales))
 
 
+def dense_rows(n, A, F, seed):
+    """float32 [n][A][F] standard normal x 0.5 with every entry of magnitude 2^-20 or more and no two entries of a row equal: rows
+    in which every feature - every column of W1, the last quad's included - reaches the logits, and in which two columns that
+    change places show.  (Observation rows are sparse: about half their features are 0.0 in every row the oracle produces.)"""
+    for k in range(16):                                         # (a collision or a tiny draw is rare: the whole array is drawn again)
+        x = (np.random.default_rng(2000 + seed + 7919 * k).standard_normal((n, A, F)) * 0.5).astype(np.float32)
+        s = np.sort(x, axis=-1)
+        if (np.abs(x) >= 2.0 ** -20).all() and (s[..., 1:] != s[..., :-1]).all() and float(np.abs(x).max()) < 8.0:
+            return x
+    raise AssertionError("dense_rows: no draw without a tiny entry or two equal entries in a row")
+
+
+def exact_logit_weights(F, L, dead=False):
+    """one weight set whose logits are the float32 values `L` [C] in bits for ANY finite row: W1 = 0, b1 = (1, 0, ..., 0), W2[c][0] =
+    L_c, the rest 0, b2 = 0 - hidden unit 0 is 1.0, the others 0.0, and the butterfly adds zeros to L_c.  `dead`: b1 = -1 everywhere,
+    so every hidden unit is 0.0, with an ordinary W2 and b2 = L: the logits are b2's bits (L must hold no 0.0, whose sign a sum of
+    zeros would decide) -> (w1 [64][F], b1 [64], w2 [C][64], b2 [C])"""
+    L = np.asarray(L, np.float32)
+    Cn = len(L)
+    w1, b1 = np.zeros((policy.HIDDEN, F), np.float32), np.zeros(policy.HIDDEN, np.float32)
+    w2, b2 = np.zeros((Cn, policy.HIDDEN), np.float32), np.zeros(Cn, np.float32)
+    if dead:
+        assert (L != 0).all(), "exact_logit_weights: a dead hidden layer cannot give a logit of 0.0 a sign"
+        b1[:] = -1.0
+        w2[:] = (np.random.default_rng(Cn).standard_normal(w2.shape) * 0.3).astype(np.float32)
+        b2[:] = L
+    else:
+        b1[0] = 1.0
+        w2[:, 0] = L
+    return w1, b1, w2, b2
+
+
+def logit_cases(Cn):
+    """name -> (L float32 [Cn], dead): the logits the sampling rule is shown on the device - all equal; three tied at the maximum
+    (the last action among them); one 70 and one 1000 below the maximum, both beyond the clamp at -64; one overwhelming (50 above
+    the rest: the sum of the exponentials is 1.0 exactly, so its log-probability is 0.0); every hidden unit dead, logits from b2"""
+    low = np.linspace(-1.5, -0.25, Cn).astype(np.float32)
+    tie = low.copy()
+    tie[[1, 3, Cn - 1]] = 2.0
+    clamp = (low * np.float32(0.25)).astype(np.float32)
+    clamp[2], clamp[0], clamp[Cn - 2] = 1.0, -69.0, -999.0
+    one = low.copy()
+    one[Cn - 2] = 50.0
+    dead = np.linspace(0.5, -0.75, Cn).astype(np.float32)
+    assert (dead != 0).all(), "logit_cases: b2 holds a zero"
+    return {"flat": (np.full(Cn, 0.25, np.float32), False), "tie3": (tie, False), "clamp": (clamp, False), "one": (one, False),
+            "dead": (dead, True)}
+
+
+def stack_sets(sets):
+    """weight sets (w1, b1, w2, b2) -> the stacked form `load_policy` and `expected_policy` take"""
+    return tuple(np.stack(v) for v in zip(*sets))
+
+
+def matrix_product_logits(x, w1, b1, w2, b2):
+    """the plain float32 matrix-product form of one set's logits: another summation order, other bits"""
+    return (np.maximum(x @ w1.T + b1, 0) @ w2.T + b2).astype(np.float32)
+
+
 def sets_for(A):
     """agent 0 on set 1, the others on set 0, the last agent without a policy where A >= 2"""
     s = [1] + [0] * (A - 1)
@@ -133,9 +192,50 @@ def replay(ctx, orc, got, acts):
     return recs
 
 
-def expected_policy(rows_before, W, sets, mode, seed, step0, stream, env_id_base=0):
+def logits_per_set(rows, W):
+    """rows float32 [...][F], W stacked sets -> [host_logits of every row under set s, float32 [...][C], for each s]: what many
+    launches over the same rows share"""
+    x = np.ascontiguousarray(rows).view(np.float32)
+    return [policy.host_logits(x, W[0][s], W[1][s], W[2][s], W[3][s]) for s in range(len(W[0]))]
+
+
+def swap_columns(w1, f):
+    """w1 [64][F] with columns f and f + 1 exchanged"""
+    out = w1.copy()
+    out[:, [f, f + 1]] = w1[:, [f + 1, f]]
+    return out
+
+
+def dense_conditions(ctx, rows, W, per_set):
+    """what makes a comparison on the rows able to fail, from the model alone, for every set of W: the expected logits of EVERY row
+    change when the last two columns of W1 change places, when the first two do, and when every column moves one place; the sets'
+    logits differ pairwise in every row; and at least 25 % of the logits differ in bits from the matrix-product form -> that share"""
+    x = np.ascontiguousarray(rows).view(np.float32)
+    F = x.shape[-1]
+    x = x.reshape(-1, F)
+    base = [np.ascontiguousarray(p).reshape(len(x), -1).view(np.uint32) for p in per_set]
+    differ = total = 0
+    for s, want in enumerate(base):
+        w1, rest = W[0][s], (W[1][s], W[2][s], W[3][s])
+        for what, other in (("the last two columns of W1 exchanged", swap_columns(w1, F - 2)), ("the first two columns of W1 exchanged", swap_columns(w1, 0)),
+                            ("every column of W1 moved one place", np.roll(w1, 1, axis=1))):
+            got = policy.host_logits(x, other, *rest).view(np.uint32)
+            same = int((got == want).all(axis=-1).sum())
+            assert same == 0, f"{ctx}: set {s} with {what} gives the same logits in {same} of {len(x)} rows: the case shows nothing"
+        for t in range(s):
+            same = int((base[t] == want).all(axis=-1).sum())
+            assert same == 0, f"{ctx}: sets {t} and {s} give the same logits in {same} of {len(x)} rows: the case shows nothing"
+        differ += int((matrix_product_logits(x, w1, *rest).view(np.uint32) != want).sum())
+        total += want.size
+    share = differ / total
+    assert share >= 0.25, f"{ctx}: only {share:.1%} of the logits differ from the matrix-product form: the case shows nothing"
+    return share
+
+
+def expected_policy(rows_before, W, sets, mode, seed, step0, stream, env_id_base=0, per_set=None):
     """half 2: rows_before uint32 / float32 [T][n][A][F] - the row before every step - -> (actions int32 [T][n][A], logits float32
-    [T][n][A][C] with NaN where no policy wrote, mask [A] of the policy agents); agents without a set take `stream`"""
+    [T][n][A][C] with NaN where no policy wrote, mask [A] of the policy agents); agents without a set take `stream`.
+    `per_set`: logits_per_set(rows_before, W), computed once for several calls on the same rows"""
     x = np.ascontiguousarray(rows_before).view(np.float32)
     T, n, A, _ = x.shape
     Cn = W[2].shape[1]
@@ -149,7 +249,7 @@ def expected_policy(rows_before, W, sets, mode, seed, step0, stream, env_id_base
         if s is None or s == policy.NONE:
             continue
         mask[a] = True
-        logits[:, :, a] = policy.host_logits(x[:, :, a], W[0][s], W[1][s], W[2][s], W[3][s])
+        logits[:, :, a] = policy.host_logits(x[:, :, a], W[0][s], W[1][s], W[2][s], W[3][s]) if per_set is None else per_set[s][:, :, a]
         acts[:, :, a] = policy.host_actions(logits[:, :, a], mode, seed, env_ids, steps, a)
     return acts, logits, mask
 

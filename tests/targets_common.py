@@ -9,10 +9,15 @@ GAMMA, LAM = 0.99, 0.95
 REWARD_EVENTS = (-0.01, 1.0, 19.9875, -0.5)                     # what replaces the time penalty in 10 % of the steps
 
 
-def gae_data(T, n, A, seed=0, flags="both", done_share=0.08):
+DONE_BYTES = (2, 0x80, 0xFF)                                     # flag bytes other than 1: the definition is `!= 0`
+
+
+def gae_data(T, n, A, seed=0, flags="both", done_share=0.08, byte=None):
     """-> rewards float64 [T, n, A], term uint8 [T, n, A], trunc uint8 [T, n, A], values float32 [T + 1, n, A]: rewards -0.0125 with
     10 % replaced from REWARD_EVENTS, values standard normal, `done_share` of the steps done - `flags`: "term" / "trunc" put every
-    done into that array alone, "both" spreads them over term, trunc and both at once"""
+    done into that array alone, "both" spreads them over term, trunc and both at once.  `byte`: None writes a set flag as 1; a
+    sequence of non-zero bytes writes each set flag as one of them, and where both flags are set term = 0x01 with trunc = 0xFE (no
+    bit in common).  The same steps are done either way."""
     rng = np.random.default_rng(seed)
     shape = (T, n, A)
     rewards = np.full(shape, -0.0125)
@@ -30,7 +35,28 @@ def gae_data(T, n, A, seed=0, flags="both", done_share=0.08):
         assert flags == "both", f"flags = {flags!r}"
         term[done & (kind != 1)] = 1
         trunc[done & (kind != 0)] = 1
+    if byte is not None:
+        assert all(0 < int(b) < 256 for b in byte), f"byte = {byte!r}"
+        both = (term != 0) & (trunc != 0)
+        for arr in (term, trunc):
+            arr[arr != 0] = rng.choice(np.array(byte, np.uint8), int((arr != 0).sum()))
+        term[both], trunc[both] = 0x01, 0xFE
     return rewards, term, trunc, values
+
+
+def gae_float32(rewards, term, trunc, values, gamma, lam):
+    """the advantages of host_gae's recurrence carried in float32 instead of float64: what the bits of a comparison must tell apart"""
+    f = np.float32
+    r32, V = np.asarray(rewards).astype(f), np.asarray(values, f)
+    done = (np.asarray(term) != 0) | (np.asarray(trunc) != 0)
+    g, gl = f(gamma), f(f(gamma) * f(lam))
+    A, out = np.zeros(r32.shape[1:], f), np.empty(r32.shape, f)
+    for t in range(r32.shape[0] - 1, -1, -1):
+        d = (r32[t] + np.where(done[t], f(0), g * V[t + 1])) - V[t]
+        A = d + np.where(done[t], f(0), gl * A)
+        assert A.dtype == f, "gae_float32: the recurrence left float32"
+        out[t] = A
+    return out
 
 
 def scalar_gae(rewards, term, trunc, values, gamma, lam):

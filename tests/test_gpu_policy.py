@@ -74,7 +74,10 @@ def test_every_cell(movable_levels, level, agents, scheme, mode):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# row tails: F = 283, 384, 385, 513 and, on the huge instance, 639
+# row tails: F = 283, 384, 385, 513 and, on the huge instance, 639.  What this shows: the float32 rows the step kernels write at those
+# F and their staging for the policy, on observation rows.  What it does not: the weights of a row's tail - observation rows are 0.0 in
+# about half their features, the last 16 and more included (test_policy_host.py states it), so the columns of W1 there never reach a
+# logit here.  test_gpu_policy_dense.py covers them, with dense rows through cz_policy_device at the same F.
 # ---------------------------------------------------------------------------------------------------------------------------
 
 TAILS = [("coop_test", "example_odd", 2, TWO, "scheme3", 283, 0)] + \

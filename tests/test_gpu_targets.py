@@ -9,7 +9,7 @@ import pytest
 
 from cooking_zoo_amd import _native, targets
 from policy_common import PolicyTraj, weights
-from targets_common import ACT_OUTSIDE, F32_SENT, GAMMA, LAM, bits32, gae_data, synthetic_logits
+from targets_common import ACT_OUTSIDE, DONE_BYTES, F32_SENT, GAMMA, LAM, bits32, gae_data, gae_float32, synthetic_logits
 from vec_common import COOP, CROWDED4, CallerStream, make_env, tables_of
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +97,54 @@ def test_gae_equals_the_host_model(handles, n, A):
             free(*d)
         adv.free()
         ret.free()
+
+
+def gae_against_the_model(env, ctx, T, n, A, r, te, tr, V):
+    adv, ret = Guarded(env, T, n * A), Guarded(env, T, n * A)
+    d = upload(env, r, te, tr, V)
+    env.gae_device(T, *d, adv.ptr, ret.ptr, gamma=GAMMA, lam=LAM, env_count=n)
+    env.sync()
+    want_adv, want_ret = targets.host_gae(r, te, tr, V, GAMMA, LAM)
+    for o, w, name in ((adv, want_adv, "advantages"), (ret, want_ret, "returns")):
+        bad = np.argwhere(o.get(ctx) != bits32(w).reshape(T, -1))
+        assert not len(bad), f"{ctx}: {name} differ in bits at (t, series) {bad[:6].tolist()}"
+        o.free()
+    free(*d)
+
+
+@pytest.mark.parametrize("n,A", [(37, 3), (549, 2)], ids=["37x3", "549x2"])
+def test_gae_done_is_any_non_zero_flag_byte(handles, n, A):
+    """the flags as bytes 2, 0x80 and 0xFF, and term = 0x01 with trunc = 0xFE where both are set: `!= 0` is the definition"""
+    for T in LENGTHS:
+        r, te, tr, V = gae_data(T, n, A, seed=T, done_share=0.2, byte=DONE_BYTES)
+        one = gae_data(T, n, A, seed=T, done_share=0.2)
+        assert np.array_equal(te != 0, one[1] != 0) and np.array_equal(tr != 0, one[2] != 0), "`byte` moved a flag"
+        if T >= 7:
+            assert ((te == 0x01) & (tr == 0xFE)).any(), "no step with term = 0x01 and trunc = 0xFE: the case shows nothing"
+            assert all(((te == b) & (tr == 0)).any() and ((tr == b) & (te == 0)).any() for b in DONE_BYTES), "a flag byte never stands alone"
+            assert ((te | tr) == 0).any(), "every step is done"
+        assert not ((te == 1) & (tr == 0)).any() and not (tr == 1).any(), "a flag written as 1 alone: that is the other tests' case"
+        gae_against_the_model(handles[A], f"flag bytes, T = {T}, {n} x {A}", T, n, A, r, te, tr, V)
+        if T == 16:                                                # ... and without the truncations array
+            gae_against_the_model(handles[A], f"flag bytes, T = {T}, {n} x {A}, no truncations", T, n, A, r, te, None, V)
+
+
+def test_gae_over_six_decades(handles):
+    """every series' rewards and values times 10^k, k from -3 .. 3: the float64 recurrence at other exponents, under the suite's bar
+    that the same recurrence in float32 gives other bits in at least 25 % of the advantages"""
+    n, A = 549, 2
+    k = np.random.default_rng(21).integers(-3, 4, (n, A))
+    assert len(np.unique(k)) == 7
+    for T in (7, 33):
+        r, te, tr, V = gae_data(T, n, A, seed=200 + T)
+        r = r * 10.0 ** k
+        V = (V.astype(np.float64) * 10.0 ** k).astype(np.float32)
+        adv, _ = targets.host_gae(r, te, tr, V, GAMMA, LAM)
+        share = float((bits32(adv) != bits32(gae_float32(r, te, tr, V, GAMMA, LAM))).mean())
+        print(f"six decades, T = {T}: {share:.1%} of the advantages differ from the float32 recurrence")
+        assert share >= 0.25, f"T = {T}: only {share:.1%} of the advantages differ from the float32 recurrence: the case shows nothing"
+        assert np.isfinite(adv).all() and float(np.abs(adv).max()) < 1e6
+        gae_against_the_model(handles[A], f"six decades, T = {T}", T, n, A, r, te, tr, V)
 
 
 @pytest.mark.parametrize("shape", [f"{d}x{w}" for d in (2, 4, 8, 16) for w in (64, 256)])
@@ -217,11 +265,14 @@ def test_refusals_launch_nothing(handles):
 # log-probabilities
 # ---------------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("which,rows", [(w, r) for w in (5, 4) for r in (1, 37, 549 * 3)], ids=lambda v: str(v))
+# (A = 3 and A = 1 do not divide the workgroup's 256 threads: a workgroup boundary falls inside an [A]-row, and k_logprob takes the
+# agent from i % A)
+@pytest.mark.parametrize("which,rows", [(w, r) for w in (5, 4) for r in (1, 37, 549 * 3)] + [(w, r) for w in (3, 1) for r in (37, 549 * 3)],
+                         ids=lambda v: str(v))
 def test_logprob_equals_the_host_model(handles, which, rows):
     env = handles[which]
     A, Cn = env.num_agents, env.num_actions
-    assert (A, Cn) == ((2, 5) if which == 5 else (4, 8))
+    assert (A, Cn) == ((2, 5) if which == 5 else (which, 8))
     lg = synthetic_logits(rows, A, Cn, seed=rows)
     rng = np.random.default_rng(rows)
     act = rng.integers(0, Cn, (rows, A)).astype(np.int32)
@@ -234,7 +285,8 @@ def test_logprob_equals_the_host_model(handles, which, rows):
     d_lg, d_act = upload(env, lg, act)
     lp, en = Guarded(env, rows, A), Guarded(env, rows, A)
     everyone = (0,) * A
-    for sets in (everyone, (None,) + everyone[1:], everyone[:-1] + (None,)):
+    left_out = sorted({0, A // 2, A - 1}) if A >= 2 else []        # the first, the middle or the last agent (one agent: nobody)
+    for sets in [everyone] + [everyone[:a] + (None,) + everyone[a + 1:] for a in left_out]:
         chosen = np.array([s is not None for s in sets])
         for outs in ((lp, en), (lp, None), (None, en)):
             lp.fill()

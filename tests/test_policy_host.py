@@ -15,7 +15,7 @@ import pytest
 from cooking_zoo_amd import policy
 from host_common import HEADER, INSTANCES, LIB, device_code  # noqa: F401  (device_code: the fixture)
 from oracle_binding import VecOracle
-from policy_common import ROLLOUT_POLICY, weights
+from policy_common import ROLLOUT_POLICY, dense_conditions, dense_rows, exact_logit_weights, logit_cases, logits_per_set, swap_columns, weights
 from vec_common import TWO, tables_of
 
 NEW_SYMBOLS = ["cz_load_policy_device", "cz_policy_sets", "cz_policy_device", "cz_rollout_policy"]
@@ -116,6 +116,50 @@ def test_logits_are_sensitive_to_the_summation_order(oracle_rows):
         share = float((want.view(np.uint32) != other.view(np.uint32)).mean())
         assert share >= 0.25, f"only {share:.1%} of the logits differ from the matrix-product form"
         assert int((want.argmax(-1) != other.argmax(-1)).sum()) <= len(x) // 50     # (actions barely notice: the logits are the check)
+
+
+def test_observation_rows_never_reach_the_last_columns_of_w1_and_dense_rows_do(oracle_rows):
+    """the gap the dense GPU test closes, as a fact of the data: the oracle's rows at F = 283 are 0.0 in the whole last quad (and in
+    about half their features), so exchanging two columns of W1 there leaves every expected logit as it was - a pack that did so
+    on the device would pass every comparison on such rows.  On dense_rows the same exchange changes every row."""
+    F = oracle_rows.shape[-1]
+    x = oracle_rows.reshape(-1, F)
+    assert F == 283 and (x[:, 280:] == 0).all(), "the oracle's rows reach the last quad: this test and the comment above test_row_tails are out of date"
+    used = int((x != 0).any(axis=0).sum())
+    assert used <= F * 6 // 10, f"{used} of {F} features are non-zero in some row"
+    w1, b1, w2, b2 = (w[0] for w in weights(F, 5, 1, 3, scale2=0.03))
+    other = swap_columns(w1, F - 2)
+    assert (other != w1).any()
+    bits = lambda rows, w: policy.host_logits(rows, w, b1, w2, b2).view(np.uint32)
+    assert np.array_equal(bits(x, other), bits(x, w1)), "the exchange shows on observation rows after all"
+    dense = dense_rows(6, 2, F, 1).reshape(-1, F)
+    assert (dense != 0).all() and all(len(np.unique(r)) == F for r in dense)
+    assert (bits(dense, other) != bits(dense, w1)).any(axis=-1).all(), "the exchange leaves a dense row's logits as they were"
+    W4 = weights(F, 5, 4, 3, scale2=0.03)
+    share = dense_conditions("F = 283", dense, W4, logits_per_set(dense, W4))
+    print(f"dense rows, F = 283: {share:.1%} of the logits differ from the matrix-product form")
+
+
+@pytest.mark.parametrize("Cn", [5, 8])
+def test_exact_logit_weights_give_their_logits_in_bits_for_any_row(oracle_rows, Cn):
+    F = oracle_rows.shape[-1]
+    rows = np.concatenate([oracle_rows.reshape(-1, F)[:8], dense_rows(4, 2, F, Cn).reshape(-1, F), -4.0 * dense_rows(1, 2, F, 9).reshape(-1, F)])
+    for name, (L, dead) in logit_cases(Cn).items():
+        assert L.dtype == np.float32 and L.shape == (Cn,)
+        w = exact_logit_weights(F, L, dead)
+        got = policy.host_logits(rows, *w)
+        assert (got.view(np.uint32) == L.view(np.uint32)).all(), f"{name}: the logits are not L in bits"
+        assert (policy.host_actions(got) == int(L.argmax())).all()
+        if dead:
+            assert (w[1] < 0).all() and (w[2] != 0).all() and (w[3] == L).all(), "dead: every hidden unit off, the logits from b2"
+    # the sampling rule on them, by hand: u just below 1 takes the last action with a share of the sum; ties split the draw range
+    pick = lambda L, u: int(policy.sample_from(L[None], np.array([u]))[0])
+    cases = logit_cases(Cn)
+    flat, tie, clamp, one = (cases[k][0] for k in ("flat", "tie3", "clamp", "one"))
+    assert [pick(flat, (c + 0.5) / Cn) for c in range(Cn)] == list(range(Cn))
+    assert pick(tie, 0.0) == 0 and pick(tie, 0.5) == 3 and pick(tie, 1.0 - 2.0 ** -53) == Cn - 1 and policy.host_actions(tie[None])[0] == 1
+    assert pick(clamp, 0.0) == 0 and pick(clamp, 1e-25) == 1     # 70 below the maximum: clamped to exp(-64), still a share of its own
+    assert all(pick(one, u) == Cn - 2 for u in (2.0 ** -53, 0.3, 1.0 - 2.0 ** -53))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

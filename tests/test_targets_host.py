@@ -11,7 +11,7 @@ import pytest
 
 from cooking_zoo_amd import policy, targets
 from host_common import HEADER, LIB, device_code  # noqa: F401  (device_code: the fixture)
-from targets_common import GAMMA, LAM, bits32, gae_data, scalar_gae, synthetic_logits
+from targets_common import GAMMA, LAM, bits32, gae_data, gae_float32, scalar_gae, synthetic_logits
 
 NEW_SYMBOLS = ["cz_gae_device", "cz_logprob_device"]
 
@@ -92,15 +92,7 @@ def test_advantages_are_sensitive_to_the_precision_of_the_recurrence():
     float64 arithmetic"""
     r, te, tr, V = gae_data(32, 4096, 1, seed=0)
     adv, _ = targets.host_gae(r, te, tr, V, GAMMA, LAM)
-    done = (te | tr) != 0
-    f = np.float32
-    r32, g, gl = r.astype(f), f(GAMMA), f(f(GAMMA) * f(LAM))
-    A, other = np.zeros(r.shape[1:], f), np.empty(r.shape, f)
-    for t in range(31, -1, -1):
-        d = (r32[t] + np.where(done[t], f(0), g * V[t + 1])) - V[t]
-        A = d + np.where(done[t], f(0), gl * A)
-        assert A.dtype == f
-        other[t] = A
+    other = gae_float32(r, te, tr, V, GAMMA, LAM)
     share = float((bits32(adv) != bits32(other)).mean())
     print(f"float32 recurrence: {share:.1%} of the advantages differ in bits")
     assert share >= 0.25, f"only {share:.1%} of the advantages differ from the float32 recurrence"
