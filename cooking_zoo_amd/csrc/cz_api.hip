@@ -284,6 +284,7 @@ struct cz_handle_s {
     hipEvent_t ev_rank_done = nullptr;
     float *d_policy = nullptr;             // cz_load_policy_device: POLICY_MAX_SETS packed weight sets (cz_policy.h), allocated on the first load
     int32_t n_policy_sets = 0;             // sets the last load filled; 0: no table
+    int32_t n_value_sets = 0;              // cz_load_value_device: sets whose value head (behind the sets, same allocation) the last load filled
     uint32_t *d_partner = nullptr;         // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
     int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
     int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
@@ -1267,6 +1268,8 @@ struct StepCall {
     // cz_rollout_policy (fused, float32 only): the packed sets and mode (policy_pack_sets), and the two outputs of its own - `actions`
     // above stays null, the launch plays no actions of the caller
     bool policy = false; uint32_t policy_packed = 0; int32_t *actions_out = nullptr; float *logits_out = nullptr;
+    // cz_rollout_policy_value: the values output float [T + 1][N][A] and the packed value sets (policy_pack_vsets) beside them
+    float *values_out = nullptr; uint32_t value_packed = 0;
 };
 enum ObsForm { OBS_F64, OBS_CODES, OBS_F32 };      // what a launch writes its observation as (OBS_CODES: float64 rows beside the codes if P.obs)
 
@@ -1298,6 +1301,7 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 }
 
 // Which kernel a launch gets (the same table is in DESIGN.md section 4).  `form` is resolve_step's; P.wt is decided by then.
+//   fused, OBS_F32, a policy call with values -> ROLLOUT_POLICY_VALUE (cz_rollout_policy_value)
 //   fused, OBS_F32, a policy call     -> ROLLOUT_POLICY       (cz_rollout_policy)
 //   fused, OBS_F32 and P.actions      -> ROLLOUT_ACTIONS_F32  (cz_rollout_actions_f32)
 //   fused, OBS_F32                    -> ROLLOUT_F32          (cz_rollout_f32)
@@ -1311,11 +1315,11 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 //                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
 //                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
 //   one step without P.actions        -> hipErrorInvalidValue
-static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c, bool policy = false) {
+static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c, bool policy = false, bool value = false) {
     c.lean = false;
     c.cfg = -1;
     if (policy) {
-        c.mode = ROLLOUT_POLICY;
+        c.mode = value ? ROLLOUT_POLICY_VALUE : ROLLOUT_POLICY;
         return fused && form == OBS_F32 ? hipSuccess : hipErrorInvalidValue;
     }
     if (fused && form == OBS_F32) c.mode = P.actions ? ROLLOUT_ACTIONS_F32 : ROLLOUT_F32;
@@ -1408,7 +1412,9 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
         HIPCHK(h, hipEventRecord(e0, stream));
     }
     StepChoice choice;
-    const hipError_t chosen = choose_step(h, P, fused, form, choice, call.policy);
+    const hipError_t chosen = choose_step(h, P, fused, form, choice, call.policy, call.values_out != nullptr);
+    // (the values pointer travels beside the block, not in it: launch_policy_step_kernel in cz_kernels.h)
+    if (call.values_out) choice.values = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(call.values_out) | ((uintptr_t)call.value_packed << 48));
     h->last_step_lean = choice.lean ? 1 : 0;
     h->last_step_mode = choice.mode;
     h->last_step_variant = !choice.lean ? -1 : choice.cfg < 0 ? 0 : (0x100 | P.R | (P.end_all << 4) | (P.walk_touches << 5));
@@ -2299,8 +2305,10 @@ extern "C" int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d
     const size_t per_set = policy_set_floats(h->P.F);
     if (!h->d_policy) {
         if (caller_capturing(h)) return fail(h, "cz_load_policy_device: the handle's first load allocates the table: call it once outside the capture");
-        HIPCHK(h, hipMalloc(&h->d_policy, per_set * POLICY_MAX_SETS * sizeof(float)));
+        // (room for the value heads behind the sets: cz_load_value_device; zeroed, so that no launch reads what nobody wrote)
+        HIPCHK(h, hipMalloc(&h->d_policy, (size_t)policy_table_floats(h->P.F) * sizeof(float)));
         if (reinterpret_cast<uintptr_t>(h->d_policy) >> 48) return fail(h, "cz_load_policy_device: device address above 2^48");
+        HIPCHK(h, hipMemsetAsync(h->d_policy + policy_value_offset(h->P.F), 0, POLICY_VALUE_FLOATS * sizeof(float), h->stream));
     }
     const uint32_t total = (uint32_t)(per_set * (size_t)n_sets);
     hipLaunchKernelGGL((k_policy_pack<0>), dim3((total + 255u) / 256u), dim3(256), 0, h->stream, h->d_policy, n_sets, h->P.F, cz_num_actions(h),
@@ -2310,6 +2318,37 @@ extern "C" int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d
     return 0;
 }
 extern "C" int32_t cz_policy_sets(cz_handle h) { return h ? h->n_policy_sets : -1; }
+// Loads the value heads of sets 0 .. n_sets-1 from DEVICE memory in torch.nn.Linear(64, 1)'s layouts - wv float32 [n][64], bv [n][1] -
+// with one repack launch on the handle's stream (legal inside a capture).  The heads live in the policy table's allocation, which
+// cz_load_policy_device owns: refused before the first such call.  Heads past n_sets are zeroed.
+extern "C" int cz_load_value_device(cz_handle h, int32_t n_sets, const float *d_wv, const float *d_bv) {
+    if (!h) return fail(nullptr, "null handle");
+    if (n_sets < 1 || n_sets > POLICY_MAX_SETS) return fail(h, "cz_load_value_device: n_sets is %d, not 1..%d", n_sets, POLICY_MAX_SETS);
+    if (!d_wv || !d_bv) return fail(h, "cz_load_value_device: a weight pointer is null");
+    if (!h->d_policy) return fail(h, "cz_load_value_device: no weight table yet: cz_load_policy_device allocates it");
+    if (set_device(h)) return 1;
+    hipLaunchKernelGGL((k_value_pack<0>), dim3(1), dim3(320), 0, h->stream, h->d_policy + policy_value_offset(h->P.F), n_sets, d_wv, d_bv);
+    HIPCHK(h, hipGetLastError());
+    h->n_value_sets = n_sets;
+    return 0;
+}
+extern "C" int32_t cz_value_sets(cz_handle h) { return h ? h->n_value_sets : -1; }
+// `vsets` of a value call, checked: the packed form, or -1 after fail()
+static int64_t check_value_call(cz_handle h, const char *who, uint32_t vsets, int *with_set) {
+    if (!h->d_policy || h->n_policy_sets == 0) { fail(h, "%s: no weight table loaded (cz_load_policy_device)", who); return -1; }
+    const int32_t usable = h->n_policy_sets < h->n_value_sets ? h->n_policy_sets : h->n_value_sets;
+    *with_set = 0;
+    for (int a = 0; a < h->P.A; ++a) {
+        const uint32_t s = (vsets >> (8 * a)) & 0xFFu;
+        if (s == POLICY_NONE) continue;
+        if (s >= (uint32_t)usable) {
+            fail(h, "%s: agent %d asks for the value head of set %u, but %d sets and %d value heads are loaded", who, a, s, h->n_policy_sets, h->n_value_sets);
+            return -1;
+        }
+        ++*with_set;
+    }
+    return (int64_t)policy_pack_vsets(vsets, h->P.A);
+}
 // `sets` and `mode` of a policy call, checked: the packed form, or -1 after fail()
 static int64_t check_policy_call(cz_handle h, const char *who, uint32_t sets, int32_t mode, bool need_one) {
     if (!h->d_policy || h->n_policy_sets == 0) { fail(h, "%s: no weight table loaded (cz_load_policy_device)", who); return -1; }
@@ -2346,6 +2385,27 @@ extern "C" int cz_policy_device(cz_handle h, int64_t b, int64_t c, const float *
     }));
     return 0;
 }
+// The value heads on rows of the caller (policy.host_value): d_obs32 float32 [rows][A][F] -> d_values float32 [rows][A]; `rows` counts
+// [A][F]-rows as in cz_logprob_device and is not tied to the batch.  `vsets`: agent a's value set in byte a, 0xFF = none - that agent's
+// entries are left untouched.  One launch of k_value on the handle's stream (legal inside a capture); no record is read.
+extern "C" int cz_value_device(cz_handle h, int64_t rows, const float *d_obs32, uint32_t vsets, float *d_values) {
+    if (ready(h)) return 1;
+    if (rows < 1 || rows > (int64_t)0x7FFFFFFF) return fail(h, "cz_value_device: rows is %lld, not 1..%lld", (long long)rows, (long long)0x7FFFFFFF);
+    if (!d_obs32 || !d_values) return fail(h, "cz_value_device: the rows or values pointer is null");
+    int with_set = 0;
+    const int64_t vpacked = check_value_call(h, "cz_value_device", vsets, &with_set);
+    if (vpacked < 0) return 1;
+    if (!with_set) return fail(h, "cz_value_device: every agent's byte of vsets is 0xFF");
+    if (set_device(h)) return 1;
+    const int A = h->P.A, F = h->P.F;
+    const size_t lds = (size_t)A * (size_t)policy_quads(F) * 16u;
+    const ValueArgs G{d_obs32, h->d_policy, F, (uint32_t)vpacked, d_values};
+    HIPCHK(h, with_agents(A, [&](auto na) {
+        hipLaunchKernelGGL((k_value<decltype(na)::value>), dim3((unsigned)rows), dim3(64), lds, h->stream, G);
+        return hipGetLastError();
+    }));
+    return 0;
+}
 // cz_rollout_f32 with the policy in front of every fused step (k_step<..., ROLLOUT_POLICY>): agent a's action at step t is the policy's on
 // the env's float32 row before that step - for t = 0 what cz_observe_device_f32 would write at launch, later row t - 1 of the trajectory,
 // the row of a reset pass included - with the draw keyed by step0 + t; agents whose byte of `sets` is 0xFF play cz_rollout's stream,
@@ -2359,6 +2419,28 @@ extern "C" int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t 
     StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
     c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
     c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
+    return launch_step(h, c);
+}
+// cz_rollout_policy plus the value heads (k_step<..., ROLLOUT_POLICY_VALUE>): d_values float32 [T + 1][N][A], required.  Row t holds the
+// value of agent a's set in byte a of `vsets` (0xFF: none, entries untouched) on the row the policy reads in front of step t, row T the
+// value on the row step T - 1 staged - the row a following launch's step 0 reads - so d_values goes into cz_gae_device as it is.
+// `vsets` is independent of `sets`; every agent may be at 0xFF in `sets` (values under the action stream) as long as one has a value
+// set.  Everything else is what cz_rollout_policy leaves for the same arguments.
+extern "C" int cz_rollout_policy_value(cz_handle h, int32_t T, uint32_t sets, uint32_t vsets, int32_t mode, uint64_t seed, uint32_t step0, float *d_obs32,
+                                       int32_t *d_actions, float *d_logits, float *d_values, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
+    if (begin_device_call(h, T >= 1 && d_obs32 && d_values, "cz_rollout_policy_value: T must be >= 1 and the float32 trajectory and values pointers non-null",
+                          "cz_rollout_policy_value", T)) return 1;
+    if (reinterpret_cast<uintptr_t>(d_values) >> 48) return fail(h, "cz_rollout_policy_value: the values pointer is a device address above 2^48");
+    const int64_t packed = check_policy_call(h, "cz_rollout_policy_value", sets, mode, false);
+    if (packed < 0) return 1;
+    int with_value = 0;
+    const int64_t vpacked = check_value_call(h, "cz_rollout_policy_value", vsets, &with_value);
+    if (vpacked < 0) return 1;
+    if (!with_value && ((uint32_t)packed & 0xFFFu) == 0xFFFu) return fail(h, "cz_rollout_policy_value: every agent is at 0xFF in both sets and vsets (that is cz_rollout_f32)");
+    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
+    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
+    c.values_out = d_values; c.value_packed = (uint32_t)vpacked;
     return launch_step(h, c);
 }
 

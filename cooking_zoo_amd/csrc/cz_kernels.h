@@ -69,12 +69,14 @@ enum StepMode : int {
                               // ROLLOUT_ACTIONS is one; always writes row t (the in-place form of fused ring runs is not offered in float32)
     ROLLOUT_POLICY = 9,       // ROLLOUT_F32 whose actions are the MLP policy's (cz_policy.h) on the env's float32 row before the step, staged
                               // in LDS next to its store (cz_rollout_policy): agents without a weight set play the on-device stream
+    ROLLOUT_POLICY_VALUE = 10,  // ROLLOUT_POLICY that also writes the value heads' values float[T + 1][N][A] (cz_rollout_policy_value): row t
+                              // on the row the policy reads in front of step t, row T on the row the last step staged
 };
 template <int MODE, bool LEAN = false>
 struct StepTraits {
-    static_assert(MODE >= STEP && MODE <= ROLLOUT_POLICY && (!LEAN || MODE == STEP), "no such variant");
+    static_assert(MODE >= STEP && MODE <= ROLLOUT_POLICY_VALUE && (!LEAN || MODE == STEP), "no such variant");
     static constexpr bool fused = MODE == ROLLOUT || MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY ||
-                                  MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY;   // P.T steps per launch
+                                  MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY || MODE == ROLLOUT_POLICY_VALUE;   // P.T steps per launch
     static constexpr bool ext_actions = MODE == ROLLOUT_ACTIONS || MODE == ROLLOUT_ACTIONS_F32;   // a fused launch that reads the caller's actions
     static constexpr bool codes = MODE == STEP_CODES || MODE == ROLLOUT_CODES || MODE == ROLLOUT_CODES_ONLY;   // writes the compact observation
     // a fused rollout that writes codes ONLY (cz_rollout_compact without a float64 trajectory).  Without the float64 path - its six
@@ -83,11 +85,15 @@ struct StepTraits {
     static constexpr bool codes_only = MODE == ROLLOUT_CODES_ONLY;
     // the float32 rows: np.float32 of the float64 feature (round to nearest even), gathered from a float32 copy of the table that the
     // workgroup makes while it stages the table into LDS - no arithmetic on values, no float64 path beside it
-    static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY;
+    static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY || MODE == ROLLOUT_POLICY_VALUE;
     // the policy in front of every fused step.  A float32 fused launch leaves three slots of the argument block unused, and the block must
     // not grow: `actions` carries the int32 [T][N][A] actions OUTPUT, `obs` the float [T][N][A][C] logits output (either may be null) and
     // `marks_out` the weight table with policy_pack_sets in the 16 bits above a device address (resolve_step in cz_api.hip puts them there)
-    static constexpr bool policy = MODE == ROLLOUT_POLICY;
+    static constexpr bool policy = MODE == ROLLOUT_POLICY || MODE == ROLLOUT_POLICY_VALUE;
+    // ... and the value heads beside it.  The values pointer float [T + 1][N][A] needs a slot too: the block's own `actions` is dead in
+    // every step kernel - the leading scalar e_actions stands in for it - so the launch puts the pointer there, with policy_pack_vsets
+    // in the 16 bits above the address (launch_policy_step_kernel), and the kernel reads it through the late block
+    static constexpr bool value = MODE == ROLLOUT_POLICY_VALUE;
     static constexpr bool f64 = !codes_only && !f32;                                     // carries the float64 observation path
     // The CodesPrefetch words (the b128 descriptor loads of the codes and of the float32 rows): fetched once behind the prologue and held
     // in registers - a fused launch fetches them again only when a reset pass has moved the env to another layout - or, desc_per_step,
@@ -952,16 +958,39 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             const size_t prow = (size_t)t * (size_t)Pt.N + (size_t)env;
             float *const lrow = Pt.obs ? reinterpret_cast<float *>(Pt.obs) + prow * (size_t)(NA * C) : nullptr;
             const int Fq = policy_quads(Pt.F);
+            // ROLLOUT_POLICY_VALUE: agent a's value on the same row goes to row t of the values - from the policy's hidden vector where
+            // the agent's two sets are one, from a second hidden pass where they differ
+            uint32_t vpk = 0xFFFu;
+            float *vrow = nullptr;
+            if constexpr (V::value) {
+                const uint64_t vslot = (uint64_t)reinterpret_cast<uintptr_t>(CZ_LATE_STEP()->actions);
+                vpk = (uint32_t)(vslot >> 48);
+                vrow = reinterpret_cast<float *>(static_cast<uintptr_t>(vslot & 0xFFFFFFFFFFFFull)) + prow * (size_t)NA;
+            }
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-                const uint32_t si = (pk >> (3 * a)) & 7u;
+                const uint32_t si = (pk >> (3 * a)) & 7u, vi = (vpk >> (3 * a)) & 7u;
                 if (si != 7u) {
                     int action;
                     float mylogit;
-                    policy_act<C>(table + (size_t)si * policy_set_floats(Pt.F), Fq, xrow + (uint32_t)(a * 4 * Fq), lane, (pk >> 12) & 1u, Pt.seed,
-                                  env_global, Pt.step0 + (uint32_t)t, a, action, mylogit);
+                    const float *const set = table + (size_t)si * policy_set_floats(Pt.F);
+                    const float hid = policy_hidden(set, Fq, xrow + (uint32_t)(a * 4 * Fq), lane);
+                    policy_heads<C>(set, Fq, hid, lane, (pk >> 12) & 1u, Pt.seed, env_global, Pt.step0 + (uint32_t)t, a, action, mylogit);
                     acts = lane == a ? (uint32_t)action : acts;
                     if (lrow && lane < C) lrow[a * C + lane] = mylogit;
+                    if constexpr (V::value) {
+                        if (vi == si) {
+                            const float v = policy_value(table, Pt.F, vi, hid, lane);
+                            if (lane == 0) vrow[a] = v;
+                        }
+                    }
+                }
+                if constexpr (V::value) {
+                    if (vi != 7u && vi != si) {
+                        const float hid = policy_hidden(table + (size_t)vi * policy_set_floats(Pt.F), Fq, xrow + (uint32_t)(a * 4 * Fq), lane);
+                        const float v = policy_value(table, Pt.F, vi, hid, lane);
+                        if (lane == 0) vrow[a] = v;
+                    }
                 }
             }
             // (cz_rollout_policy checks that T * N * A * 8 fits 32 bits)
@@ -1069,6 +1098,24 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
         }
         CZ_STAMP(6);
     }
+    if constexpr (V::value) {
+        // the bootstrap: row T of the values, on the row the last step staged - what a following launch's step 0 would read
+        const auto kp = CZ_LATE_STEP();
+        const uint64_t slot = (uint64_t)reinterpret_cast<uintptr_t>(kp->marks_out), vslot = (uint64_t)reinterpret_cast<uintptr_t>(kp->actions);
+        const float *const table = reinterpret_cast<const float *>(static_cast<uintptr_t>(slot & 0xFFFFFFFFFFFFull));
+        const uint32_t vpk = (uint32_t)(vslot >> 48);
+        float *const vrow = reinterpret_cast<float *>(static_cast<uintptr_t>(vslot & 0xFFFFFFFFFFFFull)) + ((size_t)T * (size_t)P.N + (size_t)env) * (size_t)NA;
+        const int F = kp->F, Fq = policy_quads(F);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const uint32_t vi = (vpk >> (3 * a)) & 7u;
+            if (vi != 7u) {
+                const float hid = policy_hidden(table + (size_t)vi * policy_set_floats(F), Fq, xrow + (uint32_t)(a * 4 * Fq), lane);
+                const float v = policy_value(table, F, vi, hid, lane);
+                if (lane == 0) vrow[a] = v;
+            }
+        }
+    }
     store_env(P, e, cx, rec, cells_dirty, objs_dirty, header_dirty);
     if (lane < NA) stg<double>(retp, (uint32_t)lane * 8u, ret);
     CZ_STAMP(7);
@@ -1121,7 +1168,7 @@ __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean_cfg(uint3
 }
 
 // cfg: with `lean`, the row of CZ_LEAN_CFGS whose k_step_lean_cfg the launch takes, or -1: k_step_lean
-struct StepChoice { StepMode mode; bool lean; int cfg; };       // which variant a launch takes (choose_step, cz_api.hip)
+struct StepChoice { StepMode mode; bool lean; int cfg; const void *values = nullptr; };       // which variant a launch takes (choose_step, cz_api.hip)
 // The k_step_lean_cfg kernels of the small instance: X(agents, action scheme, recipes, end_all, walk_touches), nine kernels, all under
 // scheme3.  Two agents - the headline workload and BASELINE configs 3 and 4 are (2, 3, 2, 0, 0) - with every recipe count a handle of
 // two agents can have (cz_create: agents <= recipes <= 4) and both end conditions; one recipe means one agent; walk_touches = 1 where
@@ -1193,8 +1240,9 @@ inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) 
 constexpr size_t LDS_PER_WORKGROUP = 160u << 10;
 template <int CPL>
 inline size_t policy_rows_bytes(const Params &P) { return (size_t)envs_per_wg<CPL>() * (size_t)P.A * (size_t)policy_quads(P.F) * 16u; }
+// (`values`: ROLLOUT_POLICY_VALUE's values pointer with policy_pack_vsets above it, which travels in the block's dead `actions` slot)
 template <int CPL, class K>
-inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream_t st) {
+inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream_t st, const void *values = nullptr) {
     const size_t rows = policy_rows_bytes<CPL>(P);
     hipFuncAttributes attr;
     hipError_t err = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
@@ -1204,7 +1252,9 @@ inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream
         err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows);
         if (err != hipSuccess) return err;
     }
-    return launch_step_kernel<CPL>(kernel, P, P, st, rows);
+    Params B = P;
+    if (values) B.actions = static_cast<const int32_t *>(values);
+    return launch_step_kernel<CPL>(kernel, P, B, st, rows);
 }
 
 }  // namespace cz

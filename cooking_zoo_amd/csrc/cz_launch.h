@@ -67,6 +67,9 @@ struct Inst {
                 case ROLLOUT_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_F32>, P, st);
                 case ROLLOUT_ACTIONS_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_ACTIONS_F32>, P, st);
                 case ROLLOUT_POLICY: return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY>, P, st);
+                case ROLLOUT_POLICY_VALUE:
+                    if (!c.values) return hipErrorInvalidValue;
+                    return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY_VALUE>, P, st, c.values);
                 }
                 return hipErrorInvalidValue;
             });

@@ -1,7 +1,8 @@
 // cz_policy.h -- the MLP policy the library evaluates itself (definition and host model: cooking_zoo_amd/policy.py): the packed
-// weight table, cz_exp, and policy_act, the one device function that goes from a float32 row in LDS to an action.  k_policy
-// (cz_query.h) and k_step<..., ROLLOUT_POLICY> (cz_kernels.h) both call it, so the launch of its own and the fused rollout cannot differ.
-// Beside them cz_log and policy_logprob, the log-probability and entropy of the distribution policy_act samples from (k_logprob;
+// weight table, cz_exp, and the device functions that go from a float32 row in LDS to an action and a value: policy_hidden, policy_heads
+// and policy_value.  k_policy and k_value (cz_query.h) and k_step<..., ROLLOUT_POLICY / ROLLOUT_POLICY_VALUE> (cz_kernels.h) all call
+// them, so the launches of their own and the fused rollouts cannot differ.
+// Beside them cz_log and policy_logprob, the log-probability and entropy of the distribution policy_heads samples from (k_logprob;
 // definition: cooking_zoo_amd/targets.py).
 #pragma once
 #include "cz_device.h"
@@ -21,6 +22,11 @@ __host__ __device__ inline int policy_quads(int F) { return (F + 3) >> 2; }
 __host__ __device__ inline uint32_t policy_set_floats(int F) {
     return (uint32_t)policy_quads(F) * 256u + POLICY_HIDDEN + POLICY_MAX_ACTIONS * POLICY_HIDDEN + POLICY_MAX_ACTIONS;
 }
+// Behind the POLICY_MAX_SETS sets, in the same allocation: the value heads (cz_load_value_device), wv [4][64] then bv [4].  A set's
+// value head reads that set's hidden vector.
+__host__ __device__ inline uint32_t policy_value_offset(int F) { return POLICY_MAX_SETS * policy_set_floats(F); }
+constexpr uint32_t POLICY_VALUE_FLOATS = POLICY_MAX_SETS * POLICY_HIDDEN + POLICY_MAX_SETS;
+__host__ __device__ inline uint32_t policy_table_floats(int F) { return policy_value_offset(F) + POLICY_VALUE_FLOATS; }
 // `sets` (agent a's set in byte a, 0xFF none) and the mode in 13 bits: three bits per agent, 7 = none, mode in bit 12
 __host__ __device__ inline uint32_t policy_pack_sets(uint32_t sets, uint32_t mode, int A) {
     uint32_t pk = (mode & 1u) << 12;
@@ -30,6 +36,9 @@ __host__ __device__ inline uint32_t policy_pack_sets(uint32_t sets, uint32_t mod
     }
     return pk;
 }
+
+// `vsets` (agent a's value set in byte a, 0xFF none) in 12 bits, three per agent as above
+__host__ __device__ inline uint32_t policy_pack_vsets(uint32_t vsets, int A) { return policy_pack_sets(vsets, 0u, A); }
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
 // the float32 rows a policy reads, in LDS: per env A rows of 4 * policy_quads(F) floats, the tail zeroed (sized by the launch)
@@ -63,7 +72,7 @@ __host__ __device__ inline double policy_log(double S) {
     return y;
 }
 
-// The softmax policy_act samples from, as log-probabilities (targets.host_logprob): the C logits of one row -> the float64
+// The softmax policy_heads samples from, as log-probabilities (targets.host_logprob): the C logits of one row -> the float64
 // log-probability of `action` (0.0 for an action outside 0 .. C-1) and the entropy, each rounded to float32 by the caller.
 template <int C>
 __host__ __device__ __forceinline__ void policy_logprob(const float (&logit)[C], int action, double &logp, double &entropy) {
@@ -105,15 +114,11 @@ __device__ __forceinline__ float policy_butterfly(float p) {
     return p;
 }
 
-// One agent's action from its row: `set` the agent's weight set (wave-uniform), `x` the row in LDS (4 * Fq floats, 16-byte aligned,
-// zero behind F), C the action count.  Every lane returns the same action; lane c < C returns logit c in `mylogit`.
-// The draw of POLICY_SAMPLE is spawn_uniform(seed, global env id, step, 0x300 + agent, 0).
-template <int C>
-__device__ __forceinline__ void policy_act(const float *__restrict__ set, int Fq, const float *x, int lane, uint32_t mode, uint64_t seed,
-                                           int64_t env_global, uint32_t step, int agent, int &action, float &mylogit) {
-    static_assert(C >= 1 && C <= POLICY_MAX_ACTIONS, "action count");
-    const float *const b1 = set + (uint32_t)Fq * 256u, *const w2 = b1 + POLICY_HIDDEN, *const b2 = w2 + POLICY_MAX_ACTIONS * POLICY_HIDDEN;
-    // hidden layer, lane = unit: one rounding per feature, features ascending
+// The hidden layer of one row (steps 1-2 of policy.py): `set` a weight set (wave-uniform), `x` the row in LDS (4 * Fq floats, 16-byte
+// aligned, zero behind F).  Lane j returns h_j.
+__device__ __forceinline__ float policy_hidden(const float *__restrict__ set, int Fq, const float *x, int lane) {
+    const float *const b1 = set + (uint32_t)Fq * 256u;
+    // lane = unit: one rounding per feature, features ascending
     float acc = b1[lane];
 #pragma unroll 4
     for (int q = 0; q < Fq; ++q) {
@@ -124,7 +129,16 @@ __device__ __forceinline__ void policy_act(const float *__restrict__ set, int Fq
         acc = __builtin_fmaf(w.z, v.z, acc);
         acc = __builtin_fmaf(w.w, v.w, acc);
     }
-    const float hid = acc > 0.0f ? acc : 0.0f;
+    return acc > 0.0f ? acc : 0.0f;
+}
+
+// The action heads on a hidden vector (steps 3-5): C the action count.  Every lane returns the same action; lane c < C returns
+// logit c in `mylogit`.  The draw of POLICY_SAMPLE is spawn_uniform(seed, global env id, step, 0x300 + agent, 0).
+template <int C>
+__device__ __forceinline__ void policy_heads(const float *__restrict__ set, int Fq, float hid, int lane, uint32_t mode, uint64_t seed,
+                                             int64_t env_global, uint32_t step, int agent, int &action, float &mylogit) {
+    static_assert(C >= 1 && C <= POLICY_MAX_ACTIONS, "action count");
+    const float *const w2 = set + (uint32_t)Fq * 256u + POLICY_HIDDEN, *const b2 = w2 + POLICY_MAX_ACTIONS * POLICY_HIDDEN;
     float logit[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) logit[c] = policy_butterfly(w2[c * POLICY_HIDDEN + lane] * hid) + b2[c];
@@ -152,6 +166,12 @@ __device__ __forceinline__ void policy_act(const float *__restrict__ set, int Fq
         for (int c = C - 2; c >= 0; --c) pick = S[c] > thr ? c : pick;
         action = pick;
     }
+}
+
+// The value head of set `vs` on that set's hidden vector (step 3b): one more row of the output layer.  Every lane returns the value.
+__device__ __forceinline__ float policy_value(const float *__restrict__ table, int F, uint32_t vs, float hid, int lane) {
+    const float *const heads = table + policy_value_offset(F);
+    return policy_butterfly(heads[vs * POLICY_HIDDEN + (uint32_t)lane] * hid) + heads[POLICY_MAX_SETS * POLICY_HIDDEN + vs];
 }
 
 }  // namespace cz

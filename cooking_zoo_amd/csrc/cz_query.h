@@ -1073,7 +1073,7 @@ struct PolicyArgs {
     int32_t *actions;              // [count][A] or null
     float *logits;                 // [count][A][C] or null
 };
-// One wavefront per env: the env's rows go to LDS (zero behind F), then policy_act per agent with a weight set; the entries of the
+// One wavefront per env: the env's rows go to LDS (zero behind F), then policy_hidden and policy_heads per agent with a weight set; the entries of the
 // other agents are left as they are in both outputs.
 template <int NA>
 __global__ __launch_bounds__(64) void k_policy(const PolicyArgs G) {
@@ -1095,11 +1095,56 @@ __global__ __launch_bounds__(64) void k_policy(const PolicyArgs G) {
         float mylogit;
         const float *const set = G.table + (size_t)si * policy_set_floats(G.F);
         const uint32_t mode = (G.packed >> 12) & 1u;
-        if (G.C == 5) policy_act<5>(set, Fq, x + a * 4 * Fq, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
-        else policy_act<8>(set, Fq, x + a * 4 * Fq, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
+        const float hid = policy_hidden(set, Fq, x + a * 4 * Fq, lane);
+        if (G.C == 5) policy_heads<5>(set, Fq, hid, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
+        else policy_heads<8>(set, Fq, hid, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
         if (G.actions && lane == 0) G.actions[i * NA + a] = action;
         if (G.logits && lane < G.C) G.logits[(i * NA + a) * (size_t)G.C + lane] = mylogit;
     }
+}
+
+// ---- the value head as a launch of its own (cz_value_device; definition: policy.py step 3b).  Rows of the caller, no record read.
+struct ValueArgs {
+    const float *obs32;            // [rows][A][F]
+    const float *table;            // the packed weight sets with the value heads behind them
+    int32_t F;
+    uint32_t vpacked;              // policy_pack_vsets: every agent's value set
+    float *values;                 // [rows][A]
+};
+// One wavefront per [A][F]-row, in the shape of k_policy: the rows go to LDS (zero behind F), then policy_hidden and policy_value per
+// agent with a value set; the entries of the other agents are left as they are.
+template <int NA>
+__global__ __launch_bounds__(64) void k_value(const ValueArgs G) {
+    const int lane = (int)threadIdx.x;
+    const size_t i = blockIdx.x;
+    const int Fq = policy_quads(G.F);
+    float *const x = reinterpret_cast<float *>(policy_rows);
+    const float *const src = G.obs32 + i * (size_t)(NA * G.F);
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+        for (int f = lane; f < 4 * Fq; f += 64) x[a * 4 * Fq + f] = f < G.F ? src[(size_t)a * G.F + f] : 0.0f;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+        const uint32_t vi = (G.vpacked >> (3 * a)) & 7u;
+        if (vi == 7u) continue;
+        const float hid = policy_hidden(G.table + (size_t)vi * policy_set_floats(G.F), Fq, x + a * 4 * Fq, lane);
+        const float v = policy_value(G.table, G.F, vi, hid, lane);
+        if (lane == 0) G.values[i * NA + a] = v;
+    }
+}
+// torch's layouts - wv [n][64], bv [n][1] - into the value heads behind the sets (cz_policy.h): one thread per float of them; heads
+// past n_sets are zeroed
+template <int UNUSED = 0>
+__global__ __launch_bounds__(320) void k_value_pack(float *__restrict__ heads, int32_t n_sets, const float *__restrict__ wv,
+                                                                    const float *__restrict__ bv) {
+    const uint32_t idx = threadIdx.x, wv_end = POLICY_MAX_SETS * POLICY_HIDDEN;
+    if (idx >= POLICY_VALUE_FLOATS) return;
+    float v = 0.0f;
+    if (idx < wv_end) { if ((idx >> 6) < (uint32_t)n_sets) v = wv[idx]; }
+    else if (idx - wv_end < (uint32_t)n_sets) v = bv[idx - wv_end];
+    heads[idx] = v;
 }
 // torch's layouts - W1 [n][64][F], b1 [n][64], W2 [n][C][64], b2 [n][C] - into the table's (cz_policy.h): one thread per float of it
 template <int UNUSED = 0>

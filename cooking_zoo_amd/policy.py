@@ -1,5 +1,6 @@
-"""The MLP policy the library evaluates on the device (cz_load_policy_device, cz_policy_device, cz_rollout_policy; device code:
-csrc/cz_policy.h), as an arithmetic definition numpy reproduces bit for bit.
+"""The MLP policy the library evaluates on the device (cz_load_policy_device, cz_policy_device, cz_rollout_policy; the critic:
+cz_load_value_device, cz_value_device, cz_rollout_policy_value; device code: csrc/cz_policy.h), as an arithmetic definition numpy
+reproduces bit for bit.
 
 A weight set is the parameters of `Sequential(Linear(F, 64), ReLU(), Linear(64, C))` in torch's own layout: W1 float32 [64][F],
 b1 float32 [64], W2 float32 [C][64], b2 float32 [C]; F is the handle's row length, C its action count, the hidden width is 64 -
@@ -9,6 +10,13 @@ one lane of a wavefront per unit.  For one float32 row x[0..F):
   2. h_j = acc_j > 0 ? acc_j : 0.
   3. per action c: p_j = W2[c][j] * h_j (one float32 rounding), six butterfly levels p_j = p_j + p_(j xor 2^k), k = 0..5, each a
      float32 add - the adjacent-pair tree `p = p[..., 0::2] + p[..., 1::2]` applied six times - and logit_c = p + b2[c].
+  3b. A weight set may carry a value head, `Linear(64, 1)` in torch's layout: wv float32 [64] (`weight[0]`) and bv float32 [1].
+     With h_j of steps 1-2: p_j = wv[j] * h_j (one float32 rounding), the same six butterfly levels, value = p + bv - exactly the
+     arithmetic of one logit (`host_value`).  Every policy-or-value call takes `vsets` beside `sets`, agent a's byte: the weight set
+     whose W1, b1 and value head give agent a's value, 0xFF = none (that agent's entries are left untouched).  It is independent of
+     `sets`: a shared trunk is vsets == sets, a separate critic is another weight set whose action head is never used, and an agent on
+     the action stream may have a value.  Where an agent's two bytes are equal the device computes the hidden vector once, where they
+     differ it makes a second pass: the bits are the same either way.
   4. GREEDY: the smallest c with the largest logit.
   5. SAMPLE, in float64 with every operation rounded on its own: z_c = logit_c - max, e_c = cz_exp(max(z_c, -64)), running sums
      S_0 = e_0, S_c = S_(c-1) + e_c, thr = u * S_(C-1); the action is the smallest c with S_c > thr, or C-1 if there is none.
@@ -78,6 +86,23 @@ def cz_exp(z):
     return np.ldexp(p, k.astype(np.int64))
 
 
+def host_hidden(x, w1, b1):
+    """steps 1-2: float32 rows x [..., F] -> the float32 hidden vector [..., 64]"""
+    F = x.shape[-1]
+    acc = np.broadcast_to(b1, x.shape[:-1] + (HIDDEN,)).copy()
+    for f in range(F):
+        acc = fmaf32(w1[:, f], x[..., f:f + 1], acc)
+    return np.where(acc > 0, acc, np.float32(0))
+
+
+def host_heads(h, w2, b2):
+    """step 3: the hidden vector [..., 64] and output rows w2 [C, 64], b2 [C] -> float32 [..., C]"""
+    p = w2 * h[..., None, :]                                   # [..., C, 64], one float32 rounding each
+    for _ in range(6):
+        p = p[..., 0::2] + p[..., 1::2]
+    return (p[..., 0] + b2).astype(np.float32)
+
+
 def host_logits(x, w1, b1, w2, b2):
     """float32 rows x [..., F] -> float32 logits [..., C] of one weight set, bit for bit the device's"""
     x = np.asarray(x, np.float32)
@@ -85,14 +110,19 @@ def host_logits(x, w1, b1, w2, b2):
     F = x.shape[-1]
     if w1.shape != (HIDDEN, F) or b1.shape != (HIDDEN,) or w2.ndim != 2 or w2.shape[1] != HIDDEN or b2.shape != (w2.shape[0],):
         raise ValueError(f"weight shapes {w1.shape} {b1.shape} {w2.shape} {b2.shape} for rows of {F} features")
-    acc = np.broadcast_to(b1, x.shape[:-1] + (HIDDEN,)).copy()
-    for f in range(F):
-        acc = fmaf32(w1[:, f], x[..., f:f + 1], acc)
-    h = np.where(acc > 0, acc, np.float32(0))
-    p = w2 * h[..., None, :]                                   # [..., C, 64], one float32 rounding each
-    for _ in range(6):
-        p = p[..., 0::2] + p[..., 1::2]
-    return (p[..., 0] + b2).astype(np.float32)
+    return host_heads(host_hidden(x, w1, b1), w2, b2)
+
+
+def host_value(x, w1, b1, wv, bv):
+    """float32 rows x [..., F] -> float32 values [...] of one weight set's value head (step 3b), bit for bit the device's: wv [64]
+    (or torch's `weight` [1, 64]) and bv [1] (or a scalar)"""
+    x = np.asarray(x, np.float32)
+    w1, b1 = np.asarray(w1, np.float32), np.asarray(b1, np.float32)
+    wv, bv = np.asarray(wv, np.float32).reshape(-1), np.asarray(bv, np.float32).reshape(-1)
+    F = x.shape[-1]
+    if w1.shape != (HIDDEN, F) or b1.shape != (HIDDEN,) or wv.shape != (HIDDEN,) or bv.shape != (1,):
+        raise ValueError(f"weight shapes {w1.shape} {b1.shape} {wv.shape} {bv.shape} for rows of {F} features")
+    return host_heads(host_hidden(x, w1, b1), wv[None, :], bv)[..., 0]
 
 
 def sample_from(logits, u):

@@ -567,6 +567,27 @@ class ShardedVecEnv:
     def policy_sets(self):
         return self.shards[0].policy_sets
 
+    def load_value(self, wv, bv):
+        """`CookingVecEnv.load_value` on every shard: the same value heads everywhere"""
+        self._each(lambda i, env: env.load_value(wv, bv))
+
+    @property
+    def value_sets(self):
+        return self.shards[0].value_sets
+
+    def value_device(self, d_obs32, d_values, vsets=(0, 0, 0, 0), rows=None):
+        """`CookingVecEnv.value_device` on every shard over its part of the ShardedBuffers.  `rows` counts the [A, F]-rows of the
+        whole batch - (T + 1) * N for buffers with leading = (T + 1,), a multiple of N - and every shard takes its share; None reads
+        it from the leading shape of `d_obs32`."""
+        if rows is None:
+            per_env = int(np.prod(d_obs32.leading, dtype=np.int64)) if isinstance(d_obs32, ShardedBuffer) else 1
+        else:
+            per_env, rest = divmod(int(rows), self.num_envs)
+            if rest or per_env < 1:
+                raise ValueError(f"value_device over shards: rows = {rows} is not a positive multiple of the {self.num_envs} envs")
+        P = self._part
+        self._each(lambda i, env: env.value_device(P(d_obs32, i), P(d_values, i), vsets=vsets, rows=per_env * env.num_envs))
+
     def policy_device(self, d_obs32, d_actions=None, d_logits=None, sets=(0, 0, 0, 0), mode="greedy", seed=0, step=0):
         """`CookingVecEnv.policy_device` on every shard over its part of the ShardedBuffers (per env: rows float32 [A, F], actions
         int32 [A], logits float32 [A, num_actions]).  The draws of "sample" are keyed by the global env id: shards reproduce one handle."""
@@ -579,6 +600,14 @@ class ShardedVecEnv:
         P = self._part
         self._each(lambda i, env: env.rollout_policy(T, P(d_obs32, i), P(d_actions, i), P(d_logits, i), P(d_rewards, i), P(d_term, i),
                                                      P(d_trunc, i), sets=sets, mode=mode, seed=seed, step0=step0))
+
+    def rollout_policy_value(self, T, d_obs32, d_values, d_actions=None, d_logits=None, d_rewards=None, d_term=None, d_trunc=None,
+                             sets=(0, 0, 0, 0), vsets=None, mode="greedy", seed=0, step0=0):
+        """`CookingVecEnv.rollout_policy_value` on every shard (the buffers: ShardedBuffers with leading = (T,), and (T + 1,) for
+        `d_values`)"""
+        P = self._part
+        self._each(lambda i, env: env.rollout_policy_value(T, P(d_obs32, i), P(d_values, i), P(d_actions, i), P(d_logits, i), P(d_rewards, i),
+                                                           P(d_term, i), P(d_trunc, i), sets=sets, vsets=vsets, mode=mode, seed=seed, step0=step0))
 
     def gae_device(self, T, d_rewards, d_term, d_trunc, d_values, d_adv=None, d_ret=None, gamma=0.99, lam=0.95, agents=None, env_count=None):
         """`CookingVecEnv.gae_device` on every shard over its part of the ShardedBuffers: leading = (T,), and (T + 1,) for the

@@ -1102,6 +1102,49 @@ class CookingVecEnv:
         """weight sets the last `load_policy` filled (0: none loaded)"""
         return int(_native.lib().cz_policy_sets(self._h))
 
+    def load_value(self, wv, bv):
+        """load the value heads of weight sets 0 .. n-1, `Linear(64, 1)` in torch's own layouts: wv [64] or `weight` [1, 64], bv [1],
+        float32 - one set, or a stack of up to 4 with a leading axis (wv [n, 64] or [n, 1, 64], bv [n, 1]).  Device tensors are
+        repacked by one launch on the env's stream with no host trip, like `load_policy`, which must have been called once before
+        (it owns the table); numpy arrays go through `alloc` + `from_host` first."""
+        H = _policy.HIDDEN
+        wshape, bshape = tuple(int(s) for s in wv.shape), tuple(int(s) for s in bv.shape)
+        if wshape in ((H,), (1, H)) and bshape in ((1,), ()):
+            n = 1
+        elif len(wshape) in (2, 3) and wshape[1:] in ((H,), (1, H)) and bshape in ((wshape[0], 1), (wshape[0],)):
+            n = wshape[0]
+        else:
+            raise ValueError(f"load_value: shapes {wshape} and {bshape}, expected [64] / [1, 64] and [1], or stacks [n, 64] / [n, 1, 64] and [n, 1]")
+        parts = []
+        for v, shape in zip((wv, bv), ((n, H), (n, 1))):
+            if hasattr(v, "data_ptr") or hasattr(v, "ptr"):
+                if str(v.dtype) not in ("torch.float32", "float32"):
+                    raise ValueError(f"load_value: device tensors must be float32, not {v.dtype}")
+                parts.append(v)
+            else:
+                key = ("value", len(parts), shape)
+                buf = self._policy_stage.get(key)
+                if buf is None:
+                    buf = self._policy_stage[key] = self.alloc(shape, np.float32)
+                buf.from_host(np.ascontiguousarray(v, np.float32).reshape(shape))
+                parts.append(buf)
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_load_value_device(self._h, n, p(parts[0]), p(parts[1])))
+
+    @property
+    def value_sets(self):
+        """weight sets whose value head the last `load_value` filled (0: none loaded)"""
+        return int(_native.lib().cz_value_sets(self._h))
+
+    def value_device(self, d_obs32, d_values, vsets=(0, 0, 0, 0), rows=None):
+        """the value heads on float32 rows of the caller, one launch, stream-ordered and capturable: `d_obs32` float32 [rows, A, F]
+        -> `d_values` float32 [rows, A], bit for bit `policy.host_value`.  `vsets`: agent a's value set - the weight set whose W1, b1
+        and value head are used - None / 0xFF = none, that agent's entries are left untouched.  `rows` counts [A, F]-rows: None is
+        the handle's N, a whole trajectory passes (T + 1) * N.  No record is read."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_value_device(self._h, self._count(rows), p(d_obs32), _policy.pack_sets(vsets, self.num_agents),
+                                                             p(d_values)))
+
     def policy_device(self, d_obs32, d_actions=None, d_logits=None, sets=(0, 0, 0, 0), mode="greedy", seed=0, step=0, env_begin=0,
                       env_count=None):
         """the policy on float32 rows of the caller, one launch, stream-ordered and capturable: `d_obs32` float32 [n, A, F] ->
@@ -1121,11 +1164,28 @@ class CookingVecEnv:
         t - 1 of the trajectory, a reset pass's row included), the draw of "sample" keyed by step0 + t.  Agents whose set is None /
         0xFF play `rollout`'s own action stream of `seed`.  `d_obs32` float32 [T, N, A, F] is required; `d_actions` int32 [T, N, A]
         (every agent's action as played) and `d_logits` float32 [T, N, A, num_actions] (policy agents only, the rest untouched)
-        are optional; rewards, flags, state, statistics and episode records are `rollout_actions_f32`'s over the same actions."""
+        are optional; rewards, flags, state, statistics and episode records are `rollout_actions_f32`'s over the same actions.
+        (`rollout_policy_value` is this launch with the critic's values beside it.)"""
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_rollout_policy(self._h, int(T), _policy.pack_sets(sets, self.num_agents), _policy.MODES[mode],
                                                                int(seed), int(step0), p(d_obs32), p(d_actions), p(d_logits), p(d_rewards),
                                                                p(d_term), p(d_trunc)))
+        self._issued(T)
+
+    def rollout_policy_value(self, T, d_obs32, d_values, d_actions=None, d_logits=None, d_rewards=None, d_term=None, d_trunc=None,
+                             sets=(0, 0, 0, 0), vsets=None, mode="greedy", seed=0, step0=0):
+        """`rollout_policy` that also evaluates the critic (`load_value`) in the same launch: `d_values` float32 [T + 1, N, A],
+        required.  Row t is the value on the row the policy reads in front of step t, row T the value on the row step T - 1 left -
+        what the next launch's step 0 reads - so `d_values` goes into `gae_device` as it is.  `vsets`: agent a's value set - the
+        weight set whose W1, b1 and value head are used - None / 0xFF per agent = no value (entries untouched); `vsets=None` means
+        "as `sets`", the shared trunk, which costs one more output row per agent and step; a set of its own is a second hidden
+        pass.  Every agent of `sets` may be None as long as one has a value set: values under the action stream.  Everything else
+        is bit for bit `rollout_policy` with the same arguments."""
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_rollout_policy_value(
+            self._h, int(T), _policy.pack_sets(sets, self.num_agents), _policy.pack_sets(sets if vsets is None else vsets, self.num_agents),
+            _policy.MODES[mode], int(seed), int(step0), p(d_obs32), p(d_actions), p(d_logits), p(d_values), p(d_rewards), p(d_term),
+            p(d_trunc)))
         self._issued(T)
 
     # ------------------------------------------------------------------ what a learner trains on (cooking_zoo_amd/targets.py)

@@ -698,6 +698,32 @@ int cz_policy_device(cz_handle h, int64_t env_begin, int64_t env_count, const fl
 int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t mode, uint64_t seed, uint32_t step0, float *d_obs32,
                       int32_t *d_actions, float *d_logits, double *d_rewards, uint8_t *d_terminations, uint8_t *d_truncations);
 
+/* ---- The critic (policy.py, step 3b).  A weight set may carry a value head, Linear(64, 1) in torch's layout: wv float32 [64]
+ * (weight[0]) and bv [1].  With h_j of the set's hidden layer: p_j = wv[j] * h_j, the same six butterfly levels, value = p + bv -
+ * the arithmetic of one logit, which policy.host_value reproduces bit for bit.  Every call below takes `vsets`, agent a's byte: the
+ * weight set whose W1, b1 and value head give agent a's value, 0xFF = none (entries untouched).  It is independent of `sets`: a
+ * shared trunk is vsets == sets, a separate critic is another weight set whose action head is never used.  Equal bytes: one hidden
+ * pass; different bytes: a second one; the bits are the same either way.  A byte >= min(cz_policy_sets, cz_value_sets) is refused.
+ *
+ * cz_load_value_device: the value heads of sets 0 .. n_sets-1 from DEVICE memory, d_wv [n][64] and d_bv [n][1]; one repack launch on
+ * the handle's stream, legal inside a stream capture.  The heads live in the policy table's allocation: refused before the first
+ * cz_load_policy_device.  Refused besides: n_sets outside 1..4, a NULL pointer. */
+int cz_load_value_device(cz_handle h, int32_t n_sets, const float *d_wv, const float *d_bv);
+int32_t cz_value_sets(cz_handle h);            /* sets whose value head the last load filled; 0: none */
+/* The value alone on rows of the caller, one launch (k_value): d_obs32 float32 [rows][A][F] -> d_values float32 [rows][A].  `rows`
+ * counts [A][F]-rows as in cz_logprob_device and is not tied to the batch: a whole [T + 1] * N trajectory is one launch.  Stream-
+ * ordered and capturable; no record is read.  Refused: rows < 1, a NULL pointer, every agent at 0xFF, a byte past the loaded heads. */
+int cz_value_device(cz_handle h, int64_t rows, const float *d_obs32, uint32_t vsets, float *d_values);
+/* cz_rollout_policy plus d_values float32 [T + 1][N][A], required (k_step<..., ROLLOUT_POLICY_VALUE>).  Row t is the value on exactly
+ * the row the policy reads in front of fused step t; row T is the value on the row staged by step T - 1 - the row a following
+ * launch's step 0 would read - so d_values goes into cz_gae_device as it is.  Everything else is bit for bit what cz_rollout_policy
+ * leaves for the same arguments.  Unlike cz_rollout_policy, every agent may be at 0xFF in `sets` as long as one has a `vsets` byte:
+ * values under the action stream.  Refused: what cz_rollout_policy refuses otherwise, a NULL d_values, every agent at 0xFF in both
+ * words. */
+int cz_rollout_policy_value(cz_handle h, int32_t T, uint32_t sets, uint32_t vsets, int32_t mode, uint64_t seed, uint32_t step0,
+                            float *d_obs32, int32_t *d_actions, float *d_logits, float *d_values, double *d_rewards,
+                            uint8_t *d_terminations, uint8_t *d_truncations);
+
 /* ---- What an on-policy learner trains on, from the trajectory cz_rollout_policy leaves in device memory (definition and numpy
  * model: cooking_zoo_amd/targets.py).  Float64 throughout, every operation rounded on its own, outputs rounded to float32 once; numpy
  * reproduces both calls bit for bit; NaN, infinities and subnormal intermediates are NOT pinned.  Both are one launch on the handle's
