@@ -1265,12 +1265,16 @@ struct StepCall {
     uint32_t *marks = nullptr;     // every env's recipe marks (the host step)
     bool fused = false;            // T steps in one launch (the rollouts, fused ring runs); seed and step0 are theirs as well
     int32_t T = 1; uint64_t seed = 0; uint32_t step0 = 0;
-    // cz_rollout_policy (fused, float32 only): the packed sets and mode (policy_pack_sets), and the two outputs of its own - `actions`
+    // cz_rollout_policy, cz_rollout_policy_value (fused, float32 only): what the policy adds to the launch (cz_policy.h) - `actions`
     // above stays null, the launch plays no actions of the caller
-    bool policy = false; uint32_t policy_packed = 0; int32_t *actions_out = nullptr; float *logits_out = nullptr;
-    // cz_rollout_policy_value: the values output float [T + 1][N][A] and the packed value sets (policy_pack_vsets) beside them
-    float *values_out = nullptr; uint32_t value_packed = 0;
+    const PolicyLaunch *policy = nullptr;
 };
+// the fused call of a rollout: T steps, the stream's seed and step0, the three outputs every rollout has; the entry point adds its own
+static StepCall fused_call(int32_t T, uint64_t seed, uint32_t step0, double *rewards, uint8_t *term, uint8_t *trunc) {
+    StepCall c{nullptr, nullptr, rewards, term, trunc};
+    c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    return c;
+}
 enum ObsForm { OBS_F64, OBS_CODES, OBS_F32 };      // what a launch writes its observation as (OBS_CODES: float64 rows beside the codes if P.obs)
 
 // The outputs of one launch, in the Params its kernel gets: what the call named, and - one-step launches only - the handle's durable
@@ -1291,12 +1295,6 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
     P.actions = c.actions; P.obs = c.obs; P.rewards = c.rewards; P.term = c.term; P.trunc = c.trunc; P.marks_out = c.marks;
     P.T = c.T; P.seed = c.seed; P.step0 = c.step0;
     if (obs32) P.obs32 = obs32; else P.codes = codes;
-    if (c.policy) {
-        // ROLLOUT_POLICY reads three slots no float32 fused launch uses (StepTraits::policy): the block must not grow
-        P.actions = c.actions_out;
-        P.obs = reinterpret_cast<double *>(c.logits_out);
-        P.marks_out = reinterpret_cast<uint32_t *>(reinterpret_cast<uintptr_t>(h->d_policy) | ((uintptr_t)c.policy_packed << 48));
-    }
     return nullptr;
 }
 
@@ -1315,11 +1313,12 @@ static const char *resolve_step(cz_handle h, const StepCall &c, Params &P, ObsFo
 //                                        every setting it fixes at compile time holds: float64 rows of at most 128 * OBS_PAIRS features with
 //                                        write-through stores, no marks buffer, narrow recipe tables, no despawn / respawn
 //   one step without P.actions        -> hipErrorInvalidValue
-static hipError_t choose_step(cz_handle h, const Params &P, bool fused, ObsForm form, StepChoice &c, bool policy = false, bool value = false) {
+static hipError_t choose_step(cz_handle h, const Params &P, const StepCall &call, ObsForm form, StepChoice &c) {
+    const bool fused = call.fused;
     c.lean = false;
     c.cfg = -1;
-    if (policy) {
-        c.mode = value ? ROLLOUT_POLICY_VALUE : ROLLOUT_POLICY;
+    if (call.policy) {
+        c.mode = call.policy->values ? ROLLOUT_POLICY_VALUE : ROLLOUT_POLICY;
         return fused && form == OBS_F32 ? hipSuccess : hipErrorInvalidValue;
     }
     if (fused && form == OBS_F32) c.mode = P.actions ? ROLLOUT_ACTIONS_F32 : ROLLOUT_F32;
@@ -1399,6 +1398,9 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
 #ifdef CZ_TIMELINE
     P.timeline = (h->tl_base && h->tl_cap > 0) ? h->tl_base + (size_t)(h->tl_count++ % h->tl_cap) * (size_t)P.N * 2 : nullptr;
 #endif
+    // a policy rollout: its borrowed slots of P, and the kernel's block beside it - a copy of P, which nothing writes behind this point
+    Params policy_block;
+    if (call.policy && !policy_encode(*call.policy, P, policy_block)) return fail(h, "a policy rollout: a pointer that carries a tag (policy_encode) is a device address above 2^48");
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->ktime && caller_capturing(h)) return fail(h, "kernel timing (cz_kernel_time_reset) cannot run inside a stream capture of the caller");
     if (h->ktime) {
@@ -1412,17 +1414,15 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
         HIPCHK(h, hipEventRecord(e0, stream));
     }
     StepChoice choice;
-    const hipError_t chosen = choose_step(h, P, fused, form, choice, call.policy, call.values_out != nullptr);
-    // (the values pointer travels beside the block, not in it: launch_policy_step_kernel in cz_kernels.h)
-    if (call.values_out) choice.values = reinterpret_cast<const void *>(reinterpret_cast<uintptr_t>(call.values_out) | ((uintptr_t)call.value_packed << 48));
+    const hipError_t chosen = choose_step(h, P, call, form, choice);
     h->last_step_lean = choice.lean ? 1 : 0;
     h->last_step_mode = choice.mode;
     h->last_step_variant = !choice.lean ? -1 : choice.cfg < 0 ? 0 : (0x100 | P.R | (P.end_all << 4) | (P.walk_touches << 5));
     HIPCHK(h, chosen);
     if (split && !fused) {
-        if (split->only != 1) HIPCHK(h, h->kl.step(sub_range(P, form, 0, split->begin1), stream, choice));
-        if (split->only != 0) HIPCHK(h, h->kl.step(sub_range(P, form, split->begin1, P.N - split->begin1), split->side, choice));
-    } else HIPCHK(h, h->kl.step(P, stream, choice));
+        if (split->only != 1) HIPCHK(h, h->kl.step(sub_range(P, form, 0, split->begin1), stream, choice, nullptr));
+        if (split->only != 0) HIPCHK(h, h->kl.step(sub_range(P, form, split->begin1, P.N - split->begin1), split->side, choice, nullptr));
+    } else HIPCHK(h, h->kl.step(P, stream, choice, call.policy ? &policy_block : nullptr));
     if (h->ktime) HIPCHK(h, hipEventRecord(e1, stream));
     return 0;
 }
@@ -2242,8 +2242,8 @@ extern "C" int cz_launch_counts(cz_handle h, int64_t *graph_kernels, int64_t *di
 extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, double *d_obs, double *d_rewards,
                           uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1, "cz_rollout: T must be >= 1", "cz_rollout", T)) return 1;
-    StepCall c{nullptr, d_obs, d_rewards, d_term, d_trunc};
-    c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    StepCall c = fused_call(T, seed, step0, d_rewards, d_term, d_trunc);
+    c.obs = d_obs;
     return launch_step(h, c);
 }
 
@@ -2252,8 +2252,8 @@ extern "C" int cz_rollout(cz_handle h, int32_t T, uint64_t seed, uint32_t step0,
 extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_t step0, uint8_t *d_codes, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_codes, "cz_rollout_compact: T must be >= 1 and the codes pointer non-null", "cz_rollout_compact", T)) return 1;
-    StepCall c{nullptr, d_obs, d_rewards, d_term, d_trunc};
-    c.codes = d_codes; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    StepCall c = fused_call(T, seed, step0, d_rewards, d_term, d_trunc);
+    c.obs = d_obs; c.codes = d_codes;
     return launch_step(h, c);
 }
 
@@ -2263,8 +2263,8 @@ extern "C" int cz_rollout_compact(cz_handle h, int32_t T, uint64_t seed, uint32_
 extern "C" int cz_rollout_actions(cz_handle h, int32_t T, const int32_t *d_actions, double *d_obs, double *d_rewards,
                                   uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_actions, "cz_rollout_actions: T must be >= 1 and the actions pointer non-null", "cz_rollout_actions", T)) return 1;
-    StepCall c{d_actions, d_obs, d_rewards, d_term, d_trunc};
-    c.fused = true; c.T = T;
+    StepCall c = fused_call(T, 0, 0, d_rewards, d_term, d_trunc);
+    c.actions = d_actions; c.obs = d_obs;
     return launch_step(h, c);
 }
 
@@ -2276,8 +2276,8 @@ extern "C" int cz_rollout_f32(cz_handle h, int32_t T, uint64_t seed, uint32_t st
                               uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_obs32, "cz_rollout_f32: T must be >= 1 and the float32 trajectory pointer non-null (without one: "
                                                 "cz_rollout with d_obs = NULL)", "cz_rollout_f32", T)) return 1;
-    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
-    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
+    StepCall c = fused_call(T, seed, step0, d_rewards, d_term, d_trunc);
+    c.obs32 = d_obs32;
     return launch_step(h, c);
 }
 // ... over actions of the caller (cooking_env.py:243-269 T times, :352-373): d_actions int32 [T][N][A] as for cz_rollout_actions, every
@@ -2287,8 +2287,8 @@ extern "C" int cz_rollout_actions_f32(cz_handle h, int32_t T, const int32_t *d_a
     if (begin_device_call(h, T >= 1 && d_actions && d_obs32, "cz_rollout_actions_f32: T must be >= 1 and the actions and float32 trajectory "
                                                              "pointers non-null (without a trajectory: cz_rollout_actions with d_obs = NULL)",
                           "cz_rollout_actions_f32", T)) return 1;
-    StepCall c{d_actions, nullptr, d_rewards, d_term, d_trunc};
-    c.obs32 = d_obs32; c.fused = true; c.T = T;
+    StepCall c = fused_call(T, 0, 0, d_rewards, d_term, d_trunc);
+    c.actions = d_actions; c.obs32 = d_obs32;
     return launch_step(h, c);
 }
 
@@ -2307,7 +2307,11 @@ extern "C" int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d
         if (caller_capturing(h)) return fail(h, "cz_load_policy_device: the handle's first load allocates the table: call it once outside the capture");
         // (room for the value heads behind the sets: cz_load_value_device; zeroed, so that no launch reads what nobody wrote)
         HIPCHK(h, hipMalloc(&h->d_policy, (size_t)policy_table_floats(h->P.F) * sizeof(float)));
-        if (reinterpret_cast<uintptr_t>(h->d_policy) >> 48) return fail(h, "cz_load_policy_device: device address above 2^48");
+        if (!policy_taggable(h->d_policy)) {            // (no device address is: policy_encode would refuse every launch)
+            (void)hipFree(h->d_policy);
+            h->d_policy = nullptr;
+            return fail(h, "cz_load_policy_device: device address above 2^48");
+        }
         HIPCHK(h, hipMemsetAsync(h->d_policy + policy_value_offset(h->P.F), 0, POLICY_VALUE_FLOATS * sizeof(float), h->stream));
     }
     const uint32_t total = (uint32_t)(per_set * (size_t)n_sets);
@@ -2333,33 +2337,35 @@ extern "C" int cz_load_value_device(cz_handle h, int32_t n_sets, const float *d_
     return 0;
 }
 extern "C" int32_t cz_value_sets(cz_handle h) { return h ? h->n_value_sets : -1; }
+// The agents' bytes of a policy or value call (agent a's set in byte a, 0xFF none): how many agents have a set, or -1 after
+// refuse(agent, set) - the caller's fail() - when one asks for a set past the `usable` ones
+template <class Refuse>
+static int count_sets(cz_handle h, uint32_t bytes, int32_t usable, Refuse &&refuse) {
+    int with_set = 0;
+    for (int a = 0; a < h->P.A; ++a) {
+        const uint32_t s = (bytes >> (8 * a)) & 0xFFu;
+        if (s == POLICY_NONE) continue;
+        if (s >= (uint32_t)usable) { refuse(a, s); return -1; }
+        ++with_set;
+    }
+    return with_set;
+}
 // `vsets` of a value call, checked: the packed form, or -1 after fail()
 static int64_t check_value_call(cz_handle h, const char *who, uint32_t vsets, int *with_set) {
     if (!h->d_policy || h->n_policy_sets == 0) { fail(h, "%s: no weight table loaded (cz_load_policy_device)", who); return -1; }
-    const int32_t usable = h->n_policy_sets < h->n_value_sets ? h->n_policy_sets : h->n_value_sets;
-    *with_set = 0;
-    for (int a = 0; a < h->P.A; ++a) {
-        const uint32_t s = (vsets >> (8 * a)) & 0xFFu;
-        if (s == POLICY_NONE) continue;
-        if (s >= (uint32_t)usable) {
-            fail(h, "%s: agent %d asks for the value head of set %u, but %d sets and %d value heads are loaded", who, a, s, h->n_policy_sets, h->n_value_sets);
-            return -1;
-        }
-        ++*with_set;
-    }
-    return (int64_t)policy_pack_vsets(vsets, h->P.A);
+    *with_set = count_sets(h, vsets, h->n_policy_sets < h->n_value_sets ? h->n_policy_sets : h->n_value_sets, [&](int a, uint32_t s) {
+        fail(h, "%s: agent %d asks for the value head of set %u, but %d sets and %d value heads are loaded", who, a, s, h->n_policy_sets, h->n_value_sets);
+    });
+    return *with_set < 0 ? -1 : (int64_t)policy_pack_vsets(vsets, h->P.A);
 }
 // `sets` and `mode` of a policy call, checked: the packed form, or -1 after fail()
 static int64_t check_policy_call(cz_handle h, const char *who, uint32_t sets, int32_t mode, bool need_one) {
     if (!h->d_policy || h->n_policy_sets == 0) { fail(h, "%s: no weight table loaded (cz_load_policy_device)", who); return -1; }
     if (mode != (int32_t)POLICY_GREEDY && mode != (int32_t)POLICY_SAMPLE) { fail(h, "%s: mode is %d, not CZ_POLICY_GREEDY (0) or CZ_POLICY_SAMPLE (1)", who, mode); return -1; }
-    int with_set = 0;
-    for (int a = 0; a < h->P.A; ++a) {
-        const uint32_t s = (sets >> (8 * a)) & 0xFFu;
-        if (s == POLICY_NONE) continue;
-        if (s >= (uint32_t)h->n_policy_sets) { fail(h, "%s: agent %d asks for weight set %u, but %d are loaded", who, a, s, h->n_policy_sets); return -1; }
-        ++with_set;
-    }
+    const int with_set = count_sets(h, sets, h->n_policy_sets, [&](int a, uint32_t s) {
+        fail(h, "%s: agent %d asks for weight set %u, but %d are loaded", who, a, s, h->n_policy_sets);
+    });
+    if (with_set < 0) return -1;
     if (need_one && with_set == 0) { fail(h, "%s: every agent's set is 0xFF (that is cz_rollout_f32)", who); return -1; }
     return (int64_t)policy_pack_sets(sets, (uint32_t)mode, h->P.A);
 }
@@ -2416,9 +2422,9 @@ extern "C" int cz_rollout_policy(cz_handle h, int32_t T, uint32_t sets, int32_t 
     if (begin_device_call(h, T >= 1 && d_obs32, "cz_rollout_policy: T must be >= 1 and the float32 trajectory pointer non-null", "cz_rollout_policy", T)) return 1;
     const int64_t packed = check_policy_call(h, "cz_rollout_policy", sets, mode, true);
     if (packed < 0) return 1;
-    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
-    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
-    c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
+    const PolicyLaunch L{d_actions, d_logits, h->d_policy, (uint32_t)packed};
+    StepCall c = fused_call(T, seed, step0, d_rewards, d_term, d_trunc);
+    c.obs32 = d_obs32; c.policy = &L;
     return launch_step(h, c);
 }
 // cz_rollout_policy plus the value heads (k_step<..., ROLLOUT_POLICY_VALUE>): d_values float32 [T + 1][N][A], required.  Row t holds the
@@ -2430,17 +2436,16 @@ extern "C" int cz_rollout_policy_value(cz_handle h, int32_t T, uint32_t sets, ui
                                        int32_t *d_actions, float *d_logits, float *d_values, double *d_rewards, uint8_t *d_term, uint8_t *d_trunc) {
     if (begin_device_call(h, T >= 1 && d_obs32 && d_values, "cz_rollout_policy_value: T must be >= 1 and the float32 trajectory and values pointers non-null",
                           "cz_rollout_policy_value", T)) return 1;
-    if (reinterpret_cast<uintptr_t>(d_values) >> 48) return fail(h, "cz_rollout_policy_value: the values pointer is a device address above 2^48");
+    if (!policy_taggable(d_values)) return fail(h, "cz_rollout_policy_value: the values pointer is a device address above 2^48");
     const int64_t packed = check_policy_call(h, "cz_rollout_policy_value", sets, mode, false);
     if (packed < 0) return 1;
     int with_value = 0;
     const int64_t vpacked = check_value_call(h, "cz_rollout_policy_value", vsets, &with_value);
     if (vpacked < 0) return 1;
     if (!with_value && ((uint32_t)packed & 0xFFFu) == 0xFFFu) return fail(h, "cz_rollout_policy_value: every agent is at 0xFF in both sets and vsets (that is cz_rollout_f32)");
-    StepCall c{nullptr, nullptr, d_rewards, d_term, d_trunc};
-    c.obs32 = d_obs32; c.fused = true; c.T = T; c.seed = seed; c.step0 = step0;
-    c.policy = true; c.policy_packed = (uint32_t)packed; c.actions_out = d_actions; c.logits_out = d_logits;
-    c.values_out = d_values; c.value_packed = (uint32_t)vpacked;
+    const PolicyLaunch L{d_actions, d_logits, h->d_policy, (uint32_t)packed, d_values, (uint32_t)vpacked};
+    StepCall c = fused_call(T, seed, step0, d_rewards, d_term, d_trunc);
+    c.obs32 = d_obs32; c.policy = &L;
     return launch_step(h, c);
 }
 

@@ -86,13 +86,10 @@ struct StepTraits {
     // the float32 rows: np.float32 of the float64 feature (round to nearest even), gathered from a float32 copy of the table that the
     // workgroup makes while it stages the table into LDS - no arithmetic on values, no float64 path beside it
     static constexpr bool f32 = MODE == STEP_F32 || MODE == ROLLOUT_F32 || MODE == ROLLOUT_ACTIONS_F32 || MODE == ROLLOUT_POLICY || MODE == ROLLOUT_POLICY_VALUE;
-    // the policy in front of every fused step.  A float32 fused launch leaves three slots of the argument block unused, and the block must
-    // not grow: `actions` carries the int32 [T][N][A] actions OUTPUT, `obs` the float [T][N][A][C] logits output (either may be null) and
-    // `marks_out` the weight table with policy_pack_sets in the 16 bits above a device address (resolve_step in cz_api.hip puts them there)
+    // the policy in front of every fused step, and the value heads beside it.  Their outputs, the weight table and the packed sets
+    // travel in slots of the argument block that a float32 fused launch leaves unused: PolicyLaunch in cz_policy.h says which, and
+    // policy_encode and the decoders next to it are the only code that knows
     static constexpr bool policy = MODE == ROLLOUT_POLICY || MODE == ROLLOUT_POLICY_VALUE;
-    // ... and the value heads beside it.  The values pointer float [T + 1][N][A] needs a slot too: the block's own `actions` is dead in
-    // every step kernel - the leading scalar e_actions stands in for it - so the launch puts the pointer there, with policy_pack_vsets
-    // in the 16 bits above the address (launch_policy_step_kernel), and the kernel reads it through the late block
     static constexpr bool value = MODE == ROLLOUT_POLICY_VALUE;
     static constexpr bool f64 = !codes_only && !f32;                                     // carries the float64 observation path
     // The CodesPrefetch words (the b128 descriptor loads of the codes and of the float32 rows): fetched once behind the prologue and held
@@ -952,9 +949,8 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             // agents with a weight set: the policy on the row in LDS - row t - 1 of the trajectory, whatever wrote it, or the row before
             // step 0 - in place of the stream's action; every agent's action as played and the policy agents' logits go to row t
             constexpr int C = SCHEME == 3 ? 5 : 8;
-            const uint64_t slot = (uint64_t)reinterpret_cast<uintptr_t>(Pt.marks_out);
-            const float *const table = reinterpret_cast<const float *>(static_cast<uintptr_t>(slot & 0xFFFFFFFFFFFFull));
-            const uint32_t pk = (uint32_t)(slot >> 48);
+            const float *const table = policy_slot_pointer<const float>(Pt.marks_out);
+            const uint32_t pk = policy_slot_tag(Pt.marks_out);
             const size_t prow = (size_t)t * (size_t)Pt.N + (size_t)env;
             float *const lrow = Pt.obs ? reinterpret_cast<float *>(Pt.obs) + prow * (size_t)(NA * C) : nullptr;
             const int Fq = policy_quads(Pt.F);
@@ -963,9 +959,9 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
             uint32_t vpk = 0xFFFu;
             float *vrow = nullptr;
             if constexpr (V::value) {
-                const uint64_t vslot = (uint64_t)reinterpret_cast<uintptr_t>(CZ_LATE_STEP()->actions);
-                vpk = (uint32_t)(vslot >> 48);
-                vrow = reinterpret_cast<float *>(static_cast<uintptr_t>(vslot & 0xFFFFFFFFFFFFull)) + prow * (size_t)NA;
+                const int32_t *const vslot = CZ_LATE_STEP()->actions;
+                vpk = policy_slot_tag(vslot);
+                vrow = policy_slot_pointer<float>(vslot) + prow * (size_t)NA;
             }
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
@@ -975,7 +971,7 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
                     float mylogit;
                     const float *const set = table + (size_t)si * policy_set_floats(Pt.F);
                     const float hid = policy_hidden(set, Fq, xrow + (uint32_t)(a * 4 * Fq), lane);
-                    policy_heads<C>(set, Fq, hid, lane, (pk >> 12) & 1u, Pt.seed, env_global, Pt.step0 + (uint32_t)t, a, action, mylogit);
+                    policy_heads<C>(set, Fq, hid, lane, (pk >> POLICY_VSETS_BITS) & 1u, Pt.seed, env_global, Pt.step0 + (uint32_t)t, a, action, mylogit);
                     acts = lane == a ? (uint32_t)action : acts;
                     if (lrow && lane < C) lrow[a * C + lane] = mylogit;
                     if constexpr (V::value) {
@@ -1101,10 +1097,11 @@ __device__ __forceinline__ void step_kernel(uint32_t *e_state, const int32_t *e_
     if constexpr (V::value) {
         // the bootstrap: row T of the values, on the row the last step staged - what a following launch's step 0 would read
         const auto kp = CZ_LATE_STEP();
-        const uint64_t slot = (uint64_t)reinterpret_cast<uintptr_t>(kp->marks_out), vslot = (uint64_t)reinterpret_cast<uintptr_t>(kp->actions);
-        const float *const table = reinterpret_cast<const float *>(static_cast<uintptr_t>(slot & 0xFFFFFFFFFFFFull));
-        const uint32_t vpk = (uint32_t)(vslot >> 48);
-        float *const vrow = reinterpret_cast<float *>(static_cast<uintptr_t>(vslot & 0xFFFFFFFFFFFFull)) + ((size_t)T * (size_t)P.N + (size_t)env) * (size_t)NA;
+        const uint32_t *const slot = kp->marks_out;                  // (read in this order: the other one reorders the shipped streams)
+        const int32_t *const vslot = kp->actions;
+        const float *const table = policy_slot_pointer<const float>(slot);
+        const uint32_t vpk = policy_slot_tag(vslot);
+        float *const vrow = policy_slot_pointer<float>(vslot) + ((size_t)T * (size_t)P.N + (size_t)env) * (size_t)NA;
         const int F = kp->F, Fq = policy_quads(F);
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
@@ -1168,7 +1165,7 @@ __global__ __launch_bounds__(64 * envs_per_wg<CPL>()) void k_step_lean_cfg(uint3
 }
 
 // cfg: with `lean`, the row of CZ_LEAN_CFGS whose k_step_lean_cfg the launch takes, or -1: k_step_lean
-struct StepChoice { StepMode mode; bool lean; int cfg; const void *values = nullptr; };       // which variant a launch takes (choose_step, cz_api.hip)
+struct StepChoice { StepMode mode; bool lean; int cfg; };       // which variant a launch takes (choose_step, cz_api.hip)
 // The k_step_lean_cfg kernels of the small instance: X(agents, action scheme, recipes, end_all, walk_touches), nine kernels, all under
 // scheme3.  Two agents - the headline workload and BASELINE configs 3 and 4 are (2, 3, 2, 0, 0) - with every recipe count a handle of
 // two agents can have (cz_create: agents <= recipes <= 4) and both end conditions; one recipe means one agent; walk_touches = 1 where
@@ -1240,9 +1237,10 @@ inline hipError_t launch_step_kernel(K kernel, const Params &P, hipStream_t st) 
 constexpr size_t LDS_PER_WORKGROUP = 160u << 10;
 template <int CPL>
 inline size_t policy_rows_bytes(const Params &P) { return (size_t)envs_per_wg<CPL>() * (size_t)P.A * (size_t)policy_quads(P.F) * 16u; }
-// (`values`: ROLLOUT_POLICY_VALUE's values pointer with policy_pack_vsets above it, which travels in the block's dead `actions` slot)
+// (`block`: the kernel's by-value block as policy_encode made it; a launch without one is refused)
 template <int CPL, class K>
-inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream_t st, const void *values = nullptr) {
+inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, const Params *block, hipStream_t st) {
+    if (!block) return hipErrorInvalidValue;
     const size_t rows = policy_rows_bytes<CPL>(P);
     hipFuncAttributes attr;
     hipError_t err = hipFuncGetAttributes(&attr, reinterpret_cast<const void *>(kernel));
@@ -1252,9 +1250,7 @@ inline hipError_t launch_policy_step_kernel(K kernel, const Params &P, hipStream
         err = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows);
         if (err != hipSuccess) return err;
     }
-    Params B = P;
-    if (values) B.actions = static_cast<const int32_t *>(values);
-    return launch_step_kernel<CPL>(kernel, P, B, st, rows);
+    return launch_step_kernel<CPL>(kernel, P, *block, st, rows);
 }
 
 }  // namespace cz

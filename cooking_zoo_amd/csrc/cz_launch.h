@@ -9,8 +9,9 @@ namespace cz {
 
 // launchers exported by each instantiation unit
 struct Launchers {
-    // lean: k_step_lean (mode STEP, and only where has_lean); otherwise k_step<..., mode>.  Fused modes run P.T steps per launch
-    hipError_t (*step)(const Params &, hipStream_t, StepChoice);
+    // lean: k_step_lean (mode STEP, and only where has_lean); otherwise k_step<..., mode>.  Fused modes run P.T steps per launch.
+    // The last argument is the kernel's block of the two policy modes (policy_encode), null for every other launch
+    hipError_t (*step)(const Params &, hipStream_t, StepChoice, const Params *);
     hipError_t (*reset)(const Params &, hipStream_t, int64_t, int, const int32_t *, const uint32_t *, const uint32_t *, double *);
     hipError_t (*observe)(const Params &, hipStream_t, int64_t, int, double *, uint8_t *);
     bool has_lean;             // the instance carries the k_step_lean kernels
@@ -37,7 +38,7 @@ struct Launchers {
 
 template <int OPL, int CPL, bool HAS_LEAN = false>
 struct Inst {
-    static hipError_t step(const Params &P, hipStream_t st, StepChoice c) {
+    static hipError_t step(const Params &P, hipStream_t st, StepChoice c, const Params *policy_block) {
         if constexpr (HAS_LEAN) {
             if (c.lean && c.cfg >= 0) {
                 if (c.cfg != lean_cfg_of(P)) return hipErrorInvalidValue;
@@ -66,10 +67,8 @@ struct Inst {
                 case STEP_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, STEP_F32>, P, st);
                 case ROLLOUT_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_F32>, P, st);
                 case ROLLOUT_ACTIONS_F32: return launch_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_ACTIONS_F32>, P, st);
-                case ROLLOUT_POLICY: return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY>, P, st);
-                case ROLLOUT_POLICY_VALUE:
-                    if (!c.values) return hipErrorInvalidValue;
-                    return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY_VALUE>, P, st, c.values);
+                case ROLLOUT_POLICY: return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY>, P, policy_block, st);
+                case ROLLOUT_POLICY_VALUE: return launch_policy_step_kernel<CPL>(k_step<OPL, CPL, NA, S, ROLLOUT_POLICY_VALUE>, P, policy_block, st);
                 }
                 return hipErrorInvalidValue;
             });

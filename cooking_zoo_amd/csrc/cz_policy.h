@@ -28,8 +28,10 @@ __host__ __device__ inline uint32_t policy_value_offset(int F) { return POLICY_M
 constexpr uint32_t POLICY_VALUE_FLOATS = POLICY_MAX_SETS * POLICY_HIDDEN + POLICY_MAX_SETS;
 __host__ __device__ inline uint32_t policy_table_floats(int F) { return policy_value_offset(F) + POLICY_VALUE_FLOATS; }
 // `sets` (agent a's set in byte a, 0xFF none) and the mode in 13 bits: three bits per agent, 7 = none, mode in bit 12
+constexpr int POLICY_VSETS_BITS = 3 * MAX_AGENTS, POLICY_SETS_BITS = POLICY_VSETS_BITS + 1;
+static_assert(POLICY_MAX_SETS <= 7, "a set index takes three bits, and 7 stays free for `none`");
 __host__ __device__ inline uint32_t policy_pack_sets(uint32_t sets, uint32_t mode, int A) {
-    uint32_t pk = (mode & 1u) << 12;
+    uint32_t pk = (mode & 1u) << POLICY_VSETS_BITS;
     for (int a = 0; a < MAX_AGENTS; ++a) {
         const uint32_t s = a < A ? (sets >> (8 * a)) & 0xFFu : POLICY_NONE;
         pk |= (s == POLICY_NONE ? 7u : s) << (3 * a);
@@ -39,6 +41,43 @@ __host__ __device__ inline uint32_t policy_pack_sets(uint32_t sets, uint32_t mod
 
 // `vsets` (agent a's value set in byte a, 0xFF none) in 12 bits, three per agent as above
 __host__ __device__ inline uint32_t policy_pack_vsets(uint32_t vsets, int A) { return policy_pack_sets(vsets, 0u, A); }
+
+// ---- The policy rollouts' borrowed slots (k_step<..., ROLLOUT_POLICY / ROLLOUT_POLICY_VALUE>): this description, policy_encode and
+// the two decoders are everything that knows them.  The step kernel's argument block must not grow, and a float32 fused launch leaves
+// `actions`, `obs` and `marks_out` of Params unused - and the kernel block's own `actions` dead, since the leading scalar e_actions
+// (early_of) stands in for it.  What a policy rollout adds to such a launch:
+struct PolicyLaunch {
+    int32_t *actions = nullptr;        // output int32 [T][N][A], every agent's action as played (may be null) -> Params::actions, so e_actions
+    float *logits = nullptr;           // output float [T][N][A][C], policy agents only (may be null)          -> Params::obs
+    const float *table = nullptr;      // the weight table, with `packed` (policy_pack_sets) as its tag         -> Params::marks_out
+    uint32_t packed = 0;
+    float *values = nullptr;           // output float [T + 1][N][A]; null: ROLLOUT_POLICY.  With `vpacked`     -> the kernel block's `actions`
+    uint32_t vpacked = 0;              // (policy_pack_vsets) as its tag
+};
+// A tag rides in the bits of a slot that no device address uses
+constexpr int POLICY_TAG_SHIFT = 48;
+constexpr uint64_t POLICY_ADDRESS_MASK = (1ull << POLICY_TAG_SHIFT) - 1;
+static_assert(sizeof(void *) == 8 && sizeof(uintptr_t) == 8, "a slot is a 64-bit pointer");
+static_assert(POLICY_SETS_BITS <= 64 - POLICY_TAG_SHIFT && POLICY_VSETS_BITS <= 64 - POLICY_TAG_SHIFT, "the packed sets fit the tag");
+inline bool policy_taggable(const void *p) { return (reinterpret_cast<uintptr_t>(p) >> POLICY_TAG_SHIFT) == 0; }
+// The encoder: the one writer of the four slots.  `P` is the launch's otherwise finished Params - the leading scalars are made from
+// it - and `block` becomes the kernel's by-value block.  False, and nothing written: an address reaches into the tag's bits.
+inline bool policy_encode(const PolicyLaunch &L, Params &P, Params &block) {
+    if (!policy_taggable(L.table) || !policy_taggable(L.values)) return false;
+    const auto tagged = [](const void *p, uint32_t tag) { return reinterpret_cast<uintptr_t>(p) | ((uintptr_t)tag << POLICY_TAG_SHIFT); };
+    P.actions = L.actions;
+    P.obs = reinterpret_cast<double *>(L.logits);
+    P.marks_out = reinterpret_cast<uint32_t *>(tagged(L.table, L.packed));
+    block = P;
+    if (L.values) block.actions = reinterpret_cast<const int32_t *>(tagged(L.values, L.vpacked));
+    return true;
+}
+// The decoders: a tagged slot -> its pointer, its packed bits
+template <class T>
+__device__ __forceinline__ T *policy_slot_pointer(const void *slot) {
+    return reinterpret_cast<T *>(static_cast<uintptr_t>((uint64_t)reinterpret_cast<uintptr_t>(slot) & POLICY_ADDRESS_MASK));
+}
+__device__ __forceinline__ uint32_t policy_slot_tag(const void *slot) { return (uint32_t)((uint64_t)reinterpret_cast<uintptr_t>(slot) >> POLICY_TAG_SHIFT); }
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
 // the float32 rows a policy reads, in LDS: per env A rows of 4 * policy_quads(F) floats, the tail zeroed (sized by the launch)

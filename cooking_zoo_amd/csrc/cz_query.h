@@ -1094,7 +1094,7 @@ __global__ __launch_bounds__(64) void k_policy(const PolicyArgs G) {
         int action;
         float mylogit;
         const float *const set = G.table + (size_t)si * policy_set_floats(G.F);
-        const uint32_t mode = (G.packed >> 12) & 1u;
+        const uint32_t mode = (G.packed >> POLICY_VSETS_BITS) & 1u;
         const float hid = policy_hidden(set, Fq, x + a * 4 * Fq, lane);
         if (G.C == 5) policy_heads<5>(set, Fq, hid, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);
         else policy_heads<8>(set, Fq, hid, lane, mode, G.seed, G.env_global0 + (int64_t)i, G.step, a, action, mylogit);

@@ -1069,6 +1069,20 @@ class CookingVecEnv:
         self._issued(T)
 
     # ------------------------------------------------------------------ the MLP policy (cooking_zoo_amd/policy.py)
+    def _weight_part(self, who, role, k, v, shape):
+        """the device side of `who`'s k-th weight array: a device tensor (float32) passes as it is, a numpy array is staged as `shape`
+        in a buffer the env keeps by role, position and shape"""
+        if hasattr(v, "data_ptr") or hasattr(v, "ptr"):
+            if str(v.dtype) not in ("torch.float32", "float32"):
+                raise ValueError(f"{who}: device tensors must be float32, not {v.dtype}")
+            return v
+        key = (role, k, shape)
+        buf = self._policy_stage.get(key)
+        if buf is None:
+            buf = self._policy_stage[key] = self.alloc(shape, np.float32)
+        buf.from_host(np.ascontiguousarray(v, np.float32).reshape(shape))
+        return buf
+
     def load_policy(self, w1, b1, w2, b2):
         """load weight sets of `Sequential(Linear(F, 64), ReLU(), Linear(64, num_actions))` in torch's own layouts: w1 [64, F],
         b1 [64], w2 [C, 64], b2 [C], float32 - one set, or a stack of up to 4 with a leading axis.  Device tensors (anything with
@@ -1083,17 +1097,7 @@ class CookingVecEnv:
             got = tuple(int(s) for s in v.shape)
             if got != (shape if stacked else shape[1:]):
                 raise ValueError(f"load_policy: shape {got}, expected {shape if stacked else shape[1:]} (F = {F}, C = {Cn})")
-            if hasattr(v, "data_ptr") or hasattr(v, "ptr"):
-                if str(v.dtype) not in ("torch.float32", "float32"):
-                    raise ValueError(f"load_policy: device tensors must be float32, not {v.dtype}")
-                parts.append(v)
-            else:
-                key = ("policy", len(parts), shape)
-                buf = self._policy_stage.get(key)
-                if buf is None:
-                    buf = self._policy_stage[key] = self.alloc(shape, np.float32)
-                buf.from_host(np.ascontiguousarray(v, np.float32).reshape(shape))
-                parts.append(buf)
+            parts.append(self._weight_part("load_policy", "policy", len(parts), v, shape))
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_load_policy_device(self._h, n, p(parts[0]), p(parts[1]), p(parts[2]), p(parts[3])))
 
@@ -1115,19 +1119,7 @@ class CookingVecEnv:
             n = wshape[0]
         else:
             raise ValueError(f"load_value: shapes {wshape} and {bshape}, expected [64] / [1, 64] and [1], or stacks [n, 64] / [n, 1, 64] and [n, 1]")
-        parts = []
-        for v, shape in zip((wv, bv), ((n, H), (n, 1))):
-            if hasattr(v, "data_ptr") or hasattr(v, "ptr"):
-                if str(v.dtype) not in ("torch.float32", "float32"):
-                    raise ValueError(f"load_value: device tensors must be float32, not {v.dtype}")
-                parts.append(v)
-            else:
-                key = ("value", len(parts), shape)
-                buf = self._policy_stage.get(key)
-                if buf is None:
-                    buf = self._policy_stage[key] = self.alloc(shape, np.float32)
-                buf.from_host(np.ascontiguousarray(v, np.float32).reshape(shape))
-                parts.append(buf)
+        parts = [self._weight_part("load_value", "value", k, v, shape) for k, (v, shape) in enumerate(zip((wv, bv), ((n, H), (n, 1))))]
         p = _dev_ptr
         _native.check(self._h, _native.lib().cz_load_value_device(self._h, n, p(parts[0]), p(parts[1])))
 
