@@ -15,6 +15,7 @@
 #include "../../include/cookingzoo.h"
 #include "cz_launch.h"
 #include "cz_generate.h"
+#include "cz_owned.h"
 
 using namespace cz;
 
@@ -267,72 +268,87 @@ __global__ __launch_bounds__(64) void k_save_where(const uint32_t *__restrict__ 
 // host: handle + C-ABI
 // ======================================================================================================
 
+// the owners of everything a handle (or a call) has to give back
+template <class T> using DevMem = Owned<T *, hipFree>;          // hipMalloc
+template <class T> using PinnedMem = Owned<T *, hipHostFree>;   // hipHostMalloc
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+using OwnedGraph = Owned<hipGraph_t, hipGraphDestroy>;
+using OwnedGraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+
 struct cz_handle_s {
     cz_config cfg;
     Params P;
-    hipStream_t stream = nullptr;      // the stream every call of this handle is ordered on
-    hipStream_t own_stream = nullptr;  // the one cz_create made (cz_set_stream may point `stream` at a caller's)
+    hipStream_t stream = nullptr;      // the stream every call of this handle is ordered on (not owned: own_stream, or a caller's)
+    // Members are destroyed in reverse order of declaration: the streams stand in front of every buffer, event and graph that work on
+    // them may still reference, so they outlive them (cz_destroy has waited for all four by then).
+    OwnedStream own_stream;            // the one cz_create made (cz_set_stream may point `stream` at a caller's)
+    OwnedStream rank_stream;           // cz_load_layout_ranks: its copies run here; the handle's stream waits for them on the device
+    OwnedStream copy_stream;           // cz_update_layouts copies run here, beside the steps
+    OwnedStream split_stream;          // the second chain of a split run (made by its first one)
     Launchers kl;
     int n_layouts = 0, n_recipes = 0;
-    uint32_t *d_state = nullptr, *d_lay_init = nullptr, *d_lay_desc = nullptr, *d_recipes = nullptr;
-    uint32_t *d_lay_block = nullptr;       // the allocation behind d_lay_init: LAY_CTL_WORDS control words, then the records
-    uint16_t *d_lay_rank = nullptr;        // [L][W * H]: the position of a cell's static object in world_objects[class] (cz_load_layout_ranks, cz_generate_layouts)
+    DevMem<uint32_t> d_state, d_lay_desc, d_recipes;
+    DevMem<uint32_t> d_lay_block;          // the allocation behind d_lay_init: LAY_CTL_WORDS control words, then the records
+    uint32_t *d_lay_init = nullptr;        // a view: the records inside d_lay_block
+    DevMem<uint16_t> d_lay_rank;           // [L][W * H]: the position of a cell's static object in world_objects[class] (cz_load_layout_ranks, cz_generate_layouts)
     std::vector<uint8_t> rank_ok;          // per pool slot: its rank row belongs to its layout
     int rank_missing = 0;                  // how many do not
-    uint16_t *h_rank_stage = nullptr;      // pinned staging of cz_load_layout_ranks, a place per slot
-    hipStream_t rank_stream = nullptr;     // its copies run here; the handle's stream waits for them on the device
-    hipEvent_t ev_rank_done = nullptr;
-    float *d_policy = nullptr;             // cz_load_policy_device: POLICY_MAX_SETS packed weight sets (cz_policy.h), allocated on the first load
+    PinnedMem<uint16_t> h_rank_stage;      // pinned staging of cz_load_layout_ranks, a place per slot
+    OwnedEvent ev_rank_done;               // behind its copies on rank_stream
+    DevMem<float> d_policy;                // cz_load_policy_device: POLICY_MAX_SETS packed weight sets (cz_policy.h), allocated on the first load
     int32_t n_policy_sets = 0;             // sets the last load filled; 0: no table
     int32_t n_value_sets = 0;              // cz_load_value_device: sets whose value head (behind the sets, same allocation) the last load filled
-    uint32_t *d_partner = nullptr;         // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
+    DevMem<uint32_t> d_partner;            // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
     int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
     int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
-    char *h_lay_stage = nullptr;           // pinned staging of cz_update_layouts: [L] records, then [L] descriptors
-    hipStream_t copy_stream = nullptr;     // cz_update_layouts copies run here, beside the steps
-    hipEvent_t ev_copy_done = nullptr, ev_steps_issued = nullptr;
+    PinnedMem<char> h_lay_stage;           // pinned staging of cz_update_layouts: [L] records, then [L] descriptors
+    OwnedEvent ev_copy_done, ev_steps_issued;
     bool copy_pending = false;             // a copy has been issued that no cz_set_layout_group has waited for yet
     struct SlotRange { int32_t first, count; };
     std::vector<SlotRange> upd_ranges;     // staged by cz_update_layouts, not copied yet (flush_updates)
     std::vector<SlotRange> staged_on_copy, staged_on_main;   // slots of copies issued on the copy stream / in order on the handle's stream whose completion nobody has seen yet
-    hipEvent_t ev_main_copy_done = nullptr;
+    OwnedEvent ev_main_copy_done;
     int32_t lay_groups = 1, lay_active = 0;
     int64_t n_layout_updates = 0;
-    void *d_gen_tables = nullptr;          // cz_load_level_programs: failure counter | program offsets | programs | level of every slot
+    DevMem<void> d_gen_tables;             // cz_load_level_programs: failure counter | program offsets | programs | level of every slot
     GenParams gen = {};                     // ... and where its parts are
     int gen_layouts = 0;                   // the pool size those tables were made for
     std::vector<SlotRange> gen_slices;     // per pool slot: the run of slots of its level (the pool slice an env of that level draws from)
-    void *d_spawn_tables = nullptr;        // cz_set_spawn: exhausted-respawn counter | spawn areas per (level, agent) | level of every layout
+    DevMem<void> d_spawn_tables;           // cz_set_spawn: exhausted-respawn counter | spawn areas per (level, agent) | level of every layout
     int spawn_layouts = 0;                 // the pool size those tables were made for
     uint32_t spawn_bits = 5;               // width of the countdown fields the resident records are packed with (spawn_grace_bits)
-    uint32_t *d_stat_u = nullptr;
-    double *d_stat_f = nullptr;
-    uint32_t *d_ep_seen = nullptr;     // [N]: stat_u[e][SU_EPISODES] at the last cz_episodes_collect
-    int32_t *d_ep_blocks = nullptr;    // [ceil(N / EP_BLOCK)]: found envs per block, between the two launches of a collect
-    cz_stats *d_stats_out = nullptr;
-    unsigned long long *d_stats_part = nullptr;   // [256 chains][16 columns] between the two stages of the reduction
-    double *d_lut = nullptr;
-    void *d_sprites = nullptr;         // cz_load_sprites: float table [256] | sheet [RENDER_SPRITES][M][M] RGBA
+    DevMem<uint32_t> d_stat_u;
+    DevMem<double> d_stat_f;
+    DevMem<uint32_t> d_ep_seen;        // [N]: stat_u[e][SU_EPISODES] at the last cz_episodes_collect
+    DevMem<int32_t> d_ep_blocks;       // [ceil(N / EP_BLOCK)]: found envs per block, between the two launches of a collect
+    DevMem<cz_stats> d_stats_out;
+    DevMem<unsigned long long> d_stats_part;      // [256 chains][16 columns] between the two stages of the reduction
+    DevMem<double> d_lut;
+    DevMem<void> d_sprites;            // cz_load_sprites: float table [256] | sheet [RENDER_SPRITES][M][M] RGBA
     int32_t sprites_M = 0;             // 0: no sheet loaded
     double obs_table[LUT_SIZE];        // host copy of the quotient table (cz_obs_table: what the compact observation's codes index)
-    int32_t *d_reset_words = nullptr;  // [3][N]: layout ids, recipe words, pool words of a cz_reset call
-    unsigned long long *d_reset_refused = nullptr;   // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
-    unsigned long long *d_restore_refused = nullptr; // cz_restore_device: envs whose slot or row was refused (cz_restore_device_refused)
-    unsigned long long *d_tasks_refused = nullptr;   // cz_set_tasks_device: envs whose new recipe ids were out of range (cz_set_tasks_refused)
-    uint8_t *d_goal = nullptr;             // cz_load_goal_table: [n_goal_rows][GOAL_ROW_NODES] goal ids
+    DevMem<int32_t> d_reset_words;     // [3][N]: layout ids, recipe words, pool words of a cz_reset call
+    DevMem<unsigned long long> d_reset_refused;      // cz_reset_device: envs whose explicit layout id was out of range (cz_reset_device_refused)
+    DevMem<unsigned long long> d_restore_refused;    // cz_restore_device: envs whose slot or row was refused (cz_restore_device_refused)
+    DevMem<unsigned long long> d_tasks_refused;      // cz_set_tasks_device: envs whose new recipe ids were out of range (cz_set_tasks_refused)
+    DevMem<uint8_t> d_goal;                // cz_load_goal_table: [n_goal_rows][GOAL_ROW_NODES] goal ids
     int n_goal_rows = 0;                   // rows in use (0: none, or dropped by cz_load_recipes)
     int num_goals = 0;                     // the length of a goal vector
     uint8_t *codes = nullptr;          // cz_set_compact_output: one-step launches also write the compact observation here
     float *obs32 = nullptr;            // cz_set_f32_output: one-step launches called with d_obs = NULL write float32 rows here
-    void *d_codes_stage = nullptr;     // cz_step_compact with pageable host memory: device staging of the codes
-    void *d_dump = nullptr;            // [N][4] doubles: where a one-step launch writes an output array the caller passed as NULL
+    DevMem<void> d_codes_stage;        // cz_step_compact with pageable host memory: device staging of the codes
+    DevMem<void> d_dump;               // [N][4] doubles: where a one-step launch writes an output array the caller passed as NULL
     // staging for the host-pointer API
-    int32_t *d_actions = nullptr;
-    double *d_obs = nullptr;
-    char *d_small = nullptr, *h_small = nullptr;   // rewards | terminations | truncations | marks: one device block, one pinned block
-    uint32_t *h_marks = nullptr, *d_marks_mapped = nullptr;   // pinned, device-mapped marks buffer of the direct path
+    DevMem<int32_t> d_actions;
+    DevMem<double> d_obs;
+    DevMem<char> d_small;                          // rewards | terminations | truncations | marks: one device block, one pinned block
+    PinnedMem<char> h_small;
+    PinnedMem<uint32_t> h_marks;                   // pinned, device-mapped marks buffer of the direct path
+    uint32_t *d_marks_mapped = nullptr;            // ... as the device sees it (a view)
     std::vector<uint32_t> last_marks;          // recipe marks after the most recent cz_step (cz_last_marks)
-    char *h_stage = nullptr, *d_stage = nullptr;   // small batches: pinned, device-mapped staging block of cz_step
+    PinnedMem<char> h_stage;                       // small batches: pinned, device-mapped staging block of cz_step
+    char *d_stage = nullptr;                       // ... as the device sees it (a view)
     // cz_step_device_ring: which ring / output buffers / tables the cached graphs were captured for
     struct RingKey {
         const int32_t *ring = nullptr; int64_t stride = 0; int32_t period = 0;
@@ -343,15 +359,16 @@ struct cz_handle_s {
                    trunc == o.trunc && stream == o.stream && version == o.version && parts == o.parts;
         }
     } ring_key;
-    struct RunGraph { int32_t slot, len; hipGraphExec_t ge, ge2; uint64_t used; };   // ge2: the second chain of a split run, or null
+    // (hidden: the std::vector<RunGraph> members and its destructor are instantiated with it and must not join the library's exports)
+    struct __attribute__((visibility("hidden"))) RunGraph { int32_t slot, len; OwnedGraphExec ge, ge2; uint64_t used; };   // ge2: the second chain of a split run, or null
     std::vector<RunGraph> ring_graphs;             // replayable runs of this ring, keyed by (first slot, length)
     uint64_t ring_clock = 0;
     int64_t n_graph_kernels = 0, n_direct_kernels = 0;
     uint64_t tables_version = 0;                   // bumped whenever something the launches capture by value changes
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    OwnedEvent ev0, ev1;
     // kernel timing
     bool ktime = false;
-    std::vector<hipEvent_t> kev;
+    std::vector<OwnedEvent> kev;
     size_t kev_used = 0;
     double ktime_ms = 0.0;
     int64_t klaunches = 0;
@@ -378,10 +395,9 @@ struct cz_handle_s {
     int32_t ring_prefix = 0;       // CZ_RING_PREFIX: steps of a cz_step_device_ring call launched directly in front of its first graph
     int32_t ring_split = -1;       // cz_set_ring_split / CZ_RING_SPLIT: -1 automatic, 0 off, 2 two launch chains (run_split)
     bool few_queues = false;       // GPU_MAX_HW_QUEUES below 4 in the environment of cz_create: runs are never split
-    hipStream_t split_stream = nullptr;            // the second chain of a split run (made by its first one)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    OwnedEvent ev_fork, ev_join;                   // in front of and behind the second chain of a split run
     size_t zero_copy_bytes = (size_t)256 << 10;   // cz_step: batches whose buffers fit use the pinned device-mapped block (CZ_ZERO_COPY_BYTES)
-    cz_stats *d_gather = nullptr;
+    DevMem<cz_stats> d_gather;
     std::string err;
 };
 
@@ -482,6 +498,7 @@ extern "C" uint32_t cz_next_layout_group(int64_t env_global, uint32_t episode, u
     return next_layout(env_global, episode, pool_word, n_layouts, groups ? groups : 1u, active);
 }
 
+static int create_resources(cz_handle h, int C);
 extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     if (!cfg || !out) return fail(nullptr, "cz_create: null argument");
     *out = nullptr;
@@ -509,21 +526,24 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     if (cfg->device_id < 0 || cfg->device_id >= ndev) return fail(nullptr, "cz_create: device_id %d out of range", cfg->device_id);
     cz_handle h = new cz_handle_s();
     h->cfg = *cfg;
-    // from here on a failure must release what was already created
-#define CREATE_CHK(call)                                                                          \
-    do {                                                                                          \
-        hipError_t _e = (call);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            fail(nullptr, "cz_create: %s failed: %s", #call, hipGetErrorString(_e));             \
-            cz_destroy(h);                                                                        \
-            return 1;                                                                             \
-        }                                                                                         \
-    } while (0)
-    CREATE_CHK(hipSetDevice(cfg->device_id));
-    CREATE_CHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    // from here on a failure must release what was already created, and is reported as cz_create's (there is no handle to ask)
+    if (create_resources(h, C)) {
+        fail(nullptr, "cz_create: %s", h->err.c_str());
+        cz_destroy(h);
+        return 1;
+    }
+    *out = h;
+    return 0;
+}
+// what a fresh handle holds: its stream and events, the settings of the environment, the kernel instance, the records, statistics and
+// scratch of the batch, the constant tables behind Params::lut
+static int create_resources(cz_handle h, int C) {
+    const cz_config *const cfg = &h->cfg;
+    HIPCHK(h, hipSetDevice(cfg->device_id));
+    HIPCHK(h, hipStreamCreateWithFlags(h->own_stream.out(), hipStreamNonBlocking));
     h->stream = h->own_stream;
-    CREATE_CHK(hipEventCreate(&h->ev0));
-    CREATE_CHK(hipEventCreate(&h->ev1));
+    HIPCHK(h, hipEventCreate(h->ev0.out()));
+    HIPCHK(h, hipEventCreate(h->ev1.out()));
     Params &P = h->P;
     memset(&P, 0, sizeof P);
     P.N = cfg->num_envs; P.A = cfg->num_agents; P.W = cfg->width; P.H = cfg->height; P.D = cfg->max_dyn; P.F = cfg->feat_len;
@@ -551,7 +571,7 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     // (read, never set: with fewer than 4 hardware queues the runtime can crash replaying a graph that has parallel branches)
     if (const char *s = getenv("GPU_MAX_HW_QUEUES")) h->few_queues = atoi(s) < 4;
 #ifdef CZ_SMALL_ONLY      // diagnostic libraries that carry the small instance only
-    if (!(P.D <= 64 && C <= 64)) { fail(nullptr, "cz_create: this diagnostic library holds the small kernel instance only"); cz_destroy(h); return 1; }
+    if (!(P.D <= 64 && C <= 64)) return fail(h, "this diagnostic library holds the small kernel instance only");
     h->kl = launchers_small();
 #else
     h->instance = (P.D <= 64 && C <= 64) ? 0 : (P.D <= 128 && C <= 256) ? 1 : 2;
@@ -568,26 +588,26 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
     }
     const size_t N = (size_t)P.N;
     const size_t state_bytes = N * P.RW * 4;
-    CREATE_CHK(hipMalloc(&h->d_state, state_bytes));
-    CREATE_CHK(hipMemsetAsync(h->d_state, 0, state_bytes, h->stream));
-    CREATE_CHK(hipMalloc(&h->d_stat_u, N * SU_WORDS * 4));
-    CREATE_CHK(hipMalloc(&h->d_stat_f, N * SF_WORDS * 8));
-    CREATE_CHK(hipMemsetAsync(h->d_stat_u, 0, N * SU_WORDS * 4, h->stream));
-    CREATE_CHK(hipMemsetAsync(h->d_stat_f, 0, N * SF_WORDS * 8, h->stream));
-    CREATE_CHK(hipMalloc(&h->d_ep_seen, N * 4));
-    CREATE_CHK(hipMemsetAsync(h->d_ep_seen, 0, N * 4, h->stream));
-    CREATE_CHK(hipMalloc(&h->d_ep_blocks, ((N + EP_BLOCK - 1) / EP_BLOCK) * sizeof(int32_t)));
-    CREATE_CHK(hipMalloc(&h->d_stats_out, sizeof(cz_stats)));
-    CREATE_CHK(hipMalloc(&h->d_dump, N * MAX_AGENTS * sizeof(double)));
-    CREATE_CHK(hipMalloc(&h->d_reset_words, N * 3 * sizeof(int32_t)));
-    CREATE_CHK(hipMalloc(&h->d_reset_refused, sizeof(unsigned long long)));
-    CREATE_CHK(hipMemsetAsync(h->d_reset_refused, 0, sizeof(unsigned long long), h->stream));
-    CREATE_CHK(hipMalloc(&h->d_restore_refused, sizeof(unsigned long long)));
-    CREATE_CHK(hipMemsetAsync(h->d_restore_refused, 0, sizeof(unsigned long long), h->stream));
-    CREATE_CHK(hipMalloc(&h->d_tasks_refused, sizeof(unsigned long long)));
-    CREATE_CHK(hipMemsetAsync(h->d_tasks_refused, 0, sizeof(unsigned long long), h->stream));
-    CREATE_CHK(hipMalloc(&h->d_stats_part, (size_t)STAT_CHAINS * 16 * sizeof(unsigned long long)));
-    CREATE_CHK(hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMalloc(h->d_state.out(), state_bytes));
+    HIPCHK(h, hipMemsetAsync(h->d_state, 0, state_bytes, h->stream));
+    HIPCHK(h, hipMalloc(h->d_stat_u.out(), N * SU_WORDS * 4));
+    HIPCHK(h, hipMalloc(h->d_stat_f.out(), N * SF_WORDS * 8));
+    HIPCHK(h, hipMemsetAsync(h->d_stat_u, 0, N * SU_WORDS * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_stat_f, 0, N * SF_WORDS * 8, h->stream));
+    HIPCHK(h, hipMalloc(h->d_ep_seen.out(), N * 4));
+    HIPCHK(h, hipMemsetAsync(h->d_ep_seen, 0, N * 4, h->stream));
+    HIPCHK(h, hipMalloc(h->d_ep_blocks.out(), ((N + EP_BLOCK - 1) / EP_BLOCK) * sizeof(int32_t)));
+    HIPCHK(h, hipMalloc(h->d_stats_out.out(), sizeof(cz_stats)));
+    HIPCHK(h, hipMalloc(h->d_dump.out(), N * MAX_AGENTS * sizeof(double)));
+    HIPCHK(h, hipMalloc(h->d_reset_words.out(), N * 3 * sizeof(int32_t)));
+    HIPCHK(h, hipMalloc(h->d_reset_refused.out(), sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(h->d_reset_refused, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMalloc(h->d_restore_refused.out(), sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(h->d_restore_refused, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMalloc(h->d_tasks_refused.out(), sizeof(unsigned long long)));
+    HIPCHK(h, hipMemsetAsync(h->d_tasks_refused, 0, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMalloc(h->d_stats_part.out(), (size_t)STAT_CHAINS * 16 * sizeof(unsigned long long)));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     P.state = h->d_state; P.stat_u = h->d_stat_u; P.stat_f = h->d_stat_f;
     {   // observation quotients: (x - ax) / W and (y - ay) / H for every possible difference, computed here with the same
         // IEEE-754 double division Python's int / int true division performs (cooking_env.py:364-368)
@@ -630,17 +650,15 @@ extern "C" int cz_create(const cz_config *cfg, cz_handle *out) {
             rowsel[l] = (8u * (lc / 9u)) | ((4u * (lc % 9u)) << 8);
         }
         static_assert(LUT_BLOCK_BYTES == sizeof lut + sizeof submask + sizeof(SpawnCfg) + sizeof coords + sizeof rowsel, "layout of the block behind Params::lut");
-        CREATE_CHK(hipMalloc(&h->d_lut, LUT_BLOCK_BYTES));
-        CREATE_CHK(hipMemset(h->d_lut, 0, LUT_BLOCK_BYTES));
-        CREATE_CHK(hipMemcpy((char *)h->d_lut + COORD_TABLE_OFFSET, coords, sizeof coords, hipMemcpyHostToDevice));
-        CREATE_CHK(hipMemcpy((char *)h->d_lut + ROWSEL_TABLE_OFFSET, rowsel, sizeof rowsel, hipMemcpyHostToDevice));
-        CREATE_CHK(hipMemcpy(h->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
-        CREATE_CHK(hipMemcpy((char *)h->d_lut + sizeof lut, submask, sizeof submask, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMalloc(h->d_lut.out(), LUT_BLOCK_BYTES));
+        HIPCHK(h, hipMemset(h->d_lut, 0, LUT_BLOCK_BYTES));
+        HIPCHK(h, hipMemcpy((char *)h->d_lut.get() + COORD_TABLE_OFFSET, coords, sizeof coords, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy((char *)h->d_lut.get() + ROWSEL_TABLE_OFFSET, rowsel, sizeof rowsel, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy((char *)h->d_lut.get() + sizeof lut, submask, sizeof submask, hipMemcpyHostToDevice));
         P.lut = h->d_lut;
         memcpy(h->obs_table, lut, sizeof lut);
     }
-#undef CREATE_CHK
-    *out = h;
     return 0;
 }
 
@@ -648,37 +666,13 @@ extern "C" int cz_destroy(cz_handle h) {
     if (!h) return 0;
     (void)hipSetDevice(h->cfg.device_id);
     (void)hipStreamSynchronize(h->stream);
+    for (hipStream_t s : {h->copy_stream.get(), h->rank_stream.get(), h->split_stream.get()})
+        if (s) (void)hipStreamSynchronize(s);
     if (h->comm && h->rccl) {
         typedef int (*destroy_t)(void *);
         destroy_t f = (destroy_t)dlsym(h->rccl, "ncclCommDestroy");
         if (f) f(h->comm);
     }
-    void *ptrs[] = {h->d_codes_stage, h->d_spawn_tables, h->d_gen_tables, h->d_reset_words, h->d_reset_refused, h->d_restore_refused, h->d_tasks_refused, h->d_goal, h->d_dump, h->d_lut, h->d_sprites, h->d_state, h->d_lay_block, h->d_lay_desc, h->d_lay_rank, h->d_partner, h->d_policy, h->d_recipes, h->d_stat_u, h->d_stat_f, h->d_ep_seen, h->d_ep_blocks, h->d_stats_out, h->d_stats_part,
-                    h->d_actions, h->d_obs, h->d_small, h->d_gather};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto &r : h->ring_graphs) {
-        if (r.ge) (void)hipGraphExecDestroy(r.ge);
-        if (r.ge2) (void)hipGraphExecDestroy(r.ge2);
-    }
-    if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-    if (h->ev_copy_done) (void)hipEventDestroy(h->ev_copy_done);
-    if (h->ev_steps_issued) (void)hipEventDestroy(h->ev_steps_issued);
-    if (h->ev_main_copy_done) (void)hipEventDestroy(h->ev_main_copy_done);
-    if (h->h_lay_stage) (void)hipHostFree(h->h_lay_stage);
-    if (h->rank_stream) { (void)hipStreamSynchronize(h->rank_stream); (void)hipStreamDestroy(h->rank_stream); }
-    if (h->ev_rank_done) (void)hipEventDestroy(h->ev_rank_done);
-    if (h->split_stream) { (void)hipStreamSynchronize(h->split_stream); (void)hipStreamDestroy(h->split_stream); }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->h_rank_stage) (void)hipHostFree(h->h_rank_stage);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_small) (void)hipHostFree(h->h_small);
-    if (h->h_marks) (void)hipHostFree(h->h_marks);
-    for (hipEvent_t e : h->kev) (void)hipEventDestroy(e);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
     return 0;
 }
@@ -730,7 +724,7 @@ extern "C" int cz_set_spawn(cz_handle h, double despawn_rate, double respawn_rat
     }
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_spawn_tables) { HIPCHK(h, hipFree(h->d_spawn_tables)); h->d_spawn_tables = nullptr; }
+    h->d_spawn_tables.reset();
     h->spawn_layouts = 0;
     const uint32_t new_bits = spawn_grace_bits((uint32_t)grace_period, h->P.A);
     if (new_bits != h->spawn_bits) {       // episodes in flight keep their countdowns: re-pack them to the new field width
@@ -743,17 +737,17 @@ extern "C" int cz_set_spawn(cz_handle h, double despawn_rate, double respawn_rat
     if (on) {
         // one allocation: the counter word, the areas, the level of every layout
         const size_t off_areas = 16, off_levels = off_areas + ((areas.size() + 15) & ~(size_t)15);
-        HIPCHK(h, hipMalloc(&h->d_spawn_tables, off_levels + levels.size() + 16));
+        HIPCHK(h, hipMalloc(h->d_spawn_tables.out(), off_levels + levels.size() + 16));
         HIPCHK(h, hipMemset(h->d_spawn_tables, 0, off_levels + levels.size() + 16));
-        HIPCHK(h, hipMemcpy((char *)h->d_spawn_tables + off_areas, areas.data(), areas.size(), hipMemcpyHostToDevice));
-        HIPCHK(h, hipMemcpy((char *)h->d_spawn_tables + off_levels, levels.data(), levels.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy((char *)h->d_spawn_tables.get() + off_areas, areas.data(), areas.size(), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy((char *)h->d_spawn_tables.get() + off_levels, levels.data(), levels.size(), hipMemcpyHostToDevice));
         cfg.stride = (uint32_t)stride;
-        cfg.exhausted = (uint32_t *)h->d_spawn_tables;
-        cfg.areas = (const uint8_t *)h->d_spawn_tables + off_areas;
-        cfg.level_of_layout = (const uint8_t *)h->d_spawn_tables + off_levels;
+        cfg.exhausted = (uint32_t *)h->d_spawn_tables.get();
+        cfg.areas = (const uint8_t *)h->d_spawn_tables.get() + off_areas;
+        cfg.level_of_layout = (const uint8_t *)h->d_spawn_tables.get() + off_levels;
         h->spawn_layouts = h->n_layouts;
     }
-    HIPCHK(h, hipMemcpy((char *)h->d_lut + SPAWN_CFG_OFFSET, &cfg, sizeof cfg, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_lut.get() + SPAWN_CFG_OFFSET, &cfg, sizeof cfg, hipMemcpyHostToDevice));
     h->P.auto_reset = (h->P.auto_reset & 1) | (on ? 2 : 0);
     h->tables_version++;
     return 0;
@@ -809,9 +803,10 @@ extern "C" int cz_load_recipes(cz_handle h, const uint32_t *table, int32_t n, in
     for (int i = 0; i < n; ++i)
         if (table[(size_t)i * row_words] > (uint32_t)max_nodes) return fail(h, "cz_load_recipes: recipe %d has more than %d nodes", i, max_nodes);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    if (h->d_recipes) { HIPCHK(h, hipStreamSynchronize(h->stream)); HIPCHK(h, hipFree(h->d_recipes)); h->d_recipes = nullptr; h->P.recipes = nullptr; }
+    if (h->d_recipes) HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->d_recipes.reset(); h->P.recipes = nullptr;
     size_t bytes = (size_t)n * row_words * 4;
-    HIPCHK(h, hipMalloc(&h->d_recipes, bytes));
+    HIPCHK(h, hipMalloc(h->d_recipes.out(), bytes));
     // device copy: word 0 = node count; node words are re-encoded for the kernels: conditions become an accept mask over
     // the state index chopped | mashed << 1
     std::vector<uint32_t> dev(table, table + (size_t)n * row_words);
@@ -908,22 +903,22 @@ extern "C" int cz_load_layouts(cz_handle h, const uint32_t *init_records, const 
                            "cz_reset / cz_set_state them into the new range first, or load a pool that is not smaller",
                         misfits, n, h->n_layouts);
     }
-    if (h->d_lay_block) { HIPCHK(h, hipFree(h->d_lay_block)); h->d_lay_block = nullptr; h->d_lay_init = nullptr; h->P.lay_init = nullptr; }
-    if (h->d_lay_desc) { HIPCHK(h, hipFree(h->d_lay_desc)); h->d_lay_desc = nullptr; h->P.lay_desc = nullptr; }
+    h->d_lay_block.reset(); h->d_lay_init = nullptr; h->P.lay_init = nullptr;
+    h->d_lay_desc.reset(); h->P.lay_desc = nullptr;
     if (h->rank_stream) HIPCHK(h, hipStreamSynchronize(h->rank_stream));
-    if (h->d_lay_rank) { HIPCHK(h, hipFree(h->d_lay_rank)); h->d_lay_rank = nullptr; }
-    if (h->h_rank_stage) { HIPCHK(h, hipHostFree(h->h_rank_stage)); h->h_rank_stage = nullptr; }
-    if (h->h_lay_stage) { HIPCHK(h, hipHostFree(h->h_lay_stage)); h->h_lay_stage = nullptr; }
+    h->d_lay_rank.reset();
+    h->h_rank_stage.reset();
+    h->h_lay_stage.reset();
     size_t b0 = (size_t)n * h->P.RW * 4, b1 = (size_t)n * h->P.F * 4;
     // the records, behind LAY_CTL_WORDS control words (which part of their pool slices the envs draw from: all of it)
-    HIPCHK(h, hipMalloc(&h->d_lay_block, LAY_CTL_WORDS * 4 + b0));
+    HIPCHK(h, hipMalloc(h->d_lay_block.out(), LAY_CTL_WORDS * 4 + b0));
     h->d_lay_init = h->d_lay_block + LAY_CTL_WORDS;
-    HIPCHK(h, hipMalloc(&h->d_lay_desc, b1 + 16));                 // + padding: descriptors are fetched in pairs
+    HIPCHK(h, hipMalloc(h->d_lay_desc.out(), b1 + 16));                 // + padding: descriptors are fetched in pairs
     HIPCHK(h, hipMemsetAsync(h->d_lay_block, 0, LAY_CTL_WORDS * 4, h->stream));
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)(h->d_lay_block + LC_GROUPS), 1, 1, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_lay_desc, 0, b1 + 16, h->stream));
     const size_t b2 = (size_t)n * h->P.W * h->P.H * sizeof(uint16_t);
-    HIPCHK(h, hipMalloc(&h->d_lay_rank, b2));
+    HIPCHK(h, hipMalloc(h->d_lay_rank.out(), b2));
     HIPCHK(h, hipMemsetAsync(h->d_lay_rank, 0, b2, h->stream));
     h->rank_ok.assign((size_t)n, 0);
     h->rank_missing = n;
@@ -992,12 +987,12 @@ extern "C" int cz_update_layouts(cz_handle h, int32_t first, int32_t count, cons
     if (caller_capturing(h)) return fail(h, "cz_update_layouts: not inside a stream capture of the caller (it records an event on the captured stream)");
     const size_t RWb = (size_t)h->P.RW * 4, Fb = (size_t)h->P.F * 4, L = (size_t)h->n_layouts;
     if (!h->copy_stream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_copy_done, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_steps_issued, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_main_copy_done, hipEventDisableTiming));
+        HIPCHK(h, hipStreamCreateWithFlags(h->copy_stream.out(), hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_copy_done.out(), hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_steps_issued.out(), hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_main_copy_done.out(), hipEventDisableTiming));
     }
-    if (!h->h_lay_stage) HIPCHK(h, hipHostMalloc((void **)&h->h_lay_stage, L * (RWb + Fb), hipHostMallocDefault));
+    if (!h->h_lay_stage) HIPCHK(h, hipHostMalloc((void **)h->h_lay_stage.out(), L * (RWb + Fb), hipHostMallocDefault));
     if (count == 0) return 0;               // (count 0: only sets up the copy stream and the staging block, ahead of time)
     // The staging block has a place per slot.  Only an earlier copy of THESE slots that is still running, or not even issued,
     // is in the way (with the rotation of cz_set_layout_group consecutive updates go to different parts of the pool).
@@ -1123,19 +1118,19 @@ extern "C" int cz_load_level_programs(cz_handle h, const uint32_t *programs, int
     }
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_gen_tables) { HIPCHK(h, hipFree(h->d_gen_tables)); h->d_gen_tables = nullptr; }
+    h->d_gen_tables.reset();
     h->gen_layouts = 0;
     const size_t off_offs = 16, off_prog = off_offs + (((size_t)n_levels * 4 + 15) & ~(size_t)15), off_levels = off_prog + (((size_t)words * 4 + 15) & ~(size_t)15);
-    HIPCHK(h, hipMalloc(&h->d_gen_tables, off_levels + levels.size() + 16));
+    HIPCHK(h, hipMalloc(h->d_gen_tables.out(), off_levels + levels.size() + 16));
     HIPCHK(h, hipMemset(h->d_gen_tables, 0, off_levels + levels.size() + 16));
-    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_prog, programs, (size_t)words * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables + off_levels, levels.data(), levels.size(), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables.get() + off_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables.get() + off_prog, programs, (size_t)words * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_gen_tables.get() + off_levels, levels.data(), levels.size(), hipMemcpyHostToDevice));
     GenParams &G = h->gen;
-    G.failures = (uint32_t *)h->d_gen_tables;
-    G.prog_off = (const uint32_t *)((char *)h->d_gen_tables + off_offs);
-    G.programs = (const uint32_t *)((char *)h->d_gen_tables + off_prog);
-    G.level_of_slot = (const uint8_t *)h->d_gen_tables + off_levels;
+    G.failures = (uint32_t *)h->d_gen_tables.get();
+    G.prog_off = (const uint32_t *)((char *)h->d_gen_tables.get() + off_offs);
+    G.programs = (const uint32_t *)((char *)h->d_gen_tables.get() + off_prog);
+    G.level_of_slot = (const uint8_t *)h->d_gen_tables.get() + off_levels;
     G.RW = h->P.RW; G.F = h->P.F; G.W = h->P.W; G.H = h->P.H; G.D = h->P.D; G.A = h->P.A; G.dyn0_off = h->P.dyn0_off;
     // the image offsets of the handle's kernel instance (soa.Dims.img_layout): the huge one keeps a larger image
     G.img_obj0 = h->huge ? Img<16>::OBJ0 : Img<1>::OBJ0; G.img_cell0 = h->huge ? Img<16>::CELL0 : Img<1>::CELL0;
@@ -1391,9 +1386,9 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
     else P.wt = (obs_bytes > ((size_t)224 << 20) && (size_t)P.F * (f32 ? 4 : 8) >= 4096) ? 2 : 0;
     if (h->wt_override >= 0) P.wt = h->wt_override;
     if (!fused) {             // the one-step kernels store rewards and flags unconditionally
-        if (!P.rewards) P.rewards = (double *)h->d_dump;
-        if (!P.term) P.term = (uint8_t *)h->d_dump;
-        if (!P.trunc) P.trunc = (uint8_t *)h->d_dump;
+        if (!P.rewards) P.rewards = (double *)h->d_dump.get();
+        if (!P.term) P.term = (uint8_t *)h->d_dump.get();
+        if (!P.trunc) P.trunc = (uint8_t *)h->d_dump.get();
     }
 #ifdef CZ_TIMELINE
     P.timeline = (h->tl_base && h->tl_cap > 0) ? h->tl_base + (size_t)(h->tl_count++ % h->tl_cap) * (size_t)P.N * 2 : nullptr;
@@ -1407,7 +1402,7 @@ static int launch_step(cz_handle h, const StepCall &call, const RunSplit *split 
         while (h->kev.size() < h->kev_used + 2) {
             hipEvent_t e;
             HIPCHK(h, hipEventCreate(&e));
-            h->kev.push_back(e);
+            h->kev.emplace_back(e);
         }
         e0 = h->kev[h->kev_used]; e1 = h->kev[h->kev_used + 1];
         h->kev_used += 2;
@@ -1445,16 +1440,16 @@ extern "C" int cz_reset(cz_handle h, int64_t b, int64_t c, const int32_t *layout
     }
     // persistent scratch of the handle (cz_create: three words per env; the observation staging is shared with cz_step / cz_observe)
     int32_t *const d_lay = h->d_reset_words;
-    uint32_t *const d_rec = (uint32_t *)h->d_reset_words + h->P.N, *const d_pool = (uint32_t *)h->d_reset_words + 2 * (size_t)h->P.N;
+    uint32_t *const d_rec = (uint32_t *)h->d_reset_words.get() + h->P.N, *const d_pool = (uint32_t *)h->d_reset_words.get() + 2 * (size_t)h->P.N;
     HIPCHK(h, hipMemcpyAsync(d_lay, layout_ids, (size_t)c * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_rec, recipe_ids, (size_t)c * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_pool, pools.data(), (size_t)c * 4, hipMemcpyHostToDevice, h->stream));
     size_t ob = (size_t)c * h->P.A * h->P.F * 8;
-    if (obs && !h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, (size_t)h->P.N * h->P.A * h->P.F * 8));
+    if (obs && !h->d_obs) HIPCHK(h, hipMalloc(h->d_obs.out(), (size_t)h->P.N * h->P.A * h->P.F * 8));
     Params P = h->P;
     hipLaunchKernelGGL(k_count_aborted, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, h->stream, h->d_stat_u, h->d_state, h->P.RW,
                        (long long)b, (int)c);
-    const hipError_t rc = h->kl.reset(P, h->stream, b, (int)c, d_lay, d_rec, d_pool, obs ? h->d_obs : nullptr);
+    const hipError_t rc = h->kl.reset(P, h->stream, b, (int)c, d_lay, d_rec, d_pool, obs ? h->d_obs.get() : nullptr);
     return copy_back_and_wait(h, rc, obs, h->d_obs, ob);            // (pools, a host vector, must outlive its copy)
 }
 
@@ -1465,7 +1460,7 @@ extern "C" int cz_observe(cz_handle h, int64_t b, int64_t c, double *obs) {
     if (!obs) return fail(h, "cz_observe: null buffer");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     size_t ob = (size_t)c * h->P.A * h->P.F * 8;
-    if (!h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, (size_t)h->P.N * h->P.A * h->P.F * 8));
+    if (!h->d_obs) HIPCHK(h, hipMalloc(h->d_obs.out(), (size_t)h->P.N * h->P.A * h->P.F * 8));
     Params P = h->P;
     return copy_back_and_wait(h, h->kl.observe(P, h->stream, b, (int)c, h->d_obs, nullptr), obs, h->d_obs, ob);
 }
@@ -1490,10 +1485,10 @@ extern "C" int cz_observe_compact(cz_handle h, int64_t b, int64_t c, uint8_t *co
     if (!codes) return fail(h, "cz_observe_compact: null buffer");
     if (set_device(h)) return 1;
     const size_t row = (size_t)h->P.A * codes_pitch(h->P.F);
-    if (!h->d_codes_stage) HIPCHK(h, hipMalloc(&h->d_codes_stage, (size_t)h->P.N * row));
+    if (!h->d_codes_stage) HIPCHK(h, hipMalloc(h->d_codes_stage.out(), (size_t)h->P.N * row));
     Params P = h->P;
     P.wt = 0;
-    return copy_back_and_wait(h, h->kl.observe(P, h->stream, b, (int)c, nullptr, (uint8_t *)h->d_codes_stage), codes, h->d_codes_stage, (size_t)c * row);
+    return copy_back_and_wait(h, h->kl.observe(P, h->stream, b, (int)c, nullptr, (uint8_t *)h->d_codes_stage.get()), codes, h->d_codes_stage, (size_t)c * row);
 }
 
 static int set_device(cz_handle h) {
@@ -1656,14 +1651,14 @@ extern "C" int cz_load_sprites(cz_handle h, const uint8_t *rgba, int32_t n_sprit
     if (M < 1 || M > RENDER_M_MAX) return fail(h, "cz_load_sprites: M = %d is outside [1, %d]", M, RENDER_M_MAX);
     if (set_device(h)) return 1;
     HIPCHK(h, hipStreamSynchronize(h->stream));                        // (a launch in flight may still read the old sheet)
-    if (h->d_sprites) { HIPCHK(h, hipFree(h->d_sprites)); h->d_sprites = nullptr; h->sprites_M = 0; }
+    h->d_sprites.reset(); h->sprites_M = 0;
     const size_t bytes = (size_t)RENDER_SPRITES * M * M * 4;
     float ftab[256];
     const volatile float inv = 1.0f / 255.0f;                          // render.py: v * (1 / 255) in float32, torch's `x / 255` on the device
     for (int v = 0; v < 256; ++v) ftab[v] = (float)v * inv;
-    HIPCHK(h, hipMalloc(&h->d_sprites, sizeof ftab + bytes));
+    HIPCHK(h, hipMalloc(h->d_sprites.out(), sizeof ftab + bytes));
     HIPCHK(h, hipMemcpy(h->d_sprites, ftab, sizeof ftab, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy((char *)h->d_sprites + sizeof ftab, rgba, bytes, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy((char *)h->d_sprites.get() + sizeof ftab, rgba, bytes, hipMemcpyHostToDevice));
     h->sprites_M = M;
     return 0;
 }
@@ -1677,8 +1672,8 @@ extern "C" int cz_render_device(cz_handle h, int64_t b, int64_t c, int32_t P, ui
     if (set_device(h)) return 1;
     RenderArgs G{};
     G.env_begin = b;
-    G.ftab = (const float *)h->d_sprites;
-    G.sheet = (const uint32_t *)((const char *)h->d_sprites + 256 * sizeof(float));
+    G.ftab = (const float *)h->d_sprites.get();
+    G.sheet = (const uint32_t *)((const char *)h->d_sprites.get() + 256 * sizeof(float));
     G.rgb8 = d_rgb8; G.chw32 = d_chw32;
     G.P = (uint32_t)P; G.M = (uint32_t)h->sprites_M; G.vis = vis;
     // the reference's own float expressions in its own order (graphic_pipeline.py:46-55, 197-220; render.geometry), every product
@@ -1735,10 +1730,10 @@ extern "C" int cz_load_layout_ranks(cz_handle h, int32_t first, int32_t count, c
     // through a pinned staging block of the library, on a stream of its own: the caller's thread does not wait for the steps it has
     // issued (a refill under a stepping batch), and what it issues next on the handle's stream waits for the copy on the device
     if (!h->rank_stream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->rank_stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_rank_done, hipEventDisableTiming));
+        HIPCHK(h, hipStreamCreateWithFlags(h->rank_stream.out(), hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_rank_done.out(), hipEventDisableTiming));
     }
-    if (!h->h_rank_stage) HIPCHK(h, hipHostMalloc((void **)&h->h_rank_stage, (size_t)h->n_layouts * C * sizeof(uint16_t), hipHostMallocDefault));
+    if (!h->h_rank_stage) HIPCHK(h, hipHostMalloc((void **)h->h_rank_stage.out(), (size_t)h->n_layouts * C * sizeof(uint16_t), hipHostMallocDefault));
     else HIPCHK(h, hipEventSynchronize(h->ev_rank_done));             // (the last copy out of the staging block: over long ago)
     uint16_t *const stage = h->h_rank_stage + (size_t)first * C;
     memcpy(stage, ranks, (size_t)count * C * sizeof(uint16_t));
@@ -1771,9 +1766,9 @@ extern "C" int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t 
     if (set_device(h)) return 1;
     if (caller_capturing(h)) return fail(h, "cz_load_partner_table: not inside a stream capture of the caller (it allocates and copies)");
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_partner) { HIPCHK(h, hipFree(h->d_partner)); h->d_partner = nullptr; h->n_partner = h->partner_rows_alloc = 0; }
+    h->d_partner.reset(); h->n_partner = h->partner_rows_alloc = 0;
     const size_t bytes = (size_t)n * PARTNER_ROW_WORDS * 4, counter = (bytes + 7) / 8 * 8;
-    HIPCHK(h, hipMalloc(&h->d_partner, counter + 8));
+    HIPCHK(h, hipMalloc(h->d_partner.out(), counter + 8));
     HIPCHK(h, hipMemsetAsync(h->d_partner, 0, counter + 8, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_partner, rows, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1781,7 +1776,7 @@ extern "C" int cz_load_partner_table(cz_handle h, const uint32_t *rows, int32_t 
     return 0;
 }
 static unsigned long long *partner_counter(cz_handle h) {
-    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_partner) + ((size_t)h->partner_rows_alloc * PARTNER_ROW_WORDS * 4 + 7) / 8 * 8);
+    return reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h->d_partner.get()) + ((size_t)h->partner_rows_alloc * PARTNER_ROW_WORDS * 4 + 7) / 8 * 8);
 }
 // The scripted partner on the current state into DEVICE buffers (k_partner, cz_query.h; definition: cooking_zoo_amd/partner.py): the
 // action the reference's CookingAgent would return for every chosen agent of every env.  Stream-ordered, nothing is copied, waited
@@ -1824,9 +1819,9 @@ extern "C" int cz_load_goal_table(cz_handle h, const uint8_t *goal_ids, int32_t 
                 return fail(h, "cz_load_goal_table: recipe %d node %u: goal id %u (a node of the recipe: below num_goals = %d; past its %u nodes: 0xFF)", i, j, id, num_goals, nn);
         }
     }
-    if (h->d_goal) { HIPCHK(h, hipFree(h->d_goal)); h->d_goal = nullptr; h->n_goal_rows = 0; }
+    h->d_goal.reset(); h->n_goal_rows = 0;
     const size_t bytes = (size_t)n * GOAL_ROW_NODES;
-    HIPCHK(h, hipMalloc(&h->d_goal, bytes));
+    HIPCHK(h, hipMalloc(h->d_goal.out(), bytes));
     HIPCHK(h, hipMemcpyAsync(h->d_goal, goal_ids, bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->n_goal_rows = n;
@@ -1934,7 +1929,7 @@ extern "C" int cz_obs_table(cz_handle h, double *table) {
     memcpy(table, h->obs_table, sizeof h->obs_table);
     return 0;
 }
-extern "C" const void *cz_obs_table_device(cz_handle h) { return h ? (const void *)h->d_lut : nullptr; }
+extern "C" const void *cz_obs_table_device(cz_handle h) { return h ? (const void *)h->d_lut.get() : nullptr; }
 
 static bool ring_fusable(cz_handle h, const StepCall &c, int32_t K, int64_t stride);
 static int launch_ring_fused(cz_handle h, const StepCall &c, int32_t K, const int32_t *d_ring, int64_t stride, int32_t period, int32_t first_slot);
@@ -1970,9 +1965,9 @@ static int split_begin(cz_handle h, RunSplit &s) {
     const int32_t whole = (half + epw - 1) / epw * epw;
     s.begin1 = whole < N ? whole : half;
     if (!h->split_stream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->split_stream, hipStreamNonBlocking));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        HIPCHK(h, hipStreamCreateWithFlags(h->split_stream.out(), hipStreamNonBlocking));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_fork.out(), hipEventDisableTiming));
+        HIPCHK(h, hipEventCreateWithFlags(h->ev_join.out(), hipEventDisableTiming));
     }
     s.side = h->split_stream;
     return 0;
@@ -2043,10 +2038,10 @@ constexpr int RING_MAX_GRAPH = 256, RING_CACHE = 64;   // (rocprofv3 --kernel-tr
 // captures the launches of slots [slot, slot + len) on stream `on` (nothing executes) and instantiates them: the whole launches
 // (part < 0), or one chain of a split run - part 0 on the handle's stream, part 1 on the second stream, behind the phase offset
 static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t stride, int32_t slot, int32_t len, hipStream_t on,
-                        const RunSplit *split, int part, hipGraphExec_t &ge) {
+                        const RunSplit *split, int part, OwnedGraphExec &ge) {
     RunSplit one;
     if (split) { one = *split; one.only = part; }
-    hipGraph_t g = nullptr;
+    OwnedGraph g;
     HIPCHK(h, hipStreamBeginCapture(on, hipStreamCaptureModeThreadLocal));
     if (part == 1 && CZ_RING_DELAY_SLEEPS > 0) hipLaunchKernelGGL(k_ring_delay, dim3(1), dim3(64), 0, on);
     int bad = 0;
@@ -2054,21 +2049,16 @@ static int ring_capture(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t
         c.actions = d_ring + (int64_t)(slot + s) * stride;
         bad = launch_step(h, c, split ? &one : nullptr);
     }
-    const hipError_t ec = hipStreamEndCapture(on, &g);
-    if (bad) { if (g) (void)hipGraphDestroy(g); return 1; }
+    const hipError_t ec = hipStreamEndCapture(on, g.out());
+    if (bad) return 1;
     HIPCHK(h, ec);
-    const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ei != hipSuccess) { ge = nullptr; HIPCHK(h, ei); }
+    const hipError_t ei = hipGraphInstantiate(ge.out(), g, nullptr, nullptr, 0);
+    if (ei != hipSuccess) { (void)ge.release(); HIPCHK(h, ei); }
     return 0;
 }
 // drops every cached graph (waits for the ones still executing: a split replay ends joined onto the handle's stream)
 static void ring_drop(cz_handle h) {
     if (!h->ring_graphs.empty()) (void)hipStreamSynchronize(h->stream);
-    for (auto &r : h->ring_graphs) {
-        if (r.ge) (void)hipGraphExecDestroy(r.ge);
-        if (r.ge2) (void)hipGraphExecDestroy(r.ge2);
-    }
     h->ring_graphs.clear();
 }
 static bool ring_select(cz_handle h, const int32_t *d_ring, int64_t stride, int32_t period, double *d_obs, double *d_rewards,
@@ -2094,15 +2084,13 @@ static int ring_graph(cz_handle h, StepCall &c, const int32_t *d_ring, int64_t s
         for (size_t i = 1; i < h->ring_graphs.size(); ++i)
             if (h->ring_graphs[i].used < h->ring_graphs[victim].used) victim = i;
         HIPCHK(h, hipStreamSynchronize(h->stream));            // it may still be executing
-        (void)hipGraphExecDestroy(h->ring_graphs[victim].ge);
-        if (h->ring_graphs[victim].ge2) (void)hipGraphExecDestroy(h->ring_graphs[victim].ge2);
         h->ring_graphs.erase(h->ring_graphs.begin() + (long)victim);
     }
-    hipGraphExec_t ge = nullptr, ge2 = nullptr;
-    if (ring_capture(h, c, d_ring, stride, slot, len, h->stream, split, split ? 0 : -1, ge)) return 1;
-    if (split && ring_capture(h, c, d_ring, stride, slot, len, split->side, split, 1, ge2)) { (void)hipGraphExecDestroy(ge); return 1; }
-    h->ring_graphs.push_back({slot, len, ge, ge2, h->ring_clock});
-    out = ge; out2 = ge2;
+    cz_handle_s::RunGraph r{slot, len, {}, {}, h->ring_clock};
+    if (ring_capture(h, c, d_ring, stride, slot, len, h->stream, split, split ? 0 : -1, r.ge)) return 1;
+    if (split && ring_capture(h, c, d_ring, stride, slot, len, split->side, split, 1, r.ge2)) return 1;
+    out = r.ge; out2 = r.ge2;
+    h->ring_graphs.push_back(std::move(r));
     return 0;
 }
 // cz_set_ring_fused: the run as fused launches over the ring's own action rows (cz_rollout_actions' kernel, every step's outputs
@@ -2306,10 +2294,9 @@ extern "C" int cz_load_policy_device(cz_handle h, int32_t n_sets, const float *d
     if (!h->d_policy) {
         if (caller_capturing(h)) return fail(h, "cz_load_policy_device: the handle's first load allocates the table: call it once outside the capture");
         // (room for the value heads behind the sets: cz_load_value_device; zeroed, so that no launch reads what nobody wrote)
-        HIPCHK(h, hipMalloc(&h->d_policy, (size_t)policy_table_floats(h->P.F) * sizeof(float)));
+        HIPCHK(h, hipMalloc(h->d_policy.out(), (size_t)policy_table_floats(h->P.F) * sizeof(float)));
         if (!policy_taggable(h->d_policy)) {            // (no device address is: policy_encode would refuse every launch)
-            (void)hipFree(h->d_policy);
-            h->d_policy = nullptr;
+            h->d_policy.reset();
             return fail(h, "cz_load_policy_device: device address above 2^48");
         }
         HIPCHK(h, hipMemsetAsync(h->d_policy + policy_value_offset(h->P.F), 0, POLICY_VALUE_FLOATS * sizeof(float), h->stream));
@@ -2562,7 +2549,7 @@ static int host_step(cz_handle h, const int32_t *actions, double *obs, uint8_t *
                  total = o_obs + ob;
     if (total <= h->zero_copy_bytes) {
         if (!h->h_stage) {
-            HIPCHK(h, hipHostMalloc((void **)&h->h_stage, total, hipHostMallocMapped));
+            HIPCHK(h, hipHostMalloc((void **)h->h_stage.out(), total, hipHostMallocMapped));
             HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_stage, h->h_stage, 0));
         }
         memcpy(h->h_stage + o_act, actions, NA * 4);
@@ -2581,7 +2568,7 @@ static int host_step(cz_handle h, const int32_t *actions, double *obs, uint8_t *
              *d_trunc = mapped_device_pointer(trunc), *d_obs = obs ? mapped_device_pointer(obs) : nullptr;
         if (d_act && d_rew && d_term && d_trunc && (!obs || d_obs)) {
             if (!h->h_marks) {
-                HIPCHK(h, hipHostMalloc((void **)&h->h_marks, (size_t)h->P.N * 8, hipHostMallocMapped));
+                HIPCHK(h, hipHostMalloc((void **)h->h_marks.out(), (size_t)h->P.N * 8, hipHostMallocMapped));
                 HIPCHK(h, hipHostGetDevicePointer((void **)&h->d_marks_mapped, h->h_marks, 0));
             }
             StepCall c{(const int32_t *)d_act, (double *)d_obs, (double *)d_rew, (uint8_t *)d_term, (uint8_t *)d_trunc};
@@ -2594,13 +2581,13 @@ static int host_step(cz_handle h, const int32_t *actions, double *obs, uint8_t *
     const size_t s_rew = 0, s_term = NA * 8, s_trunc = s_term + ((NA + 15) & ~(size_t)15), s_marks = s_trunc + ((NA + 15) & ~(size_t)15),
                  s_total = s_marks + (size_t)h->P.N * 8;
     if (!h->d_actions) {
-        HIPCHK(h, hipMalloc(&h->d_actions, NA * 4));
-        HIPCHK(h, hipMalloc(&h->d_small, s_total));
-        HIPCHK(h, hipHostMalloc((void **)&h->h_small, s_total, hipHostMallocDefault));
+        HIPCHK(h, hipMalloc(h->d_actions.out(), NA * 4));
+        HIPCHK(h, hipMalloc(h->d_small.out(), s_total));
+        HIPCHK(h, hipHostMalloc((void **)h->h_small.out(), s_total, hipHostMallocDefault));
     }
-    if (obs && !h->d_obs) HIPCHK(h, hipMalloc(&h->d_obs, ob));
+    if (obs && !h->d_obs) HIPCHK(h, hipMalloc(h->d_obs.out(), ob));
     HIPCHK(h, hipMemcpyAsync(h->d_actions, actions, NA * 4, hipMemcpyHostToDevice, h->stream));
-    StepCall c{h->d_actions, obs ? h->d_obs : nullptr, (double *)(h->d_small + s_rew), (uint8_t *)(h->d_small + s_term), (uint8_t *)(h->d_small + s_trunc)};
+    StepCall c{h->d_actions, obs ? h->d_obs.get() : nullptr, (double *)(h->d_small + s_rew), (uint8_t *)(h->d_small + s_term), (uint8_t *)(h->d_small + s_trunc)};
     c.marks = (uint32_t *)(h->d_small + s_marks);
     return run(c, s_total, h->h_small, s_rew, s_term, s_trunc, h->h_small + s_marks);
 }
@@ -2617,8 +2604,8 @@ extern "C" int cz_step_compact(cz_handle h, const int32_t *actions, uint8_t *cod
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const size_t bytes = (size_t)h->P.N * h->P.A * (size_t)codes_pitch(h->P.F);
     void *direct = mapped_device_pointer(codes);
-    if (!direct && !h->d_codes_stage) HIPCHK(h, hipMalloc(&h->d_codes_stage, bytes));
-    if (host_step(h, actions, nullptr, direct ? (uint8_t *)direct : (uint8_t *)h->d_codes_stage, rewards, term, trunc)) return 1;
+    if (!direct && !h->d_codes_stage) HIPCHK(h, hipMalloc(h->d_codes_stage.out(), bytes));
+    if (host_step(h, actions, nullptr, direct ? (uint8_t *)direct : (uint8_t *)h->d_codes_stage.get(), rewards, term, trunc)) return 1;
     if (!direct) {
         HIPCHK(h, hipMemcpyAsync(codes, h->d_codes_stage, bytes, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2658,20 +2645,19 @@ template <class Policy>
 static int probe_closed_loop(cz_handle h, const StepCall &c, int32_t K, int32_t reps, float *us_per_step, Policy &&policy) {
     const bool was_timing = h->ktime;
     h->ktime = false;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
+    OwnedGraph g;
+    OwnedGraphExec ge;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     int bad = 0;
     for (int k = 0; k < K && !bad; ++k) {
         bad = launch_step(h, c);
         if (!bad && !getenv("CZ_PROBE_NO_POLICY")) policy();
     }
-    const hipError_t ec = hipStreamEndCapture(h->stream, &g);
+    const hipError_t ec = hipStreamEndCapture(h->stream, g.out());
     h->ktime = was_timing;
-    if (bad) { if (g) (void)hipGraphDestroy(g); return 1; }
+    if (bad) return 1;
     HIPCHK(h, ec);
-    const hipError_t ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
+    const hipError_t ei = hipGraphInstantiate(ge.out(), g, nullptr, nullptr, 0);
     HIPCHK(h, ei);
     hipError_t rc = hipGraphLaunch(ge, h->stream);                         // warm
     if (rc == hipSuccess) rc = hipEventRecord(h->ev0, h->stream);
@@ -2680,7 +2666,6 @@ static int probe_closed_loop(cz_handle h, const StepCall &c, int32_t K, int32_t 
     if (rc == hipSuccess) rc = hipEventSynchronize(h->ev1);
     float ms = 0.f;
     if (rc == hipSuccess) rc = hipEventElapsedTime(&ms, h->ev0, h->ev1);
-    (void)hipGraphExecDestroy(ge);
     HIPCHK(h, rc);
     *us_per_step = ms * 1e3f / (float)((int64_t)reps * K);
     return 0;
@@ -2853,7 +2838,7 @@ extern "C" int cz_episodes_collect(cz_handle h, uint8_t *d_mask, double *d_retur
     const bool ranked = d_list || d_count;
     if (ranked) hipLaunchKernelGGL(k_episodes_count, grid, block, 0, h->stream, h->d_stat_u, h->d_ep_seen, N, h->d_ep_blocks);
     hipLaunchKernelGGL(k_episodes_collect, grid, block, 0, h->stream, h->d_stat_u, h->d_stat_f, h->d_ep_seen, N, h->P.A, h->P.env_id_base,
-                       ranked ? h->d_ep_blocks : nullptr, d_mask, d_return, d_length, d_flags, d_list, capacity, d_count);
+                       ranked ? h->d_ep_blocks.get() : nullptr, d_mask, d_return, d_length, d_flags, d_list, capacity, d_count);
     HIPCHK(h, hipGetLastError());
     return 0;
 }
@@ -2917,7 +2902,7 @@ extern "C" int cz_comm_init(cz_handle h, int32_t n_ranks, int32_t rank, const ui
     int r = f(&h->comm, n_ranks, u, rank);
     if (r) return fail(h, "ncclCommInitRank failed: %d", r);
     h->n_ranks = n_ranks; h->rank = rank;
-    HIPCHK(h, hipMalloc(&h->d_gather, sizeof(cz_stats) * (size_t)n_ranks));
+    HIPCHK(h, hipMalloc(h->d_gather.out(), sizeof(cz_stats) * (size_t)n_ranks));
     return 0;
 }
 extern "C" int cz_stats_allgather(cz_handle h, cz_stats *out) {
