@@ -299,6 +299,9 @@ struct cz_handle_s {
     DevMem<float> d_policy;                // cz_load_policy_device: POLICY_MAX_SETS packed weight sets (cz_policy.h), allocated on the first load
     int32_t n_policy_sets = 0;             // sets the last load filled; 0: no table
     int32_t n_value_sets = 0;              // cz_load_value_device: sets whose value head (behind the sets, same allocation) the last load filled
+    DevMem<unsigned char> d_ppo;           // cz_ppo_reserve: the workspace of cz_ppo_grad_device (ppo_carve), for ...
+    int64_t ppo_positions = 0;             // ... minibatches of up to this many positions (0: none reserved) over ...
+    int32_t ppo_sets = 0;                  // ... this many loaded sets
     DevMem<uint32_t> d_partner;            // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
     int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
     int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
@@ -379,6 +382,7 @@ struct cz_handle_s {
     int wt_override = -1;          // CZ_WT experiment switch, read once
     bool lean_enabled = true;      // CZ_LEAN=0: one-step launches always take the generic kernel (A/B runs, tests)
     bool lean_cfg_enabled = true;  // CZ_LEAN_CFG=0: lean launches always take k_step_lean, never a k_step_lean_cfg (A/B runs)
+    int ppo_tile = PPO_TILE;               // CZ_PPO_TILE=<features per workgroup>: k_ppo_outer's instance (tools/ppo_sizes.py)
     int gae_shape = GAE_DEPTH * 1000 + GAE_BLOCK;   // CZ_GAE_SHAPE=<rows ahead>x<workgroup size>: k_gae's instance (tools/targets_sizes.py)
     int last_step_variant = -1;    // cz_diag_last_step_variant
     int last_step_lean = -1;       // which kernel the most recent launch_step took: 1 k_step_lean, 0 another one (cz_diag_last_step_lean)
@@ -564,6 +568,7 @@ static int create_resources(cz_handle h, int C) {
         int d = 0, w = 0;
         if (sscanf(s, "%dx%d", &d, &w) == 2) h->gae_shape = d * 1000 + w;      // (a shape the library does not carry is refused by the call)
     }
+    if (const char *s = getenv("CZ_PPO_TILE")) h->ppo_tile = atoi(s);      // (a tile the library does not carry is refused by the call)
     if (const char *s = getenv("CZ_GRAPH_MIN_RUN")) h->graph_min_run = atoi(s) < 4 ? 4 : (atoi(s) > 256 ? 256 : atoi(s));   // 4..RING_MAX_GRAPH
     if (const char *s = getenv("CZ_RING_PREFIX")) h->ring_prefix = atoi(s) < 0 ? 0 : (atoi(s) > 16 ? 16 : atoi(s));
     if (const char *s = getenv("CZ_ZERO_COPY_BYTES")) h->zero_copy_bytes = (size_t)atoll(s);
@@ -2493,6 +2498,120 @@ extern "C" int cz_logprob_device(cz_handle h, int64_t rows, const float *d_logit
     const dim3 grid((unsigned)((G.total + 255) / 256));
     if (cz_num_actions(h) == 5) hipLaunchKernelGGL((k_logprob<5>), grid, dim3(256), 0, h->stream, G);
     else hipLaunchKernelGGL((k_logprob<8>), grid, dim3(256), 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// ---- PPO's gradients (definition: cooking_zoo_amd/ppo.py; k_ppo_forward / k_ppo_outer / k_ppo_reduce in cz_query.h)
+// The workspace of a call over `positions` positions and `n_sets` loaded sets, carved from `base` into G -> its size in bytes
+static size_t ppo_carve(unsigned char *base, int64_t positions, int A, int F, int n_sets, PpoArgs &G) {
+    const size_t pairs = (size_t)positions * (size_t)A, slots = pairs * 2u, chunks = (size_t)((positions + PPO_CHUNK - 1) / PPO_CHUNK);
+    size_t at = 0;
+    const auto take = [&](auto *&field, size_t count) {
+        using T = std::remove_reference_t<decltype(*field)>;
+        field = reinterpret_cast<T *>(base + at);
+        at += (count * sizeof(T) + 255u) & ~(size_t)255u;
+    };
+    take(G.terms, pairs * PPO_TERMS);
+    take(G.chunk_stats, chunks * PPO_TERMS);
+    take(G.hid, slots * POLICY_HIDDEN);
+    take(G.da, slots * POLICY_HIDDEN);
+    take(G.small, slots * PPO_SMALL);
+    take(G.partial, chunks * (size_t)n_sets * ppo_set_floats(F));
+    return at;
+}
+// the most positions a call may name: (position, agent) pairs and their rows stay within 31 bits
+static int64_t ppo_max_positions(cz_handle h) { return (int64_t)0x3FFFFFFF / h->P.A; }
+// Allocates the workspace of cz_ppo_grad_device for minibatches of up to max_positions positions over the sets loaded now: per (position,
+// agent) two pass slots (hidden vector, da, the scalars) and the statistics' terms, per (chunk of 64 positions, loaded set) one partial
+// gradient.  Outside a capture; a call that asks for no more than is reserved does nothing (and is legal anywhere).
+extern "C" int cz_ppo_reserve(cz_handle h, int64_t max_positions) {
+    if (ready(h)) return 1;
+    if (!h->d_policy || h->n_policy_sets == 0) return fail(h, "cz_ppo_reserve: no weight table loaded (cz_load_policy_device): the workspace is sized by the loaded sets");
+    if (max_positions < 1 || max_positions > ppo_max_positions(h)) return fail(h, "cz_ppo_reserve: max_positions is %lld, not 1..%lld", (long long)max_positions, (long long)ppo_max_positions(h));
+    if (max_positions <= h->ppo_positions && h->n_policy_sets <= h->ppo_sets) return 0;
+    if (caller_capturing(h)) return fail(h, "cz_ppo_reserve: %lld positions over %d sets need an allocation: call it outside the capture", (long long)max_positions, h->n_policy_sets);
+    if (set_device(h)) return 1;
+    const int64_t positions = max_positions > h->ppo_positions ? max_positions : h->ppo_positions;
+    const int32_t n_sets = h->n_policy_sets > h->ppo_sets ? h->n_policy_sets : h->ppo_sets;
+    PpoArgs G{};
+    const size_t bytes = ppo_carve(nullptr, positions, h->P.A, h->P.F, n_sets, G);
+    HIPCHK(h, hipStreamSynchronize(h->stream));        // (a call issued earlier may still be using the old workspace)
+    h->ppo_positions = 0;
+    h->ppo_sets = 0;
+    HIPCHK(h, hipMalloc(h->d_ppo.out(), bytes));
+    h->ppo_positions = positions;
+    h->ppo_sets = n_sets;
+    return 0;
+}
+extern "C" int64_t cz_ppo_reserved(cz_handle h) { return h ? h->ppo_positions : -1; }
+extern "C" int32_t cz_ppo_chunk(void) { return PPO_CHUNK; }
+// The gradient of PPO's clipped-surrogate loss with value and entropy terms over a minibatch of a trajectory in device memory
+// (ppo.host_ppo_grad): d_obs32 float32 [rows][A][F], d_actions int32 [rows][A], d_logp_old / d_adv / d_ret float32 [rows][A]; d_index int32
+// [positions] names the minibatch's rows (NULL: positions == rows, row m), an index outside 0 .. rows-1 contributes nothing and is
+// counted in d_stats[7].  `sets` / `vsets` as in cz_rollout_policy_value.  The gradients come in torch.nn.Linear's layouts behind a
+// leading axis of cz_policy_sets(h): d_gw1 [n][64][F], d_gb1 [n][64], d_gw2 [n][C][64], d_gb2 [n][C], d_gwv [n][64], d_gbv [n][1]; sets no
+// agent uses get zeros.  d_stats float64 [8] (may be NULL).  Three launches on the handle's stream: nothing is copied, waited for or
+// allocated (legal inside a stream capture of the caller); no record is read.
+extern "C" int cz_ppo_grad_device(cz_handle h, int64_t rows, int64_t positions, const int32_t *d_index, const float *d_obs32, const int32_t *d_actions,
+                                  const float *d_logp_old, const float *d_adv, const float *d_ret, uint32_t sets, uint32_t vsets, double clip,
+                                  double c_value, double c_entropy, float *d_gw1, float *d_gb1, float *d_gw2, float *d_gb2, float *d_gwv, float *d_gbv,
+                                  double *d_stats) {
+    if (ready(h)) return 1;
+    const int A = h->P.A, F = h->P.F;
+    const int64_t packed = check_policy_call(h, "cz_ppo_grad_device", sets, (int32_t)POLICY_GREEDY, false);
+    if (packed < 0) return 1;
+    int with_value = 0;
+    int64_t vpacked = (int64_t)policy_pack_vsets(0xFFFFFFFFu, A);
+    bool any_value = false;
+    for (int a = 0; a < A; ++a) any_value |= ((vsets >> (8 * a)) & 0xFFu) != POLICY_NONE;
+    if (any_value) {                  // (without a critic no value head need be loaded)
+        vpacked = check_value_call(h, "cz_ppo_grad_device", vsets, &with_value);
+        if (vpacked < 0) return 1;
+    }
+    int with_policy = 0;
+    uint32_t used = 0;
+    for (int a = 0; a < A; ++a) {
+        const uint32_t s = (sets >> (8 * a)) & 0xFFu, vs = (vsets >> (8 * a)) & 0xFFu;
+        if (s != POLICY_NONE) { ++with_policy; used |= 1u << s; }
+        if (vs != POLICY_NONE) used |= 1u << vs;
+    }
+    if (!with_policy && !with_value) return fail(h, "cz_ppo_grad_device: every agent is at 0xFF in both sets and vsets");
+    if (rows < 1 || rows > ppo_max_positions(h)) return fail(h, "cz_ppo_grad_device: rows is %lld, not 1..%lld", (long long)rows, (long long)ppo_max_positions(h));
+    if (positions < 1) return fail(h, "cz_ppo_grad_device: positions is %lld, not >= 1", (long long)positions);
+    if (positions > h->ppo_positions) return fail(h, "cz_ppo_grad_device: %lld positions, but the workspace holds %lld (cz_ppo_reserve)", (long long)positions, (long long)h->ppo_positions);
+    if (h->n_policy_sets > h->ppo_sets) return fail(h, "cz_ppo_grad_device: %d sets are loaded, but the workspace was reserved for %d (cz_ppo_reserve again)", h->n_policy_sets, h->ppo_sets);
+    if (!d_index && positions != rows) return fail(h, "cz_ppo_grad_device: without an index positions (%lld) must equal rows (%lld)", (long long)positions, (long long)rows);
+    if (!d_obs32 || !d_actions || !d_logp_old || !d_adv || !d_ret) return fail(h, "cz_ppo_grad_device: the rows, actions, logp_old, advantages or returns pointer is null");
+    if (!d_gw1 || !d_gb1 || !d_gw2 || !d_gb2) return fail(h, "cz_ppo_grad_device: a gradient pointer of the policy's four tensors is null");
+    if (with_value && (!d_gwv || !d_gbv)) return fail(h, "cz_ppo_grad_device: a value set is named, but a value-gradient pointer is null");
+    if (!(clip >= 0.0)) return fail(h, "cz_ppo_grad_device: clip is %g, not >= 0", clip);
+    if (!(c_value >= 0.0)) return fail(h, "cz_ppo_grad_device: c_value is %g, not >= 0", c_value);
+    if (!(c_entropy >= 0.0)) return fail(h, "cz_ppo_grad_device: c_entropy is %g, not >= 0", c_entropy);
+    if (h->ppo_tile != 16 && h->ppo_tile != 32 && h->ppo_tile != 64) return fail(h, "cz_ppo_grad_device: CZ_PPO_TILE names %d features; the library carries 16, 32 and 64", h->ppo_tile);
+    if (set_device(h)) return 1;
+    PpoArgs G{};
+    G.rows = rows; G.positions = (int32_t)positions; G.A = A; G.F = F; G.C = cz_num_actions(h); G.n_sets = h->n_policy_sets;
+    G.packed = (uint32_t)packed; G.vpacked = (uint32_t)vpacked; G.used = used;
+    G.index = d_index; G.obs32 = d_obs32; G.actions = d_actions; G.logp_old = d_logp_old; G.adv = d_adv; G.ret = d_ret;
+    G.table = h->d_policy;
+    G.K.inv_p = with_policy ? 1.0 / (double)(positions * with_policy) : 0.0;
+    G.K.inv_v = with_value ? 1.0 / (double)(positions * with_value) : 0.0;
+    G.K.lo = 1.0 - clip; G.K.hi = 1.0 + clip; G.K.c_value = c_value; G.K.c_entropy = c_entropy;
+    (void)ppo_carve(h->d_ppo.get(), positions, A, F, G.n_sets, G);
+    G.gw1 = d_gw1; G.gb1 = d_gb1; G.gw2 = d_gw2; G.gb2 = d_gb2; G.gwv = d_gwv; G.gbv = d_gbv; G.stats = d_stats;
+    const unsigned pairs = (unsigned)(positions * A), chunks = (unsigned)((positions + PPO_CHUNK - 1) / PPO_CHUNK);
+    const size_t lds = (size_t)policy_quads(F) * 16u;
+    if (G.C == 5) hipLaunchKernelGGL((k_ppo_forward<5>), dim3(pairs), dim3(64), lds, h->stream, G);
+    else hipLaunchKernelGGL((k_ppo_forward<8>), dim3(pairs), dim3(64), lds, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    const dim3 outer(chunks, (unsigned)((F + h->ppo_tile - 1) / h->ppo_tile), (unsigned)G.n_sets);
+    if (h->ppo_tile == 16) hipLaunchKernelGGL((k_ppo_outer<16>), outer, dim3(64), 0, h->stream, G);
+    else if (h->ppo_tile == 32) hipLaunchKernelGGL((k_ppo_outer<32>), outer, dim3(64), 0, h->stream, G);
+    else hipLaunchKernelGGL((k_ppo_outer<64>), outer, dim3(64), 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    const unsigned elements = ppo_set_floats(F) * (unsigned)G.n_sets + PPO_TERMS;
+    hipLaunchKernelGGL((k_ppo_reduce<0>), dim3((elements + 255u) / 256u), dim3(256), 0, h->stream, G);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -3,7 +3,8 @@
 // and policy_value.  k_policy and k_value (cz_query.h) and k_step<..., ROLLOUT_POLICY / ROLLOUT_POLICY_VALUE> (cz_kernels.h) all call
 // them, so the launches of their own and the fused rollouts cannot differ.
 // Beside them cz_log and policy_logprob, the log-probability and entropy of the distribution policy_heads samples from (k_logprob;
-// definition: cooking_zoo_amd/targets.py).
+// definition: cooking_zoo_amd/targets.py), and policy_all_logits and policy_ppo_logit_grad, the forward and the float64 part of PPO's
+// gradients (k_ppo_forward; definition: cooking_zoo_amd/ppo.py).
 #pragma once
 #include "cz_device.h"
 
@@ -83,7 +84,7 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 // the float32 rows a policy reads, in LDS: per env A rows of 4 * policy_quads(F) floats, the tail zeroed (sized by the launch)
 extern __shared__ float4_t policy_rows[];
 
-// exp on [-64, 0] in plain float64 arithmetic, every operation rounded on its own (the build has -ffp-contract=off): numpy
+// exp on [-64, 64] in plain float64 arithmetic, every operation rounded on its own (the build has -ffp-contract=off): numpy
 // reproduces it bit for bit (policy.cz_exp)
 __host__ __device__ inline double policy_exp(double z) {
     const double k = floor(z * 1.4426950408889634 + 0.5);
@@ -211,6 +212,67 @@ __device__ __forceinline__ void policy_heads(const float *__restrict__ set, int 
 __device__ __forceinline__ float policy_value(const float *__restrict__ table, int F, uint32_t vs, float hid, int lane) {
     const float *const heads = table + policy_value_offset(F);
     return policy_butterfly(heads[vs * POLICY_HIDDEN + (uint32_t)lane] * hid) + heads[POLICY_MAX_SETS * POLICY_HIDDEN + vs];
+}
+
+// ---- PPO's clipped-surrogate loss, differentiated (definition: cooking_zoo_amd/ppo.py; kernels: k_ppo_forward, k_ppo_outer and
+// k_ppo_reduce in cz_query.h).  The scales the host computes once per call:
+struct PpoScales {
+    double inv_p, inv_v;           // 1 / (positions * agents with a policy set), ... with a value set; 0.0 where there is none
+    double lo, hi;                 // 1 - eps, 1 + eps
+    double c_value, c_entropy;
+};
+constexpr int PPO_CHUNK = 64;                // positions per chunk: every (chunk, set) has accumulators of its own (ppo.py)
+constexpr int PPO_TERMS = 8;                 // the statistics' terms of one (position, agent)
+// The logits of one row under set `set` - policy_heads' arithmetic, every lane gets every logit
+template <int C>
+__device__ __forceinline__ void policy_all_logits(const float *__restrict__ set, int Fq, float hid, int lane, float (&logit)[C]) {
+    const float *const w2 = set + (uint32_t)Fq * 256u + POLICY_HIDDEN, *const b2 = w2 + POLICY_MAX_ACTIONS * POLICY_HIDDEN;
+#pragma unroll
+    for (int c = 0; c < C; ++c) logit[c] = policy_butterfly(w2[c * POLICY_HIDDEN + lane] * hid) + b2[c];
+}
+// The policy part of one (position, agent) in float64 (ppo.py): the C logits, the action (inside 0 .. C-1), logp_old and the
+// advantage -> the gradient with respect to the logits, rounded to float32 once, and the statistics' terms 0, 2, 3 and 4.  The
+// softmax is policy_logprob's, so q_act here is the float64 whose rounding cz_logprob_device wrote: on the weights that played the
+// ratio is exactly 1.
+template <int C>
+__host__ __device__ __forceinline__ void policy_ppo_logit_grad(const float (&logit)[C], int action, double logp_old, double Adv, const PpoScales &K,
+                                                               float (&g)[C], double (&term)[PPO_TERMS]) {
+    float best = logit[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) best = logit[c] > best ? logit[c] : best;
+    double z[C], S = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        z[c] = (double)logit[c] - (double)best;
+        const double ex = policy_exp(z[c] > -64.0 ? z[c] : -64.0);
+        S = c == 0 ? ex : S + ex;
+    }
+    const double L = policy_log(S);
+    double q[C], p[C], qa = 0.0, acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        q[c] = z[c] - L;
+        p[c] = policy_exp(q[c] > -64.0 ? q[c] : -64.0);
+        const double pq = p[c] * q[c];
+        acc = c == 0 ? pq : acc + pq;
+        qa = action == c ? q[c] : qa;
+    }
+    const double H = -acc, lpn = (double)(float)qa;          // what cz_logprob_device writes for these logits
+    double d = lpn - logp_old;
+    d = d > -64.0 ? d : -64.0;
+    d = d < 64.0 ? d : 64.0;
+    const double ratio = policy_exp(d);
+    const bool clipped = (Adv > 0.0 && ratio > K.hi) || (Adv < 0.0 && ratio < K.lo);
+    const double glp = clipped ? 0.0 : -(Adv * ratio);
+#pragma unroll
+    for (int c = 0; c < C; ++c) g[c] = (float)(K.inv_p * (glp * ((action == c ? 1.0 : 0.0) - p[c]) + K.c_entropy * (p[c] * (q[c] + H))));
+    double rc = ratio > K.lo ? ratio : K.lo;
+    rc = rc < K.hi ? rc : K.hi;
+    const double s1 = ratio * Adv, s2 = rc * Adv;
+    term[0] = -(s1 < s2 ? s1 : s2);
+    term[2] = H;
+    term[3] = logp_old - lpn;
+    term[4] = clipped ? 1.0 : 0.0;
 }
 
 }  // namespace cz

@@ -1262,4 +1262,219 @@ __global__ __launch_bounds__(256) void k_logprob(const LogprobArgs G) {
     if (G.entropy) G.entropy[i] = (float)entropy;
 }
 
+// ---- PPO's gradients (cz_ppo_grad_device; definition: cooking_zoo_amd/ppo.py, device functions: cz_policy.h).  Three launches share
+// one argument block.  Every (position, agent) owns two pass slots - 0: the pass into its policy set, 1: the pass into its value set
+// where that is a pass of its own - and k_ppo_forward writes both slots of every (position, agent) on every call, so nothing of the
+// workspace is ever read that this call did not write.
+constexpr int PPO_SMALL = 12;                // a slot's scalars as 32-bit words: the float bits of g [8] and gv, the set (int32, -1: no pass), row * A + agent, 0
+constexpr int PPO_TILE = 32;                 // features per workgroup of k_ppo_outer, one accumulator register each.  The library carries 16, 32
+                                             // and 64 (CZ_PPO_TILE picks another, for tools/ppo_sizes.py); what each measures: profiles/r35/README.md
+// one set's floats in a partial: dW1 as [F][64] (lane j's stores coalesced), db1 [64], dW2 [8][64], db2 [8], dwv [64], dbv
+__host__ __device__ inline uint32_t ppo_set_floats(int F) {
+    return (uint32_t)F * POLICY_HIDDEN + POLICY_HIDDEN + POLICY_MAX_ACTIONS * POLICY_HIDDEN + POLICY_MAX_ACTIONS + POLICY_HIDDEN + 1u;
+}
+struct PpoArgs {
+    int64_t rows;                  // R: rows of the trajectory
+    int32_t positions;             // M: the minibatch
+    int32_t A, F, C, n_sets;       // n_sets: the loaded sets, the leading axis of every gradient
+    uint32_t packed, vpacked;      // policy_pack_sets / policy_pack_vsets
+    uint32_t used;                 // bit k: some agent's policy or value set is k
+    const int32_t *index;          // [M] or null
+    const float *obs32;            // [R][A][F]
+    const int32_t *actions;        // [R][A]
+    const float *logp_old, *adv, *ret;
+    const float *table;
+    PpoScales K;
+    // the workspace (cz_ppo_reserve)
+    double *terms;                 // [M * A][PPO_TERMS]
+    double *chunk_stats;           // [chunks][PPO_TERMS]
+    float *hid, *da;               // [slot][64]
+    uint32_t *small;               // [slot][PPO_SMALL]
+    float *partial;                // [chunk][n_sets][ppo_set_floats]
+    // the outputs, torch's layouts behind a leading axis of n_sets
+    float *gw1, *gb1, *gw2, *gb2, *gwv, *gbv;      // gwv / gbv may be null
+    double *stats;                 // [8] or null
+};
+// element `i` of a register array, i wave-varying
+template <class T, int N>
+__device__ __forceinline__ T ppo_pick(const T (&v)[N], int i) {
+    T out = v[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) out = i == k ? v[k] : out;
+    return out;
+}
+// One wavefront per (position, agent), the shape of k_value: the row goes to LDS, then policy_hidden, the logits and the value exactly
+// as the rollout computes them, the gradient with respect to the logits and the value in float64 (every lane computes all of it: the
+// wave's time is one lane's), and dh_j / da_j on lane j.  Writes the two slots and the statistics' terms.
+template <int C>
+__global__ __launch_bounds__(64) void k_ppo_forward(const PpoArgs G) {
+    const int lane = (int)threadIdx.x;
+    const uint32_t e = blockIdx.x, A = (uint32_t)G.A;
+    const uint32_t m = e / A, a = e - m * A;
+    const int64_t r = G.index ? (int64_t)G.index[m] : (int64_t)m;
+    const bool inside = r >= 0 && r < G.rows;
+    const uint32_t s = (G.packed >> (3u * a)) & 7u, vs = (G.vpacked >> (3u * a)) & 7u;
+    const int Fq = policy_quads(G.F);
+    double term[PPO_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    term[7] = !inside && a == 0u ? 1.0 : 0.0;
+    float g[POLICY_MAX_ACTIONS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float gv = 0.0f, h = 0.0f, hv = 0.0f, da0 = 0.0f, da1 = 0.0f;
+    int set0 = -1, set1 = -1;
+    bool both = false;
+    const size_t ra = inside ? (size_t)r * A + a : 0u;
+    if (inside && (s != 7u || vs != 7u)) {
+        float *const x = reinterpret_cast<float *>(policy_rows);
+        const float *const src = G.obs32 + ra * (size_t)G.F;
+        for (int f = lane; f < 4 * Fq; f += 64) x[f] = f < G.F ? src[f] : 0.0f;
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        const size_t per_set = policy_set_floats(G.F);
+        const float *const heads = G.table + policy_value_offset(G.F);
+        bool has_p = false, has_v = false;
+        if (s != 7u) {
+            const float *const set = G.table + (size_t)s * per_set;
+            h = policy_hidden(set, Fq, x, lane);
+            const int act = G.actions[ra];
+            if ((unsigned)act < (unsigned)C) {
+                has_p = true;
+                float logit[C], gc[C];
+                policy_all_logits<C>(set, Fq, h, lane, logit);
+                policy_ppo_logit_grad<C>(logit, act, (double)G.logp_old[ra], (double)G.adv[ra], G.K, gc, term);
+#pragma unroll
+                for (int c = 0; c < C; ++c) g[c] = gc[c];
+                term[5] = 1.0;
+            }
+        }
+        if (vs != 7u) {
+            hv = vs == s ? h : policy_hidden(G.table + (size_t)vs * per_set, Fq, x, lane);
+            const double dv = (double)policy_value(G.table, G.F, vs, hv, lane) - (double)G.ret[ra];
+            gv = (float)(G.K.inv_v * (G.K.c_value * dv));
+            term[1] = 0.5 * (dv * dv);
+            term[6] = 1.0;
+            has_v = true;
+        }
+        both = has_p && has_v && s == vs;
+        if (has_p) {
+            const float *const w2 = G.table + (size_t)s * per_set + (uint32_t)Fq * 256u + POLICY_HIDDEN;
+            float dh = 0.0f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) dh = __builtin_fmaf(g[c], w2[c * POLICY_HIDDEN + lane], dh);
+            if (both) dh = __builtin_fmaf(gv, heads[s * POLICY_HIDDEN + (uint32_t)lane], dh);
+            da0 = h > 0.0f ? dh : 0.0f;
+            set0 = (int)s;
+        }
+        if (has_v && !both) {
+            const float dh = __builtin_fmaf(gv, heads[vs * POLICY_HIDDEN + (uint32_t)lane], 0.0f);
+            da1 = hv > 0.0f ? dh : 0.0f;
+            set1 = (int)vs;
+        }
+    }
+    const size_t slot0 = (size_t)e * 2u, slot1 = slot0 + 1u;
+    if (set0 >= 0) { G.hid[slot0 * 64u + lane] = h; G.da[slot0 * 64u + lane] = da0; }
+    if (set1 >= 0) { G.hid[slot1 * 64u + lane] = hv; G.da[slot1 * 64u + lane] = da1; }
+    if (lane < PPO_SMALL) {
+        const uint32_t gl = __builtin_bit_cast(uint32_t, ppo_pick(g, lane)), gvb = __builtin_bit_cast(uint32_t, gv), rab = (uint32_t)ra;
+        // slot 0 carries g, and gv where the value part rides on the same pass; slot 1 carries gv alone (0u is +0.0f)
+        G.small[slot0 * PPO_SMALL + lane] = lane < 8 ? (set0 >= 0 ? gl : 0u) : lane == 8 ? (both ? gvb : 0u)
+                                            : lane == 9 ? (uint32_t)set0 : lane == 10 ? rab : 0u;
+        G.small[slot1 * PPO_SMALL + lane] = lane < 8 ? 0u : lane == 8 ? (set1 >= 0 ? gvb : 0u)
+                                            : lane == 9 ? (uint32_t)set1 : lane == 10 ? rab : 0u;
+    }
+    if (lane < PPO_TERMS) G.terms[(size_t)e * PPO_TERMS + lane] = ppo_pick(term, lane);
+}
+// Grid (chunk, feature tile, set), one wavefront, lane = hidden unit j.  Walks the chunk's slots in order and takes the passes into
+// its set: da_j from a coalesced load, the row's TILE features at a wave-uniform address, one fmaf per accumulator register.  Tile
+// 0 also accumulates dW2, db2, dwv, dbv and db1, and tile 0 of set 0 sums the chunk's statistics' terms, lane e < 8 entry e.
+template <int TILE>
+__global__ __launch_bounds__(64) void k_ppo_outer(const PpoArgs G) {
+    const int lane = (int)threadIdx.x;
+    const uint32_t chunk = blockIdx.x, tile = blockIdx.y, k = blockIdx.z, A = (uint32_t)G.A, F = (uint32_t)G.F;
+    const uint32_t m0 = chunk * PPO_CHUNK, left = (uint32_t)G.positions - m0, count = left < (uint32_t)PPO_CHUNK ? left : (uint32_t)PPO_CHUNK;
+    if ((G.used >> k) & 1u) {
+        const uint32_t f0 = tile * TILE, nt = F - f0 < (uint32_t)TILE ? F - f0 : (uint32_t)TILE;
+        float acc[TILE], aw2[POLICY_MAX_ACTIONS], ab2[POLICY_MAX_ACTIONS], awv = 0.0f, abv = 0.0f, ab1 = 0.0f;
+#pragma unroll
+        for (int t = 0; t < TILE; ++t) acc[t] = 0.0f;
+#pragma unroll
+        for (int c = 0; c < POLICY_MAX_ACTIONS; ++c) aw2[c] = ab2[c] = 0.0f;
+        const size_t slot_begin = (size_t)m0 * A * 2u, slot_end = slot_begin + (size_t)count * A * 2u;
+        for (size_t slot = slot_begin; slot < slot_end; ++slot) {
+            const uint32_t *const sm = G.small + slot * PPO_SMALL;
+            if (sm[9] != k) continue;
+            const float da = G.da[slot * 64u + lane];
+            const float *const x = G.obs32 + (size_t)sm[10] * F + f0;
+            if (nt == (uint32_t)TILE) {
+#pragma unroll
+                for (int t = 0; t < TILE; ++t) acc[t] = __builtin_fmaf(da, x[t], acc[t]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < TILE; ++t)
+                    if ((uint32_t)t < nt) acc[t] = __builtin_fmaf(da, x[t], acc[t]);
+            }
+            if (tile == 0u) {
+                const float h = G.hid[slot * 64u + lane], gv = __builtin_bit_cast(float, sm[8]);
+#pragma unroll
+                for (int c = 0; c < POLICY_MAX_ACTIONS; ++c) {
+                    const float gc = __builtin_bit_cast(float, sm[c]);
+                    aw2[c] = __builtin_fmaf(gc, h, aw2[c]);
+                    ab2[c] = ab2[c] + gc;
+                }
+                awv = __builtin_fmaf(gv, h, awv);
+                abv = abv + gv;
+                ab1 = ab1 + da;
+            }
+        }
+        float *const P = G.partial + ((size_t)chunk * (uint32_t)G.n_sets + k) * ppo_set_floats(G.F);
+#pragma unroll
+        for (int t = 0; t < TILE; ++t)
+            if ((uint32_t)t < nt) P[(size_t)(f0 + t) * 64u + lane] = acc[t];
+        if (tile == 0u) {
+            float *const rest = P + (size_t)F * 64u;
+            rest[lane] = ab1;
+#pragma unroll
+            for (int c = 0; c < POLICY_MAX_ACTIONS; ++c) rest[64 + c * 64 + lane] = aw2[c];
+            if (lane < POLICY_MAX_ACTIONS) rest[64 + 512 + lane] = ppo_pick(ab2, lane);
+            rest[64 + 512 + 8 + lane] = awv;
+            if (lane == 0) rest[64 + 512 + 8 + 64] = abv;
+        }
+    }
+    if (tile == 0u && k == 0u && lane < PPO_TERMS) {
+        const double *const t = G.terms + (size_t)m0 * A * PPO_TERMS + lane;
+        double acc = 0.0;
+        for (uint32_t i = 0; i < count * A; ++i) acc = acc + t[(size_t)i * PPO_TERMS];
+        G.chunk_stats[(size_t)chunk * PPO_TERMS + lane] = acc;
+    }
+}
+// One thread per float of the partials' per-set layout (coalesced reads, chunk after chunk), summed in ascending chunk order and
+// written where torch keeps it; sets nobody used get zeros.  Eight more threads finish the statistics.
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_ppo_reduce(const PpoArgs G) {
+    const uint32_t PS = ppo_set_floats(G.F), total = PS * (uint32_t)G.n_sets, idx = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t chunks = ((uint32_t)G.positions + PPO_CHUNK - 1u) / PPO_CHUNK, F = (uint32_t)G.F, C = (uint32_t)G.C;
+    if (idx < total) {
+        const uint32_t k = idx / PS, o = idx - k * PS;
+        float v = 0.0f;
+        if ((G.used >> k) & 1u) {
+            const float *const p = G.partial + (size_t)k * PS + o;
+            const size_t stride = (size_t)PS * (uint32_t)G.n_sets;
+            v = p[0];
+#pragma unroll 8
+            for (uint32_t ch = 1; ch < chunks; ++ch) v = v + p[ch * stride];
+        }
+        const uint32_t w1_end = F * 64u, b1_end = w1_end + 64u, w2_end = b1_end + 512u, b2_end = w2_end + 8u, wv_end = b2_end + 64u;
+        if (o < w1_end) G.gw1[((size_t)k * 64u + (o & 63u)) * F + (o >> 6)] = v;
+        else if (o < b1_end) G.gb1[k * 64u + (o - w1_end)] = v;
+        else if (o < w2_end) { const uint32_t q = o - b1_end, c = q >> 6; if (c < C) G.gw2[((size_t)k * C + c) * 64u + (q & 63u)] = v; }
+        else if (o < b2_end) { const uint32_t c = o - w2_end; if (c < C) G.gb2[k * C + c] = v; }
+        else if (o < wv_end) { if (G.gwv) G.gwv[k * 64u + (o - b2_end)] = v; }
+        else if (G.gbv) G.gbv[k] = v;
+    } else if (idx < total + PPO_TERMS && G.stats) {
+        const uint32_t e = idx - total;
+        double v = G.chunk_stats[e];
+#pragma unroll 8
+        for (uint32_t ch = 1; ch < chunks; ++ch) v = v + G.chunk_stats[(size_t)ch * PPO_TERMS + e];
+        G.stats[e] = e == 1u ? G.K.inv_v * v : e == 0u || (e >= 2u && e <= 4u) ? G.K.inv_p * v : v;
+    }
+}
+
 }  // namespace cz

@@ -76,7 +76,8 @@ def fmaf32(a, b, c):
 
 
 def cz_exp(z):
-    """exp on [-64, 0] in plain float64 arithmetic (within 2.2e-16 relative of np.exp there)"""
+    """exp on [-64, 64] in plain float64 arithmetic (within 2.2e-16 relative of np.exp there; the sampler and the log-probabilities
+    use [-64, 0], the ratio of ppo.py the whole range)"""
     z = np.asarray(z, np.float64)
     k = np.floor(z * _LOG2E + 0.5)
     r = (z - k * _LN2_HI) - k * _LN2_LO

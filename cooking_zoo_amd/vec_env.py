@@ -1205,6 +1205,38 @@ class CookingVecEnv:
         _native.check(self._h, _native.lib().cz_logprob_device(self._h, self._count(rows), p(d_logits), p(d_actions),
                                                                _policy.pack_sets(sets, self.num_agents), p(d_logp), p(d_entropy)))
 
+    # ------------------------------------------------------------------ PPO's update phase (cooking_zoo_amd/ppo.py)
+    def ppo_reserve(self, max_positions):
+        """allocate the workspace of `ppo_grad_device` for minibatches of up to `max_positions` positions over the weight sets
+        loaded now (`load_policy` first).  It allocates, so call it outside a capture; asking for no more than is reserved does
+        nothing -> the positions reserved"""
+        _native.check(self._h, _native.lib().cz_ppo_reserve(self._h, int(max_positions)))
+        return int(_native.lib().cz_ppo_reserved(self._h))
+
+    def ppo_grad_device(self, d_obs32, d_actions, d_logp_old, d_adv, d_ret, grads, d_index=None, sets=(0, 0, 0, 0), vsets=None, clip=0.2,
+                        c_value=0.5, c_entropy=0.01, d_stats=None, rows=None):
+        """the gradient of PPO's clipped-surrogate loss with value and entropy terms over a minibatch of a trajectory in device
+        memory, three launches, stream-ordered and capturable, bit for bit `ppo.host_ppo_grad`: `d_obs32` float32 [rows, A, F],
+        `d_actions` int32 [rows, A], `d_logp_old` / `d_adv` / `d_ret` float32 [rows, A] - what `rollout_policy_value`,
+        `logprob_device` and `gae_device` wrote, flattened to rows = T * N (None: the handle's N).  `d_index` int32 [M]: the
+        minibatch, position m uses row index[m] (a `torch.randperm` slice as int32; an index outside the rows is counted in
+        stats[7] and otherwise ignored); None: every row once.  `sets` / `vsets`: agent a's policy and value set, None / 0xFF =
+        none; `vsets=None` means "as `sets`", the shared trunk.  `grads`: six float32 buffers in torch.nn.Linear's layouts behind a
+        leading axis of `policy_sets` - gw1 [n, 64, F], gb1 [n, 64], gw2 [n, C, 64], gb2 [n, C], gwv [n, 64] (or [n, 1, 64]), gbv
+        [n, 1] - anything with `data_ptr()`, so a stacked parameter's `.grad`; the last two may be None when no agent has a value
+        set.  Sets no agent uses get zeros.  `d_stats` float64 [8] (optional): surrogate loss, value loss, entropy, KL estimate,
+        clipped fraction, policy parts, value parts, indices out of range.  Advantage normalisation is the caller's.
+        `ppo_reserve` must have covered M positions."""
+        n = self._count(rows)
+        vs = sets if vsets is None else vsets
+        if len(grads) != 6:
+            raise ValueError(f"ppo_grad_device: grads holds {len(grads)} buffers, not the six of (gw1, gb1, gw2, gb2, gwv, gbv)")
+        m = n if d_index is None else int(d_index.shape[0])
+        p = _dev_ptr
+        _native.check(self._h, _native.lib().cz_ppo_grad_device(
+            self._h, n, m, p(d_index), p(d_obs32), p(d_actions), p(d_logp_old), p(d_adv), p(d_ret), _policy.pack_sets(sets, self.num_agents),
+            _policy.pack_sets(vs, self.num_agents), float(clip), float(c_value), float(c_entropy), *(p(g) for g in grads), p(d_stats)))
+
     def sync(self):
         _native.check(self._h, _native.lib().cz_sync(self._h))
 

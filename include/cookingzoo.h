@@ -752,6 +752,38 @@ int cz_gae_device(cz_handle h, int32_t T, int64_t env_count, const double *d_rew
 int cz_logprob_device(cz_handle h, int64_t rows, const float *d_logits, const int32_t *d_actions, uint32_t sets,
                       float *d_logp, float *d_entropy);
 
+/* ---- PPO's update phase: the clipped-surrogate loss with value and entropy terms, differentiated by the library over the weight sets
+ * it plays with, in the rollout's own arithmetic (definition and numpy model: cooking_zoo_amd/ppo.py, which numpy reproduces bit for
+ * bit; zeros compare equal whatever their sign; NaN, infinities and subnormal intermediates are NOT pinned).  The forward is
+ * cz_rollout_policy_value's and the softmax cz_logprob_device's, so on the weights that played ratio == 1.0 exactly.
+ *
+ * cz_ppo_reserve: the workspace for minibatches of up to max_positions positions over the sets loaded now - per (position, agent)
+ * two pass slots and the statistics' terms, per (chunk of cz_ppo_chunk() positions, loaded set) one partial gradient.  It allocates,
+ * so call it outside a stream capture; a call that asks for no more than is reserved does nothing.  Refused: no table loaded,
+ * max_positions < 1 or past 2^30 / A, an allocation inside a capture.  cz_ppo_reserved: the positions reserved (0: none). */
+int cz_ppo_reserve(cz_handle h, int64_t max_positions);
+int64_t cz_ppo_reserved(cz_handle h);
+int32_t cz_ppo_chunk(void);                    /* 64: the reduction order of ppo.py is in chunks of this many positions */
+/* cz_ppo_grad_device: d_obs32 float32 [rows][A][F], d_actions int32 [rows][A], d_logp_old / d_adv / d_ret float32 [rows][A] - a
+ * trajectory flattened to rows = T * N.  d_index int32 [positions] is the minibatch, position m uses row d_index[m] (rows may repeat;
+ * an index outside 0 .. rows-1 contributes nothing and is counted in d_stats[7]); NULL means positions == rows and row m.  `sets` /
+ * `vsets`: agent a's policy and value set in byte a, 0xFF = none, as in cz_rollout_policy_value.  Per (position, agent): the policy
+ * part if the agent has a set and its action is inside 0 .. C-1 - ratio = cz_exp((float)q_act - logp_old), q_act rounded to the float32 cz_logprob_device writes, clipped where it left [1 - clip,
+ * 1 + clip] on the advantage's side - and the value part c_value * 0.5 * (v - ret)^2; both averaged over positions and agents with a
+ * set; the entropy bonus c_entropy * H.  Advantage normalisation is the caller's.  The gradients come in torch.nn.Linear's layouts
+ * behind a leading axis of cz_policy_sets(h) - the stacking the two loads take, so a stacked parameter's .grad can be the buffer:
+ * d_gw1 [n][64][F], d_gb1 [n][64], d_gw2 [n][C][64], d_gb2 [n][C], d_gwv [n][64], d_gbv [n][1] (the last two may be NULL when every
+ * byte of `vsets` is 0xFF); sets no agent uses get zeros.  The sums run in float32 fmaf chains in a fixed order, chunk by chunk
+ * (ppo.py): independent of grid shape and device.  d_stats float64 [8] (may be NULL): surrogate loss, value loss, entropy, the
+ * plain KL estimate, clipped fraction, policy parts, value parts, indices out of range.  Three launches on the handle's stream - no
+ * copy, no wait, no allocation, legal inside a stream capture of the caller; no record is read.  Refused: no table loaded, a set
+ * past the loaded ones, every agent at 0xFF in both words, positions < 1 or past the reserved ones, rows < 1, d_index == NULL with
+ * positions != rows, a NULL required pointer, clip / c_value / c_entropy negative or NaN, more sets loaded than were reserved for. */
+int cz_ppo_grad_device(cz_handle h, int64_t rows, int64_t positions, const int32_t *d_index /* may be NULL */,
+                       const float *d_obs32, const int32_t *d_actions, const float *d_logp_old, const float *d_adv, const float *d_ret,
+                       uint32_t sets, uint32_t vsets, double clip, double c_value, double c_entropy,
+                       float *d_gw1, float *d_gb1, float *d_gw2, float *d_gb2, float *d_gwv, float *d_gbv, double *d_stats);
+
 /* the action the on-device stream draws (host mirror, for parity tests) */
 uint32_t cz_action(uint64_t seed, int64_t env_global, int32_t agent, uint32_t step, uint32_t n_actions);
 /* the layout an env draws for its k-th episode under auto_reset */
