@@ -302,6 +302,7 @@ struct cz_handle_s {
     DevMem<unsigned char> d_ppo;           // cz_ppo_reserve: the workspace of cz_ppo_grad_device (ppo_carve), for ...
     int64_t ppo_positions = 0;             // ... minibatches of up to this many positions (0: none reserved) over ...
     int32_t ppo_sets = 0;                  // ... this many loaded sets
+    DevMem<double> d_adam;                 // cz_adam_reserve: the chunk partials of cz_adam_step_device for POLICY_MAX_SETS sets, then its control words (cz_adam.h)
     DevMem<uint32_t> d_partner;            // cz_load_partner_table: [n_partner][PARTNER_ROW_WORDS], then the bad-recipe counter (8 bytes)
     int n_partner = 0;                     // rows in use (0: none, or dropped by cz_load_recipes)
     int partner_rows_alloc = 0;            // rows the allocation was made for (the counter lies behind them)
@@ -2612,6 +2613,70 @@ extern "C" int cz_ppo_grad_device(cz_handle h, int64_t rows, int64_t positions, 
     HIPCHK(h, hipGetLastError());
     const unsigned elements = ppo_set_floats(F) * (unsigned)G.n_sets + PPO_TERMS;
     hipLaunchKernelGGL((k_ppo_reduce<0>), dim3((elements + 255u) / 256u), dim3(256), 0, h->stream, G);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// ---- the optimiser (definition: cooking_zoo_amd/adam.py; k_adam_norm / k_adam_finish / k_adam_update in cz_adam.h)
+extern "C" int32_t cz_sizeof_params(void) { return (int32_t)sizeof(cz_params); }
+extern "C" int32_t cz_adam_chunk(void) { return ADAM_CHUNK; }
+// Allocates what cz_adam_step_device needs beside the caller's arrays: one float64 per chunk of POLICY_MAX_SETS sets' tensors and the
+// control words behind them.  F and C are fixed by cz_create, so one allocation serves the handle's life: outside a capture the first
+// time, nothing afterwards.
+extern "C" int cz_adam_reserve(cz_handle h) {
+    if (!h) return fail(nullptr, "null handle");
+    if (h->d_adam) return 0;
+    if (caller_capturing(h)) return fail(h, "cz_adam_reserve: the first call allocates the partials: call it outside the capture");
+    if (set_device(h)) return 1;
+    const size_t words = (size_t)adam_partial_stride(h->P.F, cz_num_actions(h)) * POLICY_MAX_SETS + ADAM_CTL_WORDS;
+    HIPCHK(h, hipMalloc(h->d_adam.out(), words * sizeof(double)));
+    return 0;
+}
+static_assert(sizeof(cz_params) == sizeof(AdamGroup), "cz_params is the six pointers of an AdamGroup, in its order");
+// One optimiser step on the caller's arrays (adam.host_adam_step): global-norm clipping over the masked sets' gradients, then Adam /
+// AdamW on parameters, first and second moments - float32 in torch.nn.Linear's layouts behind a leading axis of cz_policy_sets(h), the
+// four structs host memory read during the call - with the state float64 [8] in device memory.  Unless CZ_ADAM_KEEP_TABLE is set the
+// new parameters of the masked sets are written into the weight table by the same launch, the value heads too when the value tensors
+// are given.  Three launches on the handle's stream: nothing is copied, waited for or allocated (legal inside a capture of the caller).
+extern "C" int cz_adam_step_device(cz_handle h, uint32_t set_mask, const cz_params *params, const cz_params *grads, const cz_params *exp_avg,
+                                   const cz_params *exp_avg_sq, double *d_state, double lr, const double *d_lr, double beta1, double beta2,
+                                   double eps, double weight_decay, double max_norm, uint32_t flags) {
+    if (!h) return fail(nullptr, "null handle");
+    if (!h->d_policy || h->n_policy_sets == 0) return fail(h, "cz_adam_step_device: no weight table loaded (cz_load_policy_device)");
+    if (!h->d_adam) return fail(h, "cz_adam_step_device: no partials reserved (cz_adam_reserve)");
+    if (flags & ~(uint32_t)CZ_ADAM_KEEP_TABLE) return fail(h, "cz_adam_step_device: unknown flag bits 0x%x", flags & ~(uint32_t)CZ_ADAM_KEEP_TABLE);
+    if (set_mask == 0u) return fail(h, "cz_adam_step_device: set_mask is empty");
+    if (set_mask >> h->n_policy_sets) return fail(h, "cz_adam_step_device: set_mask 0x%x names a set past the %d loaded", set_mask, h->n_policy_sets);
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !d_state) return fail(h, "cz_adam_step_device: a group or the state pointer is null");
+    const cz_params *const groups[4] = {params, grads, exp_avg, exp_avg_sq};
+    int value_pointers = 0;
+    for (const cz_params *g : groups) {
+        if (!g->w1 || !g->b1 || !g->w2 || !g->b2) return fail(h, "cz_adam_step_device: a pointer of the policy's four tensors is null");
+        value_pointers += (g->wv != nullptr) + (g->bv != nullptr);
+    }
+    if (value_pointers != 0 && value_pointers != 8) return fail(h, "cz_adam_step_device: the value tensors (wv, bv) are present in all four groups or in none; %d of 8 pointers are given", value_pointers);
+    const bool keep = (flags & CZ_ADAM_KEEP_TABLE) != 0u;
+    if (value_pointers && !keep && (set_mask >> h->n_value_sets)) return fail(h, "cz_adam_step_device: value tensors are given, but set_mask 0x%x names a set past the %d value heads loaded (cz_load_value_device, or CZ_ADAM_KEEP_TABLE)", set_mask, h->n_value_sets);
+    if (!(lr >= 0.0)) return fail(h, "cz_adam_step_device: lr is %g, not >= 0", lr);
+    if (!(weight_decay >= 0.0)) return fail(h, "cz_adam_step_device: weight_decay is %g, not >= 0", weight_decay);
+    if (!(max_norm >= 0.0)) return fail(h, "cz_adam_step_device: max_norm is %g, not >= 0", max_norm);
+    if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(h, "cz_adam_step_device: beta1 is %g, not in [0, 1)", beta1);
+    if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(h, "cz_adam_step_device: beta2 is %g, not in [0, 1)", beta2);
+    if (!(eps > 0.0)) return fail(h, "cz_adam_step_device: eps is %g, not > 0", eps);
+    if (set_device(h)) return 1;
+    AdamArgs A{};
+    A.F = h->P.F; A.C = cz_num_actions(h); A.n_sets = h->n_policy_sets; A.with_value = value_pointers ? 1 : 0; A.set_mask = set_mask;
+    const auto group = [](const cz_params &g) { return AdamGroup{{g.w1, g.b1, g.w2, g.b2, g.wv, g.bv}}; };
+    A.P = group(*params); A.G = group(*grads); A.M = group(*exp_avg); A.V = group(*exp_avg_sq);
+    A.table = keep ? nullptr : h->d_policy.get();
+    A.state = d_state; A.d_lr = d_lr; A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.omb1 = 1.0 - beta1; A.omb2 = 1.0 - beta2;
+    A.eps = eps; A.wd = weight_decay; A.max_norm = max_norm; A.partials = h->d_adam.get();
+    const unsigned sets = (unsigned)A.n_sets, stride = adam_partial_stride(A.F, A.C);
+    hipLaunchKernelGGL((k_adam_norm<0>), dim3(adam_set_chunks(A.F, A.C, A.with_value), sets), dim3(ADAM_LANES), 0, h->stream, A);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL((k_adam_finish<0>), dim3(1), dim3(ADAM_LANES), (size_t)stride * POLICY_MAX_SETS * sizeof(double), h->stream, A);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL((k_adam_update<0>), dim3((adam_set_elements(A.F, A.C, A.with_value) + ADAM_LANES - 1u) / ADAM_LANES, sets), dim3(ADAM_LANES), 0, h->stream, A);
     HIPCHK(h, hipGetLastError());
     return 0;
 }

@@ -1478,3 +1478,5 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(const PpoArgs G) {
 }
 
 }  // namespace cz
+
+#include "cz_adam.h"

@@ -65,6 +65,12 @@ def _dev_ptr(b):
     return C.c_void_p(int(b))
 
 
+def _address(b):
+    """`_dev_ptr` as a plain integer (None stays None): what a pointer field of a ctypes structure takes"""
+    q = _dev_ptr(b)
+    return q.value if isinstance(q, C.c_void_p) else q
+
+
 def resolve_recipe_tables(recipes):
     """-> (registry dict, names list).  Same rule as cooking_env.py:100-105: a non-empty user
     RECIPE_STORE replaces the default book."""
@@ -1236,6 +1242,44 @@ class CookingVecEnv:
         _native.check(self._h, _native.lib().cz_ppo_grad_device(
             self._h, n, m, p(d_index), p(d_obs32), p(d_actions), p(d_logp_old), p(d_adv), p(d_ret), _policy.pack_sets(sets, self.num_agents),
             _policy.pack_sets(vs, self.num_agents), float(clip), float(c_value), float(c_entropy), *(p(g) for g in grads), p(d_stats)))
+
+    # ------------------------------------------------------------------ the optimiser (cooking_zoo_amd/adam.py)
+    def adam_reserve(self):
+        """allocate the chunk partials of `adam_step_device` (once per handle; it allocates, so call it outside a capture)"""
+        _native.check(self._h, _native.lib().cz_adam_reserve(self._h))
+
+    def adam_step_device(self, params, grads, exp_avg, exp_avg_sq, d_state, sets=None, lr=1e-3, d_lr=None, betas=(0.9, 0.999), eps=1e-8,
+                         weight_decay=0.0, max_norm=0.0, keep_table=False):
+        """one optimiser step on the caller's device arrays, three launches, stream-ordered and capturable, bit for bit
+        `adam.host_adam_step`: global-norm clipping of the gradients to `max_norm` (0: none; `clip_grad_norm_`'s formula), then Adam,
+        or AdamW with `weight_decay` != 0.  The four groups are six-sequences (w1, b1, w2, b2, wv, bv) of float32 buffers in
+        torch.nn.Linear's layouts behind a leading axis of `policy_sets` - anything with `data_ptr()`, so stacked parameters, their
+        `.grad` (what `ppo_grad_device` wrote) and two tensors of zeros for the moments, or `alloc` buffers; the last two entries
+        may be None, in all four groups at once.  `d_state` float64 [8] on the device, `adam.fresh_state()` to begin with: steps,
+        the running products of the betas, the last gradient norm and clip coefficient, calls skipped (a gradient that is not
+        finite changes nothing and is counted), the learning rate used.  `sets`: the set indices that take part, None = every
+        loaded set; arrays of the others are neither read nor written.  `d_lr` float64 [1] on the device replaces `lr` (a
+        schedule inside a captured graph).  The masked sets of the weight table - and their value heads, when wv and bv are
+        given - become the new parameters in the same launch, so no `load_policy` / `load_value` follows; `keep_table=True`
+        leaves the table alone.  `adam_reserve` first."""
+        groups = []
+        for name, grp in (("params", params), ("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            grp = list(grp)
+            if len(grp) != 6:
+                raise ValueError(f"adam_step_device: {name} holds {len(grp)} buffers, not the six of (w1, b1, w2, b2, wv, bv)")
+            groups.append(_native.CzParams(*(_address(b) for b in grp)))
+        if sets is None:
+            mask = (1 << max(self.policy_sets, 0)) - 1
+        else:
+            mask = 0
+            for k in sets:
+                if not 0 <= int(k) < 32:
+                    raise ValueError(f"adam_step_device: set {k} is not in 0..31")
+                mask |= 1 << int(k)
+        b1, b2 = betas
+        _native.check(self._h, _native.lib().cz_adam_step_device(
+            self._h, mask, *(C.byref(g) for g in groups), _dev_ptr(d_state), float(lr), _dev_ptr(d_lr), float(b1), float(b2), float(eps),
+            float(weight_decay), float(max_norm), _native.CZ_ADAM_KEEP_TABLE if keep_table else 0))
 
     def sync(self):
         _native.check(self._h, _native.lib().cz_sync(self._h))

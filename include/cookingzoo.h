@@ -784,6 +784,41 @@ int cz_ppo_grad_device(cz_handle h, int64_t rows, int64_t positions, const int32
                        uint32_t sets, uint32_t vsets, double clip, double c_value, double c_entropy,
                        float *d_gw1, float *d_gb1, float *d_gw2, float *d_gb2, float *d_gwv, float *d_gbv, double *d_stats);
 
+/* ---- The optimiser: global-norm gradient clipping and Adam / AdamW on the caller's arrays, in a pinned float64 arithmetic that numpy
+ * reproduces bit for bit (definition and numpy models: cooking_zoo_amd/adam.py; zeros compare equal whatever their sign; NaN and
+ * subnormal intermediates are NOT pinned).  The library keeps no optimiser state: parameters, gradients, first and second moments are
+ * four groups of six float32 tensors in torch.nn.Linear's layouts behind a leading axis of cz_policy_sets(h) - w1 [n][64][F], b1 [n][64],
+ * w2 [n][C][64], b2 [n][C], wv [n][64], bv [n][1], what cz_ppo_grad_device writes and the two loads take - and d_state is float64 [8] in
+ * device memory: steps taken, the running products of the beta1 and beta2 values used, the last call's gradient norm and clip
+ * coefficient, calls skipped, the learning rate last used, one word never written; a fresh state is {0, 1, 1, 0, 0, 0, 0, 0}.
+ *
+ * cz_adam_reserve: one float64 per chunk of cz_adam_chunk() gradient elements for four sets.  It allocates, so call it outside a
+ * stream capture; every later call does nothing.
+ * cz_adam_step_device: bit k of set_mask set means set k takes part; every array of another set is neither read nor written.  The
+ * squared norm of the masked gradients is summed in a fixed order (chunks of 1024, a butterfly within a chunk, one serial chain over
+ * the chunks: adam.py), independent of grid shape and device.  A total that is not finite skips the call: parameters, moments and
+ * table stay byte for byte, word 4 of the state becomes 0.0 and word 5 counts it.  Otherwise coef = max_norm == 0 ? 1 : min(1,
+ * max_norm / (norm + 1e-6)), the moments advance on coef * g, bias correction uses the running products, weight_decay != 0 decays
+ * the parameter by lr * weight_decay first (decoupled, AdamW), and the parameter moves by lr * mh / (sqrt(vh) + eps).  lr is *d_lr where
+ * d_lr is given (device memory: a schedule inside a captured graph), the by-value argument otherwise.  The moments are stored as
+ * float32 and read back as stored, so a run restarted from saved buffers continues bit for bit.  Unless CZ_ADAM_KEEP_TABLE is set,
+ * the masked sets of the weight table - and their value heads, when the value tensors are given - become the new parameters in the
+ * same launch, byte for byte what cz_load_policy_device / cz_load_value_device of the updated arrays would leave: no reload follows.
+ * The four structs are host memory, read during the call; wv and bv are given in all four or in none.  Three launches on the
+ * handle's stream - no copy, no wait, no allocation, legal inside a stream capture of the caller.  Refused: no table loaded, no
+ * cz_adam_reserve, set_mask empty or with a bit at or past cz_policy_sets, value tensors with a masked set at or past cz_value_sets
+ * (unless CZ_ADAM_KEEP_TABLE), value pointers present in some groups only, any other NULL pointer, lr / weight_decay / max_norm
+ * negative or NaN, a beta outside [0, 1) or NaN, eps <= 0 or NaN, unknown flag bits. */
+typedef struct cz_params { float *w1, *b1, *w2, *b2, *wv, *bv; } cz_params;   /* cz_sizeof_params() */
+#define CZ_ADAM_KEEP_TABLE 1u
+int32_t cz_sizeof_params(void);
+int32_t cz_adam_chunk(void);                   /* 1024: the norm's summation order of adam.py is in chunks of this many elements */
+int cz_adam_reserve(cz_handle h);
+int cz_adam_step_device(cz_handle h, uint32_t set_mask, const cz_params *params, const cz_params *grads,
+                        const cz_params *exp_avg, const cz_params *exp_avg_sq, double *d_state,
+                        double lr, const double *d_lr /* may be NULL */, double beta1, double beta2, double eps,
+                        double weight_decay, double max_norm, uint32_t flags);
+
 /* the action the on-device stream draws (host mirror, for parity tests) */
 uint32_t cz_action(uint64_t seed, int64_t env_global, int32_t agent, uint32_t step, uint32_t n_actions);
 /* the layout an env draws for its k-th episode under auto_reset */
